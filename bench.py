@@ -2,6 +2,7 @@
 """bench.py -- FAD hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W        (N>1: launched by torch.distributed.run)
+                    [--dump-outputs DIR]                 (the last timed step's score, its terms and both sets' mu / Sigma -> DIR/*.npy)
 
 Workload (BASELINE.json configs[2], "C3"): two synthetic float16 embedding matrices of
 [100000 x 512] per GPU, RESIDENT IN HBM when the timed region starts.  One *step* is one pass of the
@@ -680,6 +681,23 @@ def extra_host(fadtk_amd, a_host, b_host, fad_ref):
                     "h2d_GBps_per_set divides the set's bytes by the WHOLE calc_embd_statistics call"}
 
 
+def dump_outputs(out_dir, hip, fad, diag, lane):
+    """--dump-outputs DIR: what the timed path handed its caller for its LAST step, as float64 .npy files -- the score, its terms
+    (fad = mean_term + tr1 + tr2 - 2 tr_sqrt) and the statistics (mu, Sigma) of both sets the chain consumed, finalised by the library
+    from a copy of the step's packed statistics (the timed handles are left as they are).  4.2 MB at D = 512.  The inputs of a run
+    are seeded (make_sets), so two builds given the same arguments can be compared file for file."""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    arrays = {"fad": np.array([fad], dtype=np.float64),
+              "fad_terms": np.array([diag["mean_term"], diag["tr1"], diag["tr2"], diag["tr_sqrt"]], dtype=np.float64)}
+    for tag, h in (("a", lane.ma), ("b", lane.mb)):
+        with hip.Moments(h.d, h.device) as t:
+            mu, cov, _ = t.import_(h.export()).finalize()
+        arrays[f"mu_{tag}"], arrays[f"cov_{tag}"] = mu, cov
+    for name, arr in arrays.items():
+        np.save(out / f"{name}.npy", arr)
+
+
 def torchrun_command(gpus, argv):
     """`python bench.py --gpus N ...` from a plain shell: the command that starts the N ranks (one per GPU, RCCL), exactly as
     fadtk_amd/cli.py:_relaunch does for the product's --gpus (reference: the spawn pool of fadtk/fad_batch.py:43-48)."""
@@ -729,6 +747,9 @@ def main():
     ap.add_argument("--chain-cus", type=int, default=0,
                     help="experiment (profiles/r04*_streams.txt): confine the square-root chains to this many CUs per XCD (CU-masked "
                          "streams) and the moments kernels to the others; 0 = no masks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (score, its terms, both sets' mu and Sigma) "
+                         "as DIR/<name>.npy, float64 (rank 0)")
     args = ap.parse_args()
     if int(args.batch) > 0 and not int(args.group) and not args.multi_stream:
         args.single_stream = True                                        # the batched schedule's default layout
@@ -858,6 +879,7 @@ def main():
     ma, mb = lanes[0].ma, lanes[0].mb
 
     host_s = [0.0, 0.0, 0.0]            # host seconds spent enqueueing moments / enqueueing chains / waiting for + collecting scores
+    last_lane = [None]                  # the lane whose score was collected last: the last step of a run_steps call (--dump-outputs)
 
     def run_steps_lanes(count, marks=None, rotate=True, lanes=None):
         lanes = all_lanes if lanes is None else lanes
@@ -874,6 +896,7 @@ def main():
             t = pc()
             out = lane.collect()
             host_s[2] += pc() - t
+            last_lane[0] = lane
             if marks is not None:
                 marks.append(time.perf_counter())
 
@@ -915,6 +938,7 @@ def main():
             for lane in grp[:m]:
                 if lane.job is not None:
                     t = pc(); out = lane.collect(); host_s[2] += pc() - t
+                    last_lane[0] = lane
                     if marks is not None:
                         marks.append(pc())
             t = pc()
@@ -934,6 +958,7 @@ def main():
             for lane in lanes[(gg % NGRP) * G:(gg % NGRP) * G + G]:
                 if lane.job is not None:
                     t = pc(); out = lane.collect(); host_s[2] += pc() - t
+                    last_lane[0] = lane
                     if marks is not None:
                         marks.append(pc())
         return out
@@ -979,6 +1004,7 @@ def main():
                 vals, diags = bjobs[q][0].result_arrays()               # (every score of the batch; the diagnostics stay ctypes records)
                 host_s[2] += pc() - t
                 out = (float(vals[-1]), diags[len(vals) - 1].as_dict())
+                last_lane[0] = blanes[q][bjobs[q][1] - 1]
                 if marks is not None:
                     now = pc()
                     marks.extend([now] * bjobs[q][1])
@@ -1082,6 +1108,8 @@ def main():
     host_timed = list(host_s)
     fence()
     elapsed = time.perf_counter() - marks[0]
+    if args.dump_outputs and rank == 0:                                  # (before anything below touches the lanes' statistics)
+        dump_outputs(args.dump_outputs, hip, fad, diag, last_lane[0])
     per_rank_s, allreduce_alone = None, None
     if distributed:
         mine = torch.tensor([elapsed], dtype=torch.float64, device=device)

@@ -175,6 +175,42 @@ def test_bench_starts_its_own_ranks_when_world_size_is_unset():
     assert out["roofline"]["frac"] > 0
 
 
+def test_bench_dump_outputs_holds_the_last_timed_step(tmp_path):
+    """`bench.py --dump-outputs DIR` writes what the last timed step computed: its score, the score's terms and both sets'
+    (mu, Sigma), float64.  With --steps 5 that step feeds pair 0 (step i feeds pair i % 4), the golden G7 pair: the statistics
+    must be those of the host pair, the score the line's `fad_last_timed_step` and the reference's; a second run writes the same."""
+    import json
+    import subprocess
+    runs = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "5", "--warmup", "1", "--timed-only", "--dump-outputs", str(d)],
+                           env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"), capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.strip().split("\n") if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        out = json.loads(lines[0])
+        assert out["steps"] == 5 and out["ms_per_step"] > 0
+        got = {p.stem: np.load(p) for p in d.glob("*.npy")}
+        assert set(got) == {"fad", "fad_terms", "mu_a", "mu_b", "cov_a", "cov_b"}
+        assert all(v.dtype == np.float64 for v in got.values()) and sum(v.nbytes for v in got.values()) <= 64 << 20
+        assert got["fad"].shape == (1,) and float(got["fad"][0]) == out["fad_last_timed_step"]
+        runs.append(got)
+    for name, v in runs[0].items():
+        np.testing.assert_array_equal(runs[1][name], v, err_msg=name)
+    got = runs[0]
+    fad = float(got["fad"][0])
+    mean_term, tr1, tr2, tr_sqrt = got["fad_terms"]
+    assert abs(mean_term + tr1 + tr2 - 2 * tr_sqrt - fad) <= 1e-12 * (tr1 + tr2)
+    g7 = json.loads((ROOT / "tests" / "golden" / "golden.json").read_text())["g7"]
+    assert abs(fad - g7["fad"]) / g7["fad"] < 1e-4
+    for tag, x in zip("ab", R.c3_pair()):
+        x = x.astype(np.float64)
+        np.testing.assert_allclose(got[f"mu_{tag}"], x.mean(axis=0), rtol=0, atol=1e-7)
+        cov = np.cov(x, rowvar=False)
+        np.testing.assert_allclose(got[f"cov_{tag}"], cov, rtol=0, atol=2e-6 * np.abs(cov).max())
+
+
 def test_fused_stats_cli_under_torchrun_with_rccl(tmp_path):
     """`fadtk <model> <base> <eval> <csv> --fused-stats` relaunched the way `--gpus N` relaunches it (torch.distributed.run),
     with a ONE-rank RCCL group (FAD_DIST_FORCE=1): embed_and_accumulate's shared buffer goes through the nccl all_reduce, rank 0
