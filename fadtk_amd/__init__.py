@@ -18,6 +18,9 @@ def __getattr__(name):
                 "W2V2Model", "HuBERTModel", "WavLMModel", "MERTModel"):
         from . import model_loader
         return getattr(model_loader, name)
+    if name in ("KernelAudioDistance", "calc_kernel_audio_distance"):      # lazy: `python -m fadtk_amd.kad` runs the module itself
+        from . import kad
+        return getattr(kad, name)
     if name == "cache_embedding_files":
         from .fad_batch import cache_embedding_files
         return cache_embedding_files

@@ -46,6 +46,14 @@ class FadDiag(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
+class FadKadResult(C.Structure):
+    _fields_ = [("mmd2", C.c_double), ("kxx_mean", C.c_double), ("kyy_mean", C.c_double), ("kxy_mean", C.c_double),
+                ("bandwidth", C.c_double), ("n", C.c_int64), ("m", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 _P = C.c_void_p
 _I64 = C.c_int64
 # name -> (restype, argtypes)     -- one entry per declaration in include/fad_hip.h
@@ -98,6 +106,9 @@ SIGNATURES = {
     "fad_logmel_vggish": (C.c_int, [_P, C.POINTER(_I64), _I64, _P, _I64, C.POINTER(_I64), C.c_int, C.c_int, _P]),
     "fad_logmel_whisper": (C.c_int, [_P, C.POINTER(_I64), _I64, C.c_int, _P, C.c_int, C.c_int, _P]),
     "fad_logmel_htsat": (C.c_int, [_P, C.POINTER(_I64), _I64, _I64, _P, C.c_int, C.c_int, _P]),
+    "fad_kad_median_distance": (C.c_int, [_P, _I64, _I64, _I64, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, _P]),
+    "fad_kad": (C.c_int, [_P, _I64, _I64, _P, _I64, _I64, _I64, C.c_int, C.c_int, C.c_double, C.POINTER(FadKadResult),
+                          C.c_int, _P]),
 }
 
 _lib = None

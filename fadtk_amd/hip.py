@@ -624,3 +624,53 @@ def resample_kaiser(wav, orig_sr: int, new_sr: int, quantize_pcm16: bool = False
     K.check(lib.fad_resample_kaiser(ptr, n, int(orig_sr), int(new_sr), int(bool(quantize_pcm16)), optr, n_out, on_dev, device,
                                     K.current_stream_ptr(device)), "fad_resample_kaiser")
     return out
+
+
+# ---------------------------------------------------------------------------------------------- Kernel Audio Distance
+def _kad_rows(x, what: str):
+    """-> rows_view of a float16 / bfloat16 / float32 frame matrix; float64 and other dtypes are refused, not converted."""
+    if K._is_torch(x):
+        import torch
+        ok = x.dtype in (torch.float16, torch.bfloat16, torch.float32)
+    else:
+        x = np.asarray(x)
+        ok = x.dtype in (np.float16, np.float32)
+    if not ok:
+        raise ValueError(f"KAD takes float16, bfloat16 or float32 rows; {what} is {x.dtype}: cast it (e.g. .astype(np.float32))")
+    return K.rows_view(x)
+
+
+def kad_median_distance(x, device: int = 0) -> float:
+    """``fad_kad_median_distance``: np.median(scipy.spatial.distance.pdist(x)) of one set of rows (numpy on the host, or a torch CUDA
+    tensor used in place on torch's current stream)."""
+    lib = K.load_library()
+    ptr, n, d, ld, code, on_dev, keep = _kad_rows(x, "x")
+    out = C.c_double()
+    K.check(lib.fad_kad_median_distance(ptr, n, ld, d, code, on_dev, C.byref(out), int(device), K.current_stream_ptr(device)),
+            "fad_kad_median_distance")
+    return float(out.value)
+
+
+def kad(x, y, bandwidth: Optional[float] = None, device: int = 0) -> dict:
+    """``fad_kad``: the unbiased Gaussian-kernel MMD^2 between the rows of x (baseline) and y -> dict of fad_kad_result
+    (mmd2, kxx_mean, kyy_mean, kxy_mean, bandwidth, n, m).  ``bandwidth=None``: the median pairwise distance of x.
+    Both sets are numpy arrays or both torch CUDA tensors of one dtype (float16 / bfloat16 / float32)."""
+    lib = K.load_library()
+    if K._is_torch(x) != K._is_torch(y) or (K._is_torch(x) and x.is_cuda != y.is_cuda):
+        import torch
+        dev = torch.device("cuda", device)
+        x = x if K._is_torch(x) else torch.from_numpy(np.ascontiguousarray(x))
+        y = y if K._is_torch(y) else torch.from_numpy(np.ascontiguousarray(y))
+        x, y = x.to(dev), y.to(dev)
+    px, n, d, ldx, cx, dev_x, kx = _kad_rows(x, "x")
+    py, m, dy, ldy, cy, dev_y, ky = _kad_rows(y, "y")
+    if d != dy:
+        raise ValueError(f"KAD: x has D = {d}, y has D = {dy}")
+    if cx != cy:
+        raise ValueError("KAD: x and y must have the same dtype")
+    res = K.FadKadResult()
+    bw = 0.0 if bandwidth is None else float(bandwidth)
+    if bandwidth is not None and not bw > 0:
+        raise ValueError(f"KAD: bandwidth must be > 0, got {bandwidth}")
+    K.check(lib.fad_kad(px, n, ldx, py, m, ldy, d, cx, dev_x, bw, C.byref(res), int(device), K.current_stream_ptr(device)), "fad_kad")
+    return res.as_dict()

@@ -311,6 +311,28 @@ int64_t fad_resample_num_samples(int64_t n, int orig_sr, int new_sr);
 int fad_resample_kaiser(const float* wav, int64_t n, int orig_sr, int new_sr, int quantize_pcm16, float* out,
                         int64_t out_capacity, int on_device, int device, void* stream);
 
+/* ------------------------------------------------------------------ Kernel Audio Distance (KAD)
+ * Not in the reference: the unbiased Gaussian-kernel MMD^2 of Chung et al. 2025 ("KAD: No More FAD!") between the rows x [n x d] and
+ * y [m x d] that FAD would reduce to (mu, Sigma):
+ *   k(a, b) = exp(-|a - b|^2 / (2 sigma^2)),   MMD^2 = Kxx + Kyy - 2 Kxy,
+ *   Kxx = sum_{i != j} k(x_i, x_j) / (n (n - 1)),  Kyy likewise,  Kxy = sum_{i, j} k(x_i, y_j) / (n m).
+ * The score may be negative (the estimator is unbiased).  Rows are float16, bfloat16 or float32 (FAD_F64 -> FAD_ERR_INVALID:
+ * cast), 1 <= d <= 2048, ld >= d; dot products in float32 on the matrix cores, sums in float64, the same bits on every run.
+ * n or m < 2 -> FAD_ERR_TOO_FEW_ROWS; a NaN/Inf row norm -> FAD_ERR_NOT_FINITE.  Work goes on `stream`; both calls synchronise it. */
+typedef struct fad_kad_result {
+    double mmd2, kxx_mean, kyy_mean, kxy_mean, bandwidth;   /* bandwidth: the sigma used */
+    int64_t n, m;
+} fad_kad_result_t;
+/* median pairwise Euclidean distance within one set (the default bandwidth): np.median(scipy.spatial.distance.pdist(x)),
+ * the mean of the two middle distances when n (n - 1) / 2 is even; exact selection on the float32 squared distances */
+int fad_kad_median_distance(const void* x, int64_t n, int64_t ld, int64_t d, int dtype, int on_device,
+                            double* sigma, int device, void* stream);
+/* unbiased Gaussian-kernel MMD^2; bandwidth <= 0: the median distance of x (a median of 0 -> FAD_ERR_INVALID).  d^2 is formed as
+ * |a|^2 + |b|^2 - 2 a.b in float32, so equal rows give exactly 0 only when their products sum exactly (e.g. integer-valued rows);
+ * otherwise a rounding residue may leave a tiny positive median, which is used as the bandwidth. */
+int fad_kad(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype,
+            int on_device, double bandwidth, fad_kad_result_t* out, int device, void* stream);
+
 /* ------------------------------------------------------------------ diagnostics (NOT part of the drop-in surface)
  * Nothing in fadtk corresponds to these two calls and no binding of the reference needs them: they exist for bench.py's
  * roofline object (HIP events around the tile kernel on the stream it is launched on) and for the GPU tests that check
