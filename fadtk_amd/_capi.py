@@ -109,6 +109,8 @@ SIGNATURES = {
     "fad_kad_median_distance": (C.c_int, [_P, _I64, _I64, _I64, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, _P]),
     "fad_kad": (C.c_int, [_P, _I64, _I64, _P, _I64, _I64, _I64, C.c_int, C.c_int, C.c_double, C.POINTER(FadKadResult),
                           C.c_int, _P]),
+    "fad_kad_individual": (C.c_int, [_P, _I64, _I64, _P, _I64, _I64, C.POINTER(_I64), _I64, _I64, C.c_int, C.c_int, C.c_double,
+                                     C.POINTER(FadKadResult), _P, _P, _P, _P, C.c_int, _P]),
 }
 
 _lib = None

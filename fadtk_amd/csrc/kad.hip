@@ -15,6 +15,7 @@
 // arguments adds exactly the same tile sums.  KAD's code object is loaded at its first call, not by check_device's warm-up.
 #include "fad_common.h"
 #include "kad_tiles.h"
+#include "kad_song_tiles.h"
 
 #include <algorithm>
 #include <cmath>
@@ -282,12 +283,226 @@ __global__ void __launch_bounds__(256) kad_slots_sum_kernel(const double* __rest
     if (threadIdx.x == 0) out[blockIdx.x] = red[0];
 }
 
+// ------------------------------------------------------------------------------------------------- per-song passes
+// fad_kad_individual's cross (X x Y) and band (Y x Y inside each song) passes: the main loop of kad_pass_kernel, with an epilogue
+// that keeps per-column sums (kad_song_tiles.h).  In the 32 x 32 MFMA layout a lane owns its column, so a column's sum over a tile
+// is 32 in-register adds per lane; the two lane halves and the two wm waves of a column meet once, at the end of a work unit.
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+
+struct ColArgs {
+    const char* a; const char* b;              // row operand (X, or Y for the band), column operand (Y)
+    const float* ha; const float* hb;
+    int64_t pitch;
+    int nchunks;
+    float c;                                   // log2(e) / sigma^2
+    int64_t u0, cnt;                           // the launch's units [u0, u0 + cnt)
+    int64_t TI, TJ, rr;                        // cross: the unit map
+    const kad::Unit* units;                    // band: (J, I0, I1) per unit
+    const int* row_end;                        // band: offsets[song(i) + 1] per row of Y, 0 on padding rows
+    double* slots; int64_t slot_pitch;         // cross: slots[R * slot_pitch + j]; band: slots[u * kTile + c]
+};
+
+// k(S') of the wave's 64 rows of a tile added into the lane's two columns (cbase + 32 bj + lane % 32); MASK 0: every pair, 1: a
+// diagonal tile (column > row), 2: a band tile holding more than one song (column < end of the row's song, and on a diagonal tile
+// column > row).  Masks are selects: a NaN row that the clamp turned into k = 1 still adds nothing where it is masked.
+template <int MASK>
+__device__ __forceinline__ void col_sums(const f32x16 (&acc)[2][2], float c, int rbase, int cbase, int lane, const int* lend, bool diag,
+                                         double (&dcol)[2]) {
+    int lrow = rbase + 4 * (lane >> 5), lcol = cbase + (lane & 31);
+    if (MASK) asm volatile("" : "+v"(lrow), "+v"(lcol));         // per tile, not hoisted out of the tile loop as lane masks (tile_sum)
+    i32x4 le[2][4];
+    if (MASK == 2) {
+#pragma unroll
+        for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) le[bi][q] = *reinterpret_cast<const i32x4*>(lend + lrow + bi * 32 + 8 * q);
+    }
+#pragma unroll
+    for (int bj = 0; bj < 2; ++bj) {
+        float s = 0.f;
+#pragma unroll
+        for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+            for (int g = 0; g < 16; ++g) {
+                float v = acc[bi][bj][g] * c, w;                  // as tile_sum: the MFMA result read by ordinary code, the clamp in asm
+                asm("v_min_f32 %0, 0, %1" : "=v"(w) : "v"(v));
+                float e = __builtin_amdgcn_exp2f(w);
+                const int r = lrow + bi * 32 + (g & 3) + 8 * (g >> 2), col = lcol + bj * 32;
+                if (MASK == 1) e = col > r ? e : 0.f;
+                if (MASK == 2) e = (col < le[bi][g >> 2][g & 3] && (!diag || col > r)) ? e : 0.f;
+                s += e;
+            }
+        dcol[bj] += (double)s;
+    }
+}
+
+template <int DT, bool BAND>
+__global__ void __launch_bounds__(kThreads, 2) kad_cols_kernel(ColArgs p) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    char* la = lds;
+    char* lb = lds + kOpBytes;
+    float* lh = reinterpret_cast<float*>(lds + 2 * kOpBytes);                          // [0, 128): rows, [128, 256): columns
+    int* lend = reinterpret_cast<int*>(lds + 2 * kOpBytes + 2 * kTile * 4);           // BAND: end of each row's song - J * 128, in [0, 128]
+    double* lx = reinterpret_cast<double*>(lds + 2 * kOpBytes + 3 * kTile * 4);       // the wm = 1 waves' column sums of a unit
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
+    const int rbase = wm * 64, cbase = wn * 64;
+    const int64_t G = gridDim.x, nslots = kad::launch_slots(p.cnt);
+
+    for (int64_t L = blockIdx.x; L < nslots; L += G) {
+        bool live;
+        const int64_t v = kad::slot_tile(L, p.cnt, &live);
+        if (!live) continue;                                                          // uniform over the workgroup
+        const int64_t u = p.u0 + v;
+        const kad::Unit un = BAND ? p.units[u] : kad::cross_unit(u, p.TI, p.TJ, p.rr);
+        const char* gb = p.b + un.J * kTile * p.pitch;
+        double dcol[2] = {0.0, 0.0};
+
+        for (int64_t I = un.I0; I < un.I1; ++I) {
+            const char* ga = p.a + I * kTile * p.pitch;
+            __syncthreads();                                                          // the previous tile is done with LDS
+            if (tid < kTile) {
+                lh[tid] = p.ha[I * kTile + tid];
+                if (BAND) {
+                    const int64_t e = (int64_t)p.row_end[I * kTile + tid] - un.J * kTile;
+                    lend[tid] = e < 0 ? 0 : e > kTile ? kTile : (int)e;
+                }
+            } else {
+                lh[tid] = p.hb[un.J * kTile + tid - kTile];
+            }
+
+            u32x4 ra[4], rb[4];
+            auto load = [&](int ch) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int row = (tid >> 3) + 32 * q, col = (tid & 7) * 16;
+                    ra[q] = *reinterpret_cast<const u32x4*>(ga + row * p.pitch + ch * kChunk + col);
+                    rb[q] = *reinterpret_cast<const u32x4*>(gb + row * p.pitch + ch * kChunk + col);
+                }
+            };
+            load(0);
+            __syncthreads();
+
+            f32x16 acc[2][2];
+#pragma unroll
+            for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+                for (int bj = 0; bj < 2; ++bj) {
+                    const float hc = lh[kTile + cbase + bj * 32 + (lane & 31)];
+#pragma unroll
+                    for (int g = 0; g < 16; ++g)
+                        acc[bi][bj][g] = lh[rbase + bi * 32 + (g & 3) + 8 * (g >> 2) + 4 * (lane >> 5)] + hc;
+                }
+
+            for (int ch = 0; ch < p.nchunks; ++ch) {
+                if (ch) __syncthreads();
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int row = (tid >> 3) + 32 * q, col = (tid & 7) * 16;
+                    *reinterpret_cast<u32x4*>(la + row * kLdsRow + col) = ra[q];
+                    *reinterpret_cast<u32x4*>(lb + row * kLdsRow + col) = rb[q];
+                }
+                __syncthreads();
+                if (ch + 1 < p.nchunks) load(ch + 1);
+                chunk_mfma<DT>(la + rbase * kLdsRow, lb + cbase * kLdsRow, lane, acc);
+            }
+
+            if (BAND) {
+                const bool diag = I == un.J;
+                if (lend[0] >= kTile) {                                               // the tile lies inside one song (uniform)
+                    if (diag) col_sums<1>(acc, p.c, rbase, cbase, lane, lend, true, dcol);
+                    else col_sums<0>(acc, p.c, rbase, cbase, lane, lend, false, dcol);
+                } else {
+                    col_sums<2>(acc, p.c, rbase, cbase, lane, lend, diag, dcol);
+                }
+            } else {
+                col_sums<0>(acc, p.c, rbase, cbase, lane, lend, false, dcol);
+            }
+        }
+
+        // a column: the two lane halves, then the wm = 0 and wm = 1 waves, in this order
+#pragma unroll
+        for (int bj = 0; bj < 2; ++bj) dcol[bj] += __shfl_xor(dcol[bj], 32, 64);
+        if (wm == 1 && lane < 32) {
+#pragma unroll
+            for (int bj = 0; bj < 2; ++bj) lx[cbase + bj * 32 + lane] = dcol[bj];
+        }
+        __syncthreads();
+        if (wm == 0 && lane < 32) {
+            double* slot = BAND ? p.slots + u * kTile : p.slots + (u / p.TJ) * p.slot_pitch + un.J * kTile;
+#pragma unroll
+            for (int bj = 0; bj < 2; ++bj) slot[cbase + bj * 32 + lane] = dcol[bj] + lx[cbase + bj * 32 + lane];
+        }
+    }
+}
+
+constexpr size_t kLdsCols = 2 * kOpBytes + 3 * kTile * 4 + kTile * sizeof(double);
+
+// row_end[i] = offsets[song(i) + 1] for the rows of Y (the last song s with offsets[s] <= i), 0 on the padding rows
+__global__ void __launch_bounds__(256) kad_row_end_kernel(const int64_t* __restrict__ offsets, int64_t n_songs, int64_t m, int64_t m_pad,
+                                                          int* __restrict__ row_end) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= m_pad) return;
+    if (i >= m) { row_end[i] = 0; return; }
+    int64_t lo = 0, hi = n_songs;                                                     // offsets[lo] <= i < offsets[hi]
+    while (hi - lo > 1) {
+        const int64_t mid = lo + (hi - lo) / 2;
+        if (offsets[mid] <= i) lo = mid; else hi = mid;
+    }
+    row_end[i] = (int)offsets[lo + 1];
+}
+
+// One workgroup per song: r_xy(j) = sum over the cross slot rows, r_yy(j) = sum over the band units of j's column block, both in a
+// fixed order, then summed over the song's rows in a fixed order -> Kxy, Kyy and a status (too few rows, a non-finite row norm).
+__global__ void __launch_bounds__(256) kad_song_reduce_kernel(const double* __restrict__ cross, int64_t nr, int64_t pitch,
+                                                              const double* __restrict__ band, const int64_t* __restrict__ band_start,
+                                                              const float* __restrict__ hy, const int64_t* __restrict__ offsets, double n,
+                                                              double* __restrict__ kyy, double* __restrict__ kxy, int* __restrict__ status) {
+    __shared__ double rx[256];
+    __shared__ double ry[256];
+    __shared__ int rbad[256];
+    const int64_t s = blockIdx.x, b = offsets[s], e = offsets[s + 1], m = e - b;
+    double sx = 0.0, sy = 0.0;
+    int bad = 0;
+    for (int64_t j = b + threadIdx.x; j < e; j += 256) {
+        double x = 0.0, y = 0.0;
+        for (int64_t R = 0; R < nr; ++R) x += cross[R * pitch + j];
+        const int64_t J = j / kTile;
+        for (int64_t u = band_start[J]; u < band_start[J + 1]; ++u) y += band[u * kTile + (j - J * kTile)];
+        sx += x;
+        sy += y;
+        bad |= !isfinite(hy[j]);
+    }
+    rx[threadIdx.x] = sx; ry[threadIdx.x] = sy; rbad[threadIdx.x] = bad;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+            rx[threadIdx.x] += rx[threadIdx.x + w];
+            ry[threadIdx.x] += ry[threadIdx.x + w];
+            rbad[threadIdx.x] |= rbad[threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double md = (double)m;
+        if (m < 2 || rbad[0]) {
+            status[s] = m < 2 ? FAD_ERR_TOO_FEW_ROWS : FAD_ERR_NOT_FINITE;
+            kyy[s] = kxy[s] = NAN;
+        } else {
+            status[s] = FAD_OK;
+            kxy[s] = rx[0] / (n * md);
+            kyy[s] = 2.0 * ry[0] / (md * (md - 1.0));
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------------------------ host side
 struct KadWorkspace {
     DevBuf raw[2], img[2], h[2], slots, small;       // small: info, pass offsets, pass sums, histograms
+    DevBuf cross, band, songs;                       // fad_kad_individual: column slots of the two passes, song tables and outputs
     void release_all() {
         for (int i = 0; i < 2; ++i) { raw[i].release(); img[i].release(); h[i].release(); }
-        slots.release(); small.release();
+        slots.release(); small.release(); cross.release(); band.release(); songs.release();
     }
 };
 
@@ -318,9 +533,9 @@ static int check_rows(const void* x, int64_t n, int64_t ld, int64_t d, int dtype
     return FAD_OK;
 }
 
-// rows -> the set's padded image and h; reads back the norm sum and checks every norm is finite
-static int pack_set(int slot, const void* x, int64_t n, int64_t ld, int64_t d, int dtype, int on_device, int device, hipStream_t st,
-                    KadWorkspace& ws, Packed* out) {
+// rows -> the set's padded image and h (no check of the norms)
+static int pack_image(int slot, const void* x, int64_t n, int64_t ld, int64_t d, int dtype, int on_device, int device, hipStream_t st,
+                      KadWorkspace& ws, Packed* out) {
     const size_t es = dtype_size(dtype);
     const int64_t dp = depth_elems(d, dtype), n_pad = kad::blocks(n) * kTile;
     if (!on_device) {
@@ -340,15 +555,23 @@ static int pack_set(int slot, const void* x, int64_t n, int64_t ld, int64_t d, i
         default: kad_pack_kernel<float><<<grid, 256, 0, st>>>(static_cast<const float*>(x), n, ld, d, static_cast<float*>(ws.img[slot].p), dp, n_pad, h); break;
     }
     FAD_HIP_TRY(hipGetLastError());
+    *out = Packed{static_cast<const char*>(ws.img[slot].p), h, n, dp * (int64_t)es, (int)(dp * (int64_t)es / kChunk), 0.0};
+    return FAD_OK;
+}
+
+// rows -> the set's padded image and h; reads back the norm sum and checks every norm is finite
+static int pack_set(int slot, const void* x, int64_t n, int64_t ld, int64_t d, int dtype, int on_device, int device, hipStream_t st,
+                    KadWorkspace& ws, Packed* out) {
+    FAD_TRY(pack_image(slot, x, n, ld, d, dtype, on_device, device, st, ws, out));
     double* info_d = static_cast<double*>(ws.small.p) + 2 * slot;
-    kad_norm_info_kernel<<<1, 256, 0, st>>>(h, n, info_d);
+    kad_norm_info_kernel<<<1, 256, 0, st>>>(out->h, n, info_d);
     FAD_HIP_TRY(hipGetLastError());
     double info[2];
     FAD_HIP_TRY(hipMemcpyAsync(info, info_d, sizeof(info), hipMemcpyDeviceToHost, st));
     FAD_HIP_TRY(hipStreamSynchronize(st));
     if (info[1] != 0.0)
         return set_error(FAD_ERR_NOT_FINITE, "KAD: %lld of %lld rows have a NaN/Inf norm", (long long)info[1], (long long)n);
-    *out = Packed{static_cast<const char*>(ws.img[slot].p), h, n, dp * (int64_t)es, (int)(dp * (int64_t)es / kChunk), info[0]};
+    out->norm_sum = info[0];
     return FAD_OK;
 }
 
@@ -418,6 +641,30 @@ static int median_of_packed(const Packed& x, int dtype, int device, hipStream_t 
     *sigma = 0.5 * (std::sqrt((double)d2[0]) + std::sqrt((double)d2[1]));
     return FAD_OK;
 }
+
+template <bool BAND>
+static int launch_cols(int dtype, const ColArgs& p, int64_t grid, hipStream_t st) {
+    switch (dtype) {
+        case FAD_F16: kad_cols_kernel<FAD_F16, BAND><<<(unsigned)grid, kThreads, kLdsCols, st>>>(p); break;
+        case FAD_BF16: kad_cols_kernel<FAD_BF16, BAND><<<(unsigned)grid, kThreads, kLdsCols, st>>>(p); break;
+        default: kad_cols_kernel<FAD_F32, BAND><<<(unsigned)grid, kThreads, kLdsCols, st>>>(p); break;
+    }
+    FAD_HIP_TRY(hipGetLastError());
+    return FAD_OK;
+}
+
+// the launches of a column pass of `total` units of at most `unit_tiles` tiles each
+static std::vector<Launch> plan_units(int64_t total, int64_t unit_tiles, int64_t depth, bool f32, int device) {
+    std::vector<Launch> out;
+    const int64_t per = kad::units_per_launch(unit_tiles, depth, f32);
+    for (int64_t u0 = 0; u0 < total; u0 += per) {
+        const int64_t cnt = std::min(per, total - u0);
+        out.push_back(Launch{u0, cnt, kad::launch_grid(cnt, grid_cap(device))});
+    }
+    return out;
+}
+
+static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 }  // namespace
 
@@ -512,6 +759,145 @@ int fad_kad(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int
     out->bandwidth = sigma;
     out->n = n;
     out->m = m;
+    return FAD_OK;
+}
+
+
+int fad_kad_individual(const void* x, int64_t n, int64_t ldx, const void* rows, int64_t n_rows, int64_t ldy, const int64_t* offsets,
+                       int64_t n_songs, int64_t d, int dtype, int on_device, double bandwidth, fad_kad_result_t* base, double* out_mmd2,
+                       double* out_kyy_mean, double* out_kxy_mean, int32_t* out_status, int device, void* stream) {
+    using namespace fad;
+    if (!base) return set_error(FAD_ERR_INVALID, "fad_kad_individual: NULL output");
+    FAD_TRY(check_rows(x, n, ldx, d, dtype, "fad_kad_individual (x)"));
+    if (n_songs < 0 || n_songs > INT32_MAX) return set_error(FAD_ERR_INVALID, "fad_kad_individual: %lld songs", (long long)n_songs);
+    if (!offsets || (n_songs > 0 && (!out_mmd2 || !out_kyy_mean || !out_kxy_mean || !out_status)))
+        return set_error(FAD_ERR_INVALID, "fad_kad_individual: NULL offsets or per-song output");
+    if (n_rows < 0 || n_rows > INT32_MAX - kTile)
+        return set_error(FAD_ERR_INVALID, "fad_kad_individual: %lld song rows (at most %d)", (long long)n_rows, INT32_MAX - kTile);
+    if (n_rows > 0 && !rows) return set_error(FAD_ERR_INVALID, "fad_kad_individual: NULL song rows");
+    if (n_rows > 0 && ldy < d) return set_error(FAD_ERR_INVALID, "fad_kad_individual: song row pitch %lld < D = %lld", (long long)ldy, (long long)d);
+    if (offsets[0] != 0 || offsets[n_songs] != n_rows)
+        return set_error(FAD_ERR_INVALID, "fad_kad_individual: offsets run from %lld to %lld, not 0 to %lld", (long long)offsets[0],
+                         (long long)offsets[n_songs], (long long)n_rows);
+    for (int64_t s = 0; s < n_songs; ++s)
+        if (offsets[s + 1] < offsets[s]) return set_error(FAD_ERR_INVALID, "fad_kad_individual: offsets decrease at song %lld", (long long)s);
+    if (std::isnan(bandwidth) || std::isinf(bandwidth))
+        return set_error(FAD_ERR_INVALID, "fad_kad_individual: bandwidth %g is not finite", bandwidth);
+    FAD_TRY(check_device(device));
+    DeviceGuard g(device);
+    if (!g.ok) return set_error(FAD_ERR_HIP, "hipSetDevice(%d) failed", device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    KadWorkspace& ws = workspace(device);
+
+    // the baseline: sigma and Kxx exactly as fad_kad finds them (the same launches, slots and fixed-order sum)
+    Packed px;
+    FAD_TRY(pack_set(0, x, n, ldx, d, dtype, on_device, device, st, ws, &px));
+    double sigma = bandwidth;
+    if (!(sigma > 0)) FAD_TRY(median_of_packed(px, dtype, device, st, ws, &sigma));
+    if (!(sigma > 0) || !std::isfinite(sigma))
+        return set_error(FAD_ERR_INVALID, "fad_kad_individual: bandwidth %g (the median pairwise distance of the baseline when none is "
+                         "given) must be > 0 -- are all baseline rows identical?", sigma);
+    const double cd = 1.4426950408889634 / (sigma * sigma);
+    if (!(cd > 0) || !std::isfinite(cd) || !std::isfinite((float)cd) || (float)cd == 0.f)
+        return set_error(FAD_ERR_INVALID, "fad_kad_individual: bandwidth %g is outside the float32 range of the kernel", sigma);
+    const bool f32 = dtype == FAD_F32;
+    const int64_t depth = px.pitch / (int64_t)dtype_size(dtype), TI = kad::blocks(n);
+    {
+        const auto launches = plan(kad::tri_tiles(TI), depth, f32, false, device);
+        int64_t off[2] = {0, 0};
+        for (const Launch& l : launches) off[1] += l.grid;
+        FAD_TRY(ws.slots.reserve((size_t)off[1] * sizeof(double)));
+        PassArgs p{};
+        p.a = p.b = px.img; p.ha = p.hb = px.h; p.pitch = px.pitch; p.n_a = p.n_b = n; p.tiles_j = TI; p.tri = 1; p.nchunks = px.nchunks;
+        p.c = (float)cd;
+        double* slots = static_cast<double*>(ws.slots.p);
+        for (const Launch& l : launches) {
+            p.u0 = l.u0; p.cnt = l.cnt; p.slots = slots;
+            FAD_TRY(launch_pass<MODE_SUM>(dtype, p, l.grid, st));
+            slots += l.grid;
+        }
+        int64_t* off_d = reinterpret_cast<int64_t*>(static_cast<double*>(ws.small.p) + 8);
+        FAD_HIP_TRY(hipMemcpyAsync(off_d, off, sizeof(off), hipMemcpyHostToDevice, st));
+        kad_slots_sum_kernel<<<1, 256, 0, st>>>(static_cast<const double*>(ws.slots.p), off_d, static_cast<double*>(ws.small.p) + 16);
+        FAD_HIP_TRY(hipGetLastError());
+    }
+
+    // the songs: cross pass (X x Y) and band pass (pairs inside each song), per-column slots, one reduction per song
+    if (n_rows > 0 && n_songs > 0) {
+        Packed py;
+        FAD_TRY(pack_image(1, rows, n_rows, ldy, d, dtype, on_device, device, st, ws, &py));
+        const int64_t TJ = kad::blocks(n_rows), m_pad = TJ * kTile;
+        const int64_t rr = kad::cross_rows_per_unit(TI, TJ, kad::tiles_per_launch(depth, f32)), NR = kad::cross_ranges(TI, rr);
+        std::vector<kad::Unit> bunits;
+        std::vector<int64_t> bstart;
+        kad::band_units(offsets, n_songs, &bunits, &bstart);
+        const int64_t U = (int64_t)bunits.size();
+
+        // song tables and outputs, one buffer: offsets | band_start | band units | row_end | kyy | kxy | status
+        size_t at[8];
+        at[0] = 0;
+        at[1] = at[0] + align256((size_t)(n_songs + 1) * sizeof(int64_t));
+        at[2] = at[1] + align256((size_t)(TJ + 1) * sizeof(int64_t));
+        at[3] = at[2] + align256((size_t)U * sizeof(kad::Unit));
+        at[4] = at[3] + align256((size_t)m_pad * sizeof(int));
+        at[5] = at[4] + align256((size_t)n_songs * sizeof(double));
+        at[6] = at[5] + align256((size_t)n_songs * sizeof(double));
+        at[7] = at[6] + align256((size_t)n_songs * sizeof(int));
+        FAD_TRY(ws.songs.reserve(at[7]));
+        FAD_TRY(ws.cross.reserve((size_t)(NR * m_pad) * sizeof(double)));
+        FAD_TRY(ws.band.reserve((size_t)(U * kTile) * sizeof(double)));
+        char* sb = static_cast<char*>(ws.songs.p);
+        int64_t* off_d = reinterpret_cast<int64_t*>(sb + at[0]);
+        int64_t* bstart_d = reinterpret_cast<int64_t*>(sb + at[1]);
+        kad::Unit* bunits_d = reinterpret_cast<kad::Unit*>(sb + at[2]);
+        int* row_end_d = reinterpret_cast<int*>(sb + at[3]);
+        double* kyy_d = reinterpret_cast<double*>(sb + at[4]);
+        double* kxy_d = reinterpret_cast<double*>(sb + at[5]);
+        int* status_d = reinterpret_cast<int*>(sb + at[6]);
+        FAD_HIP_TRY(hipMemcpyAsync(off_d, offsets, (size_t)(n_songs + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        FAD_HIP_TRY(hipMemcpyAsync(bstart_d, bstart.data(), bstart.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        FAD_HIP_TRY(hipMemcpyAsync(bunits_d, bunits.data(), bunits.size() * sizeof(kad::Unit), hipMemcpyHostToDevice, st));
+        kad_row_end_kernel<<<(unsigned)cdiv(m_pad, 256), 256, 0, st>>>(off_d, n_songs, n_rows, m_pad, row_end_d);
+        FAD_HIP_TRY(hipGetLastError());
+
+        ColArgs p{};
+        p.b = py.img; p.hb = py.h; p.pitch = px.pitch; p.nchunks = px.nchunks; p.c = (float)cd;
+        p.a = px.img; p.ha = px.h; p.TI = TI; p.TJ = TJ; p.rr = rr;
+        p.slots = static_cast<double*>(ws.cross.p); p.slot_pitch = m_pad;
+        for (const Launch& l : plan_units(NR * TJ, rr, depth, f32, device)) {
+            p.u0 = l.u0; p.cnt = l.cnt;
+            FAD_TRY(launch_cols<false>(dtype, p, l.grid, st));
+        }
+        p.a = py.img; p.ha = py.h; p.units = bunits_d; p.row_end = row_end_d;
+        p.slots = static_cast<double*>(ws.band.p); p.slot_pitch = kTile;
+        for (const Launch& l : plan_units(U, kad::kBandPiece, depth, f32, device)) {
+            p.u0 = l.u0; p.cnt = l.cnt;
+            FAD_TRY(launch_cols<true>(dtype, p, l.grid, st));
+        }
+        kad_song_reduce_kernel<<<(unsigned)n_songs, 256, 0, st>>>(static_cast<const double*>(ws.cross.p), NR, m_pad,
+                                                                  static_cast<const double*>(ws.band.p), bstart_d, py.h, off_d, (double)n,
+                                                                  kyy_d, kxy_d, status_d);
+        FAD_HIP_TRY(hipGetLastError());
+        FAD_HIP_TRY(hipMemcpyAsync(out_kyy_mean, kyy_d, (size_t)n_songs * sizeof(double), hipMemcpyDeviceToHost, st));
+        FAD_HIP_TRY(hipMemcpyAsync(out_kxy_mean, kxy_d, (size_t)n_songs * sizeof(double), hipMemcpyDeviceToHost, st));
+        FAD_HIP_TRY(hipMemcpyAsync(out_status, status_d, (size_t)n_songs * sizeof(int), hipMemcpyDeviceToHost, st));
+    } else {
+        for (int64_t s = 0; s < n_songs; ++s) {                  // no song rows at all: every song is empty
+            out_kyy_mean[s] = out_kxy_mean[s] = NAN;
+            out_status[s] = FAD_ERR_TOO_FEW_ROWS;
+        }
+    }
+    double sxx;
+    FAD_HIP_TRY(hipMemcpyAsync(&sxx, static_cast<double*>(ws.small.p) + 16, sizeof(double), hipMemcpyDeviceToHost, st));
+    FAD_HIP_TRY(hipStreamSynchronize(st));
+
+    base->kxx_mean = 2.0 * sxx / ((double)n * (double)(n - 1));
+    base->kyy_mean = base->kxy_mean = base->mmd2 = NAN;
+    base->bandwidth = sigma;
+    base->n = n;
+    base->m = n_rows;
+    for (int64_t s = 0; s < n_songs; ++s)
+        out_mmd2[s] = out_status[s] == FAD_OK ? base->kxx_mean + out_kyy_mean[s] - 2.0 * out_kxy_mean[s] : NAN;
     return FAD_OK;
 }
 

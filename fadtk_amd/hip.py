@@ -674,3 +674,39 @@ def kad(x, y, bandwidth: Optional[float] = None, device: int = 0) -> dict:
         raise ValueError(f"KAD: bandwidth must be > 0, got {bandwidth}")
     K.check(lib.fad_kad(px, n, ldx, py, m, ldy, d, cx, dev_x, bw, C.byref(res), int(device), K.current_stream_ptr(device)), "fad_kad")
     return res.as_dict()
+
+
+def kad_individual(x, rows, offsets: Sequence[int], bandwidth: Optional[float] = None, device: int = 0) -> dict:
+    """``fad_kad_individual``: KAD between the baseline rows x and every song s = rows[offsets[s]:offsets[s + 1]], one sigma for all
+    (``bandwidth=None``: the median pairwise distance of x) -> dict of float64 arrays ``mmd2``, ``kyy_mean``, ``kxy_mean`` and int32
+    ``status`` [S] (NaN where status is FAD_ERR_TOO_FEW_ROWS or FAD_ERR_NOT_FINITE), plus ``kxx_mean``, ``bandwidth`` and ``n``.
+    x and rows are both numpy arrays or both torch CUDA tensors of one dtype (float16 / bfloat16 / float32)."""
+    lib = K.load_library()
+    if K._is_torch(x) != K._is_torch(rows) or (K._is_torch(x) and x.is_cuda != rows.is_cuda):
+        import torch
+        dev = torch.device("cuda", device)
+        x = x if K._is_torch(x) else torch.from_numpy(np.ascontiguousarray(x))
+        rows = rows if K._is_torch(rows) else torch.from_numpy(np.ascontiguousarray(rows))
+        x, rows = x.to(dev), rows.to(dev)
+    px, n, d, ldx, cx, dev_x, kx = _kad_rows(x, "x")
+    py, m, dy, ldy, cy, dev_y, ky = _kad_rows(rows, "rows")
+    if m > 0 and d != dy:
+        raise ValueError(f"KAD: x has D = {d}, the songs have D = {dy}")
+    if m > 0 and cx != cy:
+        raise ValueError("KAD: x and the songs must have the same dtype")
+    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+    if off.ndim != 1 or off.shape[0] < 1:
+        raise ValueError("KAD: offsets must be a 1-D sequence of S + 1 row indices")
+    S = off.shape[0] - 1
+    bw = 0.0 if bandwidth is None else float(bandwidth)
+    if bandwidth is not None and not bw > 0:
+        raise ValueError(f"KAD: bandwidth must be > 0, got {bandwidth}")
+    out = {k: np.full(S, np.nan) for k in ("mmd2", "kyy_mean", "kxy_mean")}
+    out["status"] = np.zeros(S, dtype=np.int32)
+    res = K.FadKadResult()
+    K.check(lib.fad_kad_individual(px, n, ldx, py if m > 0 else None, m, max(ldy, d), off.ctypes.data_as(C.POINTER(C.c_int64)), S, d,
+                                   cx, dev_x, bw, C.byref(res), out["mmd2"].ctypes.data, out["kyy_mean"].ctypes.data,
+                                   out["kxy_mean"].ctypes.data, out["status"].ctypes.data, int(device), K.current_stream_ptr(device)),
+            "fad_kad_individual")
+    out.update(kxx_mean=res.kxx_mean, bandwidth=res.bandwidth, n=res.n)
+    return out

@@ -11,22 +11,27 @@ to ``calc_embd_statistics``).  sigma defaults to the median pairwise distance wi
 (``np.median(scipy.spatial.distance.pdist(x))``).  The score is reported as ``scale * MMD^2`` (scale 1 by default) and may be
 negative: the estimator is unbiased.
 
-    python -m fadtk_amd.kad <model> <baseline_dir> <eval_dir> [csv] [--bandwidth S] [--scale F] [-w N]
+Per song (``--indiv``): KAD between the baseline and each file of the evaluation directory alone, one sigma for all, every song in
+one batched GPU call (``fad_kad_individual``); ``path,score`` lines sorted by |score|, like fadtk's per-song FAD.
+
+    python -m fadtk_amd.kad <model> <baseline_dir> <eval_dir> [csv] [--bandwidth S] [--scale F] [-w N] [--indiv]
 """
 from __future__ import annotations
 
 import logging
 import time
+import traceback
 from argparse import ArgumentParser
 from pathlib import Path
-from typing import Optional
+from typing import Optional, Sequence, Union
 
 import numpy as np
 
-from .utils import PathLike
+from .utils import PathLike, tmap, write
 
 log = logging.getLogger("fadtk_amd")
 CSV_HEADER = "model,baseline,eval,kad,bandwidth,scale,time\n"
+INDIV_BYTES = 4 << 30          # song rows per fad_kad_individual call at most (a larger set is split; sigma comes from the first call)
 
 
 def _shape_of(x):
@@ -47,6 +52,57 @@ def calc_kernel_audio_distance(x, y, bandwidth: Optional[float] = None, scale: f
     res = hip.kad(x, y, bandwidth=bandwidth, device=device)
     value = float(scale) * res["mmd2"]
     return (value, res) if details else value
+
+
+def calc_kernel_audio_distance_individual(x, songs: Sequence, bandwidth: Optional[float] = None, scale: float = 1.0, device: int = 0,
+                                          details: bool = False, max_bytes: int = INDIV_BYTES):
+    """scale * MMD^2 between the rows of x (baseline) and each song [m_s x D] alone, one sigma for all (``bandwidth=None``: the median
+    pairwise distance of x), on the GPU (``fad_kad_individual``) -> float64 array [S], NaN for songs with fewer than 2 frames or a
+    non-finite row.  numpy arrays or torch CUDA tensors; mixed dtypes are cast to float32.  Songs whose rows together exceed
+    ``max_bytes`` go in several calls, the later ones with the first call's sigma.  ``details=True`` returns (values, dict of
+    hip.kad_individual's arrays and kxx_mean / bandwidth / n)."""
+    from . import hip
+    sx = _shape_of(x)
+    if len(sx) != 2 or sx[0] < 2:
+        raise ValueError(f"KAD needs a 2-D baseline of at least 2 rows, got shape {sx}")
+    shapes = [_shape_of(y) for y in songs]
+    for sh in shapes:
+        if len(sh) != 2 or (sh[0] > 0 and sh[1] != sx[1]):
+            raise ValueError(f"KAD: a song of shape {sh} against a baseline of D = {sx[1]}")
+    torch_in = hip.K._is_torch(x)
+    if torch_in:
+        import torch
+        dts = {x.dtype, *(y.dtype for y in songs)}
+        if len(dts) > 1:
+            x, songs = x.float(), [y.float() for y in songs]
+        cat = lambda parts: torch.cat(parts, 0) if parts else x[:0]                  # noqa: E731
+    else:
+        x = np.asarray(x)
+        songs = [np.asarray(y) for y in songs]
+        if len({x.dtype, *(y.dtype for y in songs)}) > 1:
+            x, songs = x.astype(np.float32), [y.astype(np.float32) for y in songs]
+        cat = lambda parts: np.concatenate(parts, 0) if parts else x[:0]             # noqa: E731
+    row_bytes = max(1, sx[1] * (x.element_size() if torch_in else x.itemsize))
+    S = len(songs)
+    res = {k: np.full(S, np.nan) for k in ("mmd2", "kyy_mean", "kxy_mean")}
+    res["status"] = np.zeros(S, dtype=np.int32)
+    s0, bw = 0, bandwidth
+    while True:                                   # batches of whole songs under the byte budget (at least one song each)
+        s1, rows = s0, 0
+        while s1 < S and (s1 == s0 or rows + shapes[s1][0] * row_bytes <= max_bytes):
+            rows += shapes[s1][0] * row_bytes
+            s1 += 1
+        part = [y.reshape(-1, sx[1]) if shapes[s0 + i][0] == 0 else y for i, y in enumerate(songs[s0:s1])]
+        off = np.concatenate([[0], np.cumsum([shapes[s][0] for s in range(s0, s1)], dtype=np.int64)])
+        r = hip.kad_individual(x, cat(part), off, bandwidth=bw, device=device)
+        for k in ("mmd2", "kyy_mean", "kxy_mean", "status"):
+            res[k][s0:s1] = r[k]
+        res.update(kxx_mean=r["kxx_mean"], bandwidth=r["bandwidth"], n=r["n"])
+        bw, s0 = r["bandwidth"], s1
+        if s0 >= S:
+            break
+    values = float(scale) * res["mmd2"]
+    return (values, res) if details else values
 
 
 class KernelAudioDistance:
@@ -78,6 +134,58 @@ class KernelAudioDistance:
             x, y = x.astype(np.float32), y.astype(np.float32)
         return calc_kernel_audio_distance(x, y, bandwidth=bandwidth, scale=scale, device=self.device_index, details=details)
 
+    def score_individual(self, baseline: PathLike, eval_dir: PathLike, csv_name: Union[Path, str], bandwidth: Optional[float] = None,
+                         scale: float = 1.0) -> Path:
+        """Per-file KAD against the baseline, written as ``path,score`` lines sorted by |score| (FrechetAudioDistance.score_individual's
+        format).  All songs go in one batched GPU call with one sigma; files whose embedding is missing, unreadable, of another D or
+        shorter than two frames are logged and dropped.  A ``str`` name goes under data/kad-individual/<model>/; an existing CSV is
+        left as it is."""
+        csv = Path(csv_name)
+        if isinstance(csv_name, str):
+            csv = Path("data") / "kad-individual" / self.ml.name / csv_name
+        if csv.exists():
+            log.info(f"CSV file {csv} already exists, exiting...")
+            return csv
+        x = self.load_rows(baseline)
+        files = list(Path(eval_dir).glob("*.*"))
+
+        def _read(f):
+            try:
+                return self.fad.read_embedding_file(f)
+            except Exception as e:      # noqa: BLE001
+                traceback.print_exc()
+                log.error(f"An error occurred calculating individual KAD using model {self.ml.name} on file {f}")
+                log.error(e)
+                return None
+
+        embds = tmap(_read, files, desc="Loading embeddings", max_workers=self.fad.audio_load_worker)
+        keep = []
+        for f, e in zip(files, embds):
+            if e is None:
+                continue
+            if e.ndim != 2 or e.shape[1] != x.shape[1]:
+                log.error(f"Embedding of {f} has shape {e.shape}; expected [*, {x.shape[1]}]")
+            elif e.shape[0] < 2:
+                log.error(f"Individual KAD of {f} dropped: {e.shape[0]} frame(s), KAD needs at least 2")
+            else:
+                keep.append((f, e))
+        dts = {x.dtype, *(e.dtype for _, e in keep)}
+        if len(dts) > 1 or np.float64 in dts:      # one dtype for the call; float64 caches are narrowed, as score() does
+            x, keep = x.astype(np.float32), [(f, e.astype(np.float32)) for f, e in keep]
+        pairs = []
+        if keep:
+            values, res = calc_kernel_audio_distance_individual(x, [e for _, e in keep], bandwidth=bandwidth, scale=scale,
+                                                                device=self.device_index, details=True)
+            for (f, _), v, st in zip(keep, values, res["status"]):
+                if st == 0:
+                    pairs.append((f, np.float64(v)))
+                else:
+                    log.error(f"An error occurred calculating individual KAD using model {self.ml.name} on file {f} (status {st}: "
+                              f"{'fewer than two frames' if st == -6 else 'non-finite rows'})")
+        pairs = sorted(pairs, key=lambda p: np.abs(p[1]))
+        write(csv, "\n".join(",".join(str(v).replace(",", "_") for v in row) for row in pairs))
+        return csv
+
 
 def main(argv=None):
     from .cli import _registry, _setup_logging
@@ -88,10 +196,12 @@ def main(argv=None):
     p.add_argument("model", type=str, choices=list(models), help="embedding model")
     p.add_argument("baseline", type=str, help="baseline dataset directory")
     p.add_argument("eval", type=str, help="directory to evaluate")
-    p.add_argument("csv", type=str, nargs="?", help="append the result to this CSV")
+    p.add_argument("csv", type=str, nargs="?", help="append the result to this CSV; with --indiv: where per-song scores go "
+                                                    "(default kad-individual-results.csv)")
     p.add_argument("--bandwidth", type=float, default=None, help="kernel sigma (default: median pairwise distance of the baseline)")
     p.add_argument("--scale", type=float, default=1.0, help="factor applied to the reported MMD^2 (default 1)")
     p.add_argument("-w", "--workers", type=int, default=8, help="number of workers")
+    p.add_argument("--indiv", action="store_true", help="one score per song of the eval directory")
     a = p.parse_args(argv)
     model = models[a.model]
 
@@ -100,6 +210,12 @@ def main(argv=None):
         if Path(dataset).is_dir():
             cache_embedding_files(dataset, model, workers=a.workers)
     kad = KernelAudioDistance(model, audio_load_worker=a.workers, load_model=False)
+    if a.indiv:
+        assert Path(a.eval).is_dir(), "Individual KAD requires a directory as the evaluation dataset"
+        out = Path(a.csv or "kad-individual-results.csv")
+        kad.score_individual(a.baseline, a.eval, out, bandwidth=a.bandwidth, scale=a.scale)
+        log.info(f"Individual KAD scores saved to {out}")
+        return
     value, res = kad.score(a.baseline, a.eval, bandwidth=a.bandwidth, scale=a.scale, details=True)
     if a.csv:
         target = Path(a.csv)

@@ -332,6 +332,21 @@ int fad_kad_median_distance(const void* x, int64_t n, int64_t ld, int64_t d, int
  * otherwise a rounding residue may leave a tiny positive median, which is used as the bandwidth. */
 int fad_kad(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype,
             int on_device, double bandwidth, fad_kad_result_t* out, int device, void* stream);
+/* ------------------------------------------------------------------ per-song KAD (--indiv)
+ * For every song s (rows [offsets[s], offsets[s+1]) of `rows` [n_rows x d]), KAD between the baseline x [n x d] and that song alone,
+ * with one sigma for all songs: what fad_kad(x, song_s, bandwidth = sigma) gives, in one call that packs the baseline, finds sigma
+ * (bandwidth <= 0: the median distance of x) and sums its Kxx once:
+ *   mmd2[s] = Kxx + Kyy(s) - 2 Kxy(s),  Kyy(s) = sum_{i != j in s} k / (m_s (m_s - 1)),  Kxy(s) = sum_{x, j in s} k / (n m_s).
+ * `base` receives kxx_mean, bandwidth and n -- bit for bit what fad_kad and fad_kad_median_distance give on the same x -- with
+ * m = n_rows and NaN in its other fields.  Songs with fewer than 2 frames get status FAD_ERR_TOO_FEW_ROWS, songs with a NaN/Inf row
+ * norm FAD_ERR_NOT_FINITE, both with NaN outputs; the other songs do not depend on them.  Rows and x are host or device per on_device
+ * (one dtype: float16, bfloat16 or float32); offsets [n_songs + 1] and the outputs [n_songs] are host pointers either way.  Argument
+ * errors (offsets that do not run from 0 to n_rows or that decrease, dtype, d, ld, n < 2 -> FAD_ERR_TOO_FEW_ROWS) come before any
+ * device call.  n_rows < 2^31 - 128.  The same bits on every run; synchronises `stream`. */
+int fad_kad_individual(const void* x, int64_t n, int64_t ldx, const void* rows, int64_t n_rows, int64_t ldy,
+                       const int64_t* offsets, int64_t n_songs, int64_t d, int dtype, int on_device, double bandwidth,
+                       fad_kad_result_t* base, double* out_mmd2, double* out_kyy_mean, double* out_kxy_mean,
+                       int32_t* out_status, int device, void* stream);
 
 /* ------------------------------------------------------------------ diagnostics (NOT part of the drop-in surface)
  * Nothing in fadtk corresponds to these two calls and no binding of the reference needs them: they exist for bench.py's
