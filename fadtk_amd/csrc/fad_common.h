@@ -31,11 +31,6 @@ int set_error(int code, const char* fmt, ...);
 int check_device(int device);         // FAD_OK if `device` is a gfx950 GPU
 int num_cus(int device);
 
-// Host (pageable) -> device copy of `rows` rows of `width` bytes through pinned, multi-threaded staging (host_stage.cpp).
-// On return every read of `src` is done and the copy is ordered before later work on `st`; the device is never waited for.
-int host_to_device_2d(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t rows, int device,
-                      hipStream_t st);
-
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // The quotient np.mean forms from its float32 running sum (fadtk/fad.py:48 -> numpy _methods._mean: true_divide(float32 sum, intp
 // count) resolves to the float64 loop and is cast back to float32).  Identical to a float32 division while n is a float32 value
@@ -70,7 +65,7 @@ struct DevBuf {
 int segment_running_sums_launch(const void* rows, int64_t ld, int d, int dtype, const int64_t* d_offsets, int64_t n_segments, float* d_out,
                                 hipStream_t st, DevBuf* jobs = nullptr, int64_t mean_rows = 0, int device = 0);
 
-// moments.hip: the library's side stream of a device (non-blocking, high priority; nullptr with FAD_MOMENTS_RUNSUM_SIDE=0): the running-sum walks
+// moments.hip: the library's side stream of a device (non-blocking, high priority; nullptr if it cannot be created): the running-sum walks
 hipStream_t moments_side_stream(int device);
 // moments.hip: covariances of B songs of float16 frames on the moments tile kernels (for frechet.hip's batched per-song chain)
 bool song_cov_f16_ok(const void* rows, int64_t ld, int d);

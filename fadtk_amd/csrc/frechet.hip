@@ -35,8 +35,6 @@ SongKnobs SongKnobs::from_env() {
     if (const char* e = getenv("FAD_SONG_BIG")) k.big_min = atol(e);
     if (const char* e = getenv("FAD_SONG_RES")) k.res = (e[0] == '0') ? 0 : (e[0] == '1' ? 1 : 2);
     if (const char* e = getenv("FAD_SONG_FAST")) k.fast = (e[0] == '0') ? 0 : (e[0] == '2' ? 2 : 1);
-    k.gram = !off("FAD_SONG_GRAM"); k.stats16 = !off("FAD_SONG_STATS16"); k.cov16 = !off("FAD_SONG_COV16"); k.sym = !off("FAD_SONG_SYM");
-    if (const char* e = getenv("FAD_SONG_SYM_MAX_FRAMES_PER_DIM")) k.sym_max_mult = (int64_t)atoll(e);
     if (const char* e = getenv("FAD_FAST_TRACE")) k.trace = e[0] == '1';
     k.scaled = !off("FAD_SONG_SCALED");
     if (const char* e = getenv("FAD_SONG_L0_SCALE")) { const double v = atof(e); if (v > 0.0) k.l0_scale = v; }
@@ -355,13 +353,7 @@ template <int NJ> static void fast_big_launch(int d, int mode, const nsf::SplitA
     else hipLaunchKernelGGL((nsf::nsf_big<nsf::SP_U, NJ>), dim3(two + B), dim3(256), nsf::kBigLds, st, g);
 }
 // the residual partials an SP_T launch of the batch leaves per problem (the check riding on the SP_U launch sums them: g.nslots)
-// FAD_BIG_NARROW_BELOW (probe switch): narrow tiles for launches of fewer than that many wide-tile workgroups (default: big_nj's 512)
-static int fast_big_nj(int d, int products, unsigned B) {
-    static const int below = [] { const char* e = getenv("FAD_BIG_NARROW_BELOW"); return e ? atoi(e) : 0; }();
-    if (below > 0) return (products * (d / 128) * (d / 128) * (int)B < below) ? 1 : 2;
-    return nsf::big_nj(d, products, (int)B);
-}
-static int fast_big_t_slots(int d, unsigned B) { return nsf::big_tiles(d, fast_big_nj(d, 1, B)); }
+static int fast_big_t_slots(int d, unsigned B) { return nsf::big_tiles(d, nsf::big_nj(d, 1, (int)B)); }
 static int fast_split_big(int d, int mode, nsf::SplitArgs g, hipStream_t st, unsigned B, int device) {
     static std::atomic<unsigned> ready{0};
     if (device >= 0 && device < 32 && !(ready.load(std::memory_order_acquire) & (1u << device))) {
@@ -370,7 +362,7 @@ static int fast_split_big(int d, int mode, nsf::SplitArgs g, hipStream_t st, uns
         ready.fetch_or(1u << device, std::memory_order_release);
     }
     g.nprob = (int)B;
-    if (fast_big_nj(d, mode == nsf::SP_U ? 2 : 1, B) == 1) fast_big_launch<1>(d, mode, g, st, B);
+    if (nsf::big_nj(d, mode == nsf::SP_U ? 2 : 1, (int)B) == 1) fast_big_launch<1>(d, mode, g, st, B);
     else fast_big_launch<2>(d, mode, g, st, B);
     return FAD_OK;
 }
@@ -841,11 +833,10 @@ static int pairs_enqueue(Workspace& ws, int d, int B, const fad_moments_t* const
                          int mean_dtype, hipStream_t st) {
     const size_t dd = (size_t)d * d;
     const int nb = d / 32;
-    // FAD_PAIRS_BIG = smallest batch whose products run on the 128 x 128 / 128 x 64 tiles of ns_fast_big.h (their operand traffic per
-    // block is a tenth of the 32 x 32 kernels'; below, too few workgroups to fill the chip); read per call, 0 = never
-    const char* big_env = getenv("FAD_PAIRS_BIG");
-    const long big_min = big_env ? atol(big_env) : 3;
-    const bool big = big_min > 0 && B >= big_min && d >= 256;
+    // smallest batch whose products run on the 128 x 128 / 128 x 64 tiles of ns_fast_big.h (their operand traffic per block is a
+    // tenth of the 32 x 32 kernels'; below, too few workgroups to fill the chip)
+    constexpr int kPairsBigMin = 3;
+    const bool big = B >= kPairsBigMin && d >= 256;
     // (scaled steps: iteration 0 of the 32 x 32-tile family takes them as well; the batch only needs them on ONE family at a time)
     const bool wide = wide_enabled(ws.pool);
     const int max_low = wide ? kMaxLowWide : kMaxLow;
@@ -1347,14 +1338,13 @@ int fad_frechet_multi_end(fad_frechet_job_t* job, int count, double* out_fad, fa
         // workgroups; sixteen problems per launch fill the chip: ~0.3 ms per pair).  K1 left every pair's (mu, Sigma) as the single route
         // would form them (numpy's means where the handles carry them) in its block; the product Sigma_1 Sigma_2 is formed anew in
         // float64 (fast_decide_one: why not the chain's).  Pairs the batch cannot close (no finite root: the eps fallback of fad.py:94-99;
-        // too few rows) stay for the single entry point below, which reports them as it always did.  FAD_PAIRS_F64_BATCH=0: pair by pair.
-        static const bool f64_batch = [] { const char* e = getenv("FAD_PAIRS_F64_BATCH"); return !(e && e[0] == '0'); }();
+        // too few rows) stay for the single entry point below, which reports them as it always did.
         // (only what the chain REJECTED or declined -- status 2: "the float64 route decides".  A pair the blind batch merely did not finish
         //  -- status 0 / 4 -- goes to the single entry point as before: it tops the chain up by a few launches and teaches the thread the
         //  launch count its kind needs; sent here instead, every batch of k^-1 pairs ran 21 float64 steps: r06b, 2 570 scores/s for 5 200)
         int declined = 0;
         for (int b = 0; b < count; ++b) if (!done[b] && chain_status[b] == 2) ++declined;
-        if (f64_batch && rc == FAD_OK && declined >= 2) {
+        if (rc == FAD_OK && declined >= 2) {
             const PairBlock L = pair_block(d);
             const size_t dd = (size_t)d * d;
             char* blk = static_cast<char*>(ws.fast_pairs.p);

@@ -161,11 +161,6 @@ struct SongKnobs {
     long big_min = 8;           // FAD_SONG_BIG: smallest batch that iterates on the 128 x 128 tiles of ns_fast_big.h (0 = never)
     int res = 2;                // FAD_SONG_RES: D = 128 -- 2 products and iteration in one workgroup per song, 1 the iteration only, 0 the batched kernels
     int fast = 1;               // FAD_SONG_FAST: 0 = float64 routes only, 1 = low-precision chain with float64 fallback, 2 = strict (error if it accepts no song)
-    bool gram = true;           // FAD_SONG_GRAM: songs of fewer frames than dimensions through the n x n Gram matrix
-    bool stats16 = true;        // FAD_SONG_STATS16: float16 frames -> per-song statistics on the packed-f16 kernel
-    bool cov16 = true;          // FAD_SONG_COV16: float16 frames -> per-song covariances on the moments tile kernels
-    bool sym = true;            // FAD_SONG_SYM: the symmetric route sqrt(Sigma_b) Sigma_s sqrt(Sigma_b) for long songs
-    int64_t sym_max_mult = 8;   // FAD_SONG_SYM_MAX_FRAMES_PER_DIM
     bool trace = false;         // FAD_FAST_TRACE: one stderr line per song of the low-precision chain
     double l0_scale = 0.5;      // FAD_SONG_L0_SCALE: multiplier on the x_min estimate the scaled steps start from (measured 3 / 2 / 1 / 0.5 / 0.25:
                                 // 10 / 10 / 9 / 8 / 8 iterations at 32 x [1500 x 768], 10 / 9 / 8 / 7 / 8 at [1200 x 512], 7 / 6 / 6 / 7 / 8 at [2250 x 128])

@@ -655,13 +655,12 @@ static int batched_core(int d, const double* dmu_b, const double* dcov_b, const 
                         hipStream_t st, Workspace& ws, const SongKnobs& knobs, double* out_scores, int32_t* out_status, bool defer_means) {
     const int64_t dd = (int64_t)d * d;
     std::vector<int64_t> pairs, gram, gram_ns, general;
-    const bool gram_on = knobs.gram;
     for (int64_t s = 0; s < n_songs; ++s) {
         const int64_t n = h_off[s + 1] - h_off[s];
         if (n < 2) { out_status[s] = FAD_ERR_TOO_FEW_ROWS; out_scores[s] = __builtin_nan(""); }
         else if (n == 2) { out_status[s] = FAD_OK; pairs.push_back(s); }
-        else if (gram_on && n <= GRAM_MAX && n - 1 < d) { out_status[s] = FAD_OK; gram.push_back(s); }
-        else if (gram_on && n - 1 < d) { out_status[s] = FAD_OK; gram_ns.push_back(s); }
+        else if (n <= GRAM_MAX && n - 1 < d) { out_status[s] = FAD_OK; gram.push_back(s); }
+        else if (n - 1 < d) { out_status[s] = FAD_OK; gram_ns.push_back(s); }
         else { out_status[s] = FAD_OK; general.push_back(s); }
     }
     const bool others = !gram.empty() || !gram_ns.empty() || !general.empty();
@@ -679,7 +678,6 @@ static int batched_core(int d, const double* dmu_b, const double* dcov_b, const 
     std::vector<double> h_scal;
     double tr_b = 0.0;
     if (others) {                       // (two-frame songs get their scalars from pair_stats_diff)
-        const bool stats16_on = knobs.stats16;
         // songs of many frames: numpy's float32 running sums per song in a kernel of their own (the reference's per-song mean, fad.py:377)
         // -- on a stream of its own when the caller (batched_impl) defers the mean terms
         const float* runs = defer_means ? kMeanPlaceholder : nullptr;
@@ -690,7 +688,7 @@ static int batched_core(int d, const double* dmu_b, const double* dcov_b, const 
                                                 (h_off[n_songs] - h_off[0]) / n_songs, device));
             runs = static_cast<const float*>(ws.songrun.p);
         }
-        if (std::is_same<TIn, r_f16>::value && stats16_on && (h_off[n_songs] - h_off[0]) / n_songs >= 64 && song_cov_f16_ok(drows, ld, d)) {
+        if (std::is_same<TIn, r_f16>::value && (h_off[n_songs] - h_off[0]) / n_songs >= 64 && song_cov_f16_ok(drows, ld, d)) {
             const int chunks = (int)cdiv(d, 128);
             double* part = scal;
             if (chunks > 1) { FAD_TRY(ws.rows2.reserve((size_t)2 * n_songs * chunks * sizeof(double))); part = static_cast<double*>(ws.rows2.p); }
@@ -855,8 +853,7 @@ static int batched_core(int d, const double* dmu_b, const double* dcov_b, const 
             NsState* dstates = static_cast<NsState*>(ws.small.p);
             enqueue_clear_states(dstates, ns, st);
             NsState* hs = nullptr;
-            const int sym_on = knobs.sym ? 1 : 0;
-            NsProblem pb{np, ns, gmat, npp, eye, 0, zeros, 0, zeros, 0, -1, sym_on};    // A = G' I, symmetric like every iterate
+            NsProblem pb{np, ns, gmat, npp, eye, 0, zeros, 0, zeros, 0, -1, 1};    // A = G' I, symmetric like every iterate
             FAD_TRY(run_ns(pb, 0, 0.0, device, st, ws, &hs));                          // (synchronises: the index vectors may go)
             std::vector<double> h_trg((size_t)ns * GRAM_TR_PARTS);
             FAD_HIP_TRY(hipMemcpy(h_trg.data(), trg, h_trg.size() * sizeof(double), hipMemcpyDeviceToHost));
@@ -894,9 +891,8 @@ static int batched_core(int d, const double* dmu_b, const double* dcov_b, const 
             const int64_t B = (int64_t)std::min<size_t>((size_t)sub, general.size() - g0);
             FAD_HIP_TRY(hipMemcpyAsync(ids_dev, general.data() + g0, B * sizeof(int64_t), hipMemcpyHostToDevice, st));
             // float16 frames: the covariances on the float16 matrix pipe, shifted by the song's mean (moments_kernels.h: song_cov_*;
-            // FAD_SONG_COV16=0: the float64 MFMA kernel, as for every other dtype)
-            const bool cov16_on = knobs.cov16;
-            if (std::is_same<TIn, r_f16>::value && cov16_on && var_exact && song_cov_f16_ok(drows, ld, d)) {      // (only with the exact diagonal)
+            // else the float64 MFMA kernel, as for every other dtype)
+            if (std::is_same<TIn, r_f16>::value && var_exact && song_cov_f16_ok(drows, ld, d)) {      // (only with the exact diagonal)
                 int64_t max_frames = 0;
                 for (int64_t b = 0; b < B; ++b) { const int64_t sg = general[g0 + b]; max_frames = std::max(max_frames, h_off[sg + 1] - h_off[sg]); }
                 FAD_TRY(song_cov_f16_launch(drows, ld, d, d_off, ids_dev, B, max_frames, mean_exact, var_exact, covs, ws.songcov, device, st));
@@ -921,11 +917,10 @@ static int batched_core(int d, const double* dmu_b, const double* dcov_b, const 
     // the covariance of its transformed frames -- symmetric, like every iterate of its root, and the iteration's products skip
     // the mirrored tiles (GemmType::sym); the D x D product Sigma_b Sigma_s is never formed.  Costs one [n x D][D x D] product
     // per song: longer songs (Encodec: 2250 frames at D = 128) and baselines whose root does not converge keep the route below.
-    const bool symroute_on = knobs.sym;
-    if (symroute_on && d >= 64 && !general.empty()) {
+    constexpr int64_t kSymMaxFramesPerDim = 8;
+    if (d >= 64 && !general.empty()) {
         std::vector<int64_t> sym_songs, rest;
-        const int64_t max_mult = knobs.sym_max_mult;
-        for (const int64_t sg : general) ((h_off[sg + 1] - h_off[sg] <= max_mult * d) ? sym_songs : rest).push_back(sg);
+        for (const int64_t sg : general) ((h_off[sg + 1] - h_off[sg] <= kSymMaxFramesPerDim * d) ? sym_songs : rest).push_back(sg);
         bool have_root = false;
         double *broot = nullptr, *eye = nullptr, *zeros = nullptr;
         if (!sym_songs.empty()) {
@@ -1133,7 +1128,7 @@ extern "C" int fad_frechet_batched_vs_baseline(int d, const double* mu_b, const 
         const int64_t row_bytes = (int64_t)d * es;
         FAD_TRY(ws.rows.reserve((size_t)(n_rows > 0 ? n_rows : 1) * row_bytes + 16));
         if (n_rows > 0)
-            FAD_TRY(host_to_device_2d(ws.rows.p, (size_t)row_bytes, rows, (size_t)(ld * es), (size_t)row_bytes, (size_t)n_rows, device, st));
+            FAD_HIP_TRY(hipMemcpy2DAsync(ws.rows.p, (size_t)row_bytes, rows, (size_t)(ld * es), (size_t)row_bytes, (size_t)n_rows, hipMemcpyHostToDevice, st));
         drows = ws.rows.p; dld = d;
     }
     FAD_TRY(ws.offs.reserve((size_t)(n_songs + 1) * sizeof(int64_t)));

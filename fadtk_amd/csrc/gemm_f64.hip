@@ -461,11 +461,9 @@ int gemm_f64_launch(int d, const GemmType* types, int ntypes, int64_t batch, con
         }
         g.skip = skip ? skip + done * skip_stride : nullptr;
         g.skip_stride = skip_stride; g.ntypes = ntypes;
-        static const int env_remap = [] { const char* e = getenv("FAD_GEMM_REMAP"); return e ? atoi(e) : 1; }();
-        static const int env_depth = [] { const char* e = getenv("FAD_GEMM_DEPTH"); return e ? atoi(e) : 1; }();
         g.sym = (sym && bt == 64) ? 1 : 0;
         g.tri = (ntypes == 1) ? types[0].b_upper : 0;
-        g.remap = g.tri ? 0 : env_remap;            // (the XCD map hands whole column blocks to an XCD: with a triangular B
+        g.remap = g.tri ? 0 : 1;                    // (the XCD map hands whole column blocks to an XCD: with a triangular B
                                                     //  those blocks cost 1x .. 5x -- plain order mixes them)
         g.pstride = partial_stride > 0 ? partial_stride : (int)slots;
         g.gemm_z = (int)(m * ntypes);
@@ -479,12 +477,9 @@ int gemm_f64_launch(int d, const GemmType* types, int ntypes, int64_t batch, con
             if (full) hipLaunchKernelGGL((gemm_f64_kernel<64, 2, false, true>), grid, dim3(256), 0, stream, d, g);
             else hipLaunchKernelGGL((gemm_f64_kernel<64, 2, false, false>), grid, dim3(256), 0, stream, d, g);
         } else {
-            static const int env_w8 = [] { const char* e = getenv("FAD_GEMM_WAVES8"); return e ? atoi(e) : 1; }();
-            const bool w8 = env_w8 && full && (int64_t)grid.x * grid.y * (unsigned)(m * ntypes) <= (int64_t)num_cus(device);
+            const bool w8 = full && (int64_t)grid.x * grid.y * (unsigned)(m * ntypes) <= (int64_t)num_cus(device);
             if (w8) hipLaunchKernelGGL((gemm_f64_kernel<32, 1, true, true, 8>), grid, dim3(512), 0, stream, d, g);
-            else if (full && env_depth == 1) hipLaunchKernelGGL((gemm_f64_kernel<32, 1, true, true>), grid, dim3(256), 0, stream, d, g);
-            else if (full && env_depth == 2) hipLaunchKernelGGL((gemm_f64_kernel<32, 2, true, true>), grid, dim3(256), 0, stream, d, g);
-            else if (full) hipLaunchKernelGGL((gemm_f64_kernel<32, 3, true, true>), grid, dim3(256), 0, stream, d, g);
+            else if (full) hipLaunchKernelGGL((gemm_f64_kernel<32, 1, true, true>), grid, dim3(256), 0, stream, d, g);
             else hipLaunchKernelGGL((gemm_f64_kernel<32, 3, true, false>), grid, dim3(256), 0, stream, d, g);
         }
     }

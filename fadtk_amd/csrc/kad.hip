@@ -534,13 +534,13 @@ static int check_rows(const void* x, int64_t n, int64_t ld, int64_t d, int dtype
 }
 
 // rows -> the set's padded image and h (no check of the norms)
-static int pack_image(int slot, const void* x, int64_t n, int64_t ld, int64_t d, int dtype, int on_device, int device, hipStream_t st,
+static int pack_image(int slot, const void* x, int64_t n, int64_t ld, int64_t d, int dtype, int on_device, hipStream_t st,
                       KadWorkspace& ws, Packed* out) {
     const size_t es = dtype_size(dtype);
     const int64_t dp = depth_elems(d, dtype), n_pad = kad::blocks(n) * kTile;
     if (!on_device) {
         FAD_TRY(ws.raw[slot].reserve((size_t)(n * d) * es));
-        FAD_TRY(host_to_device_2d(ws.raw[slot].p, (size_t)d * es, x, (size_t)ld * es, (size_t)d * es, (size_t)n, device, st));
+        FAD_HIP_TRY(hipMemcpy2DAsync(ws.raw[slot].p, (size_t)d * es, x, (size_t)ld * es, (size_t)d * es, (size_t)n, hipMemcpyHostToDevice, st));
         x = ws.raw[slot].p;
         ld = d;
     }
@@ -560,9 +560,9 @@ static int pack_image(int slot, const void* x, int64_t n, int64_t ld, int64_t d,
 }
 
 // rows -> the set's padded image and h; reads back the norm sum and checks every norm is finite
-static int pack_set(int slot, const void* x, int64_t n, int64_t ld, int64_t d, int dtype, int on_device, int device, hipStream_t st,
+static int pack_set(int slot, const void* x, int64_t n, int64_t ld, int64_t d, int dtype, int on_device, hipStream_t st,
                     KadWorkspace& ws, Packed* out) {
-    FAD_TRY(pack_image(slot, x, n, ld, d, dtype, on_device, device, st, ws, out));
+    FAD_TRY(pack_image(slot, x, n, ld, d, dtype, on_device, st, ws, out));
     double* info_d = static_cast<double*>(ws.small.p) + 2 * slot;
     kad_norm_info_kernel<<<1, 256, 0, st>>>(out->h, n, info_d);
     FAD_HIP_TRY(hipGetLastError());
@@ -683,7 +683,7 @@ int fad_kad_median_distance(const void* x, int64_t n, int64_t ld, int64_t d, int
     hipStream_t st = static_cast<hipStream_t>(stream);
     KadWorkspace& ws = workspace(device);
     Packed px;
-    FAD_TRY(pack_set(0, x, n, ld, d, dtype, on_device, device, st, ws, &px));
+    FAD_TRY(pack_set(0, x, n, ld, d, dtype, on_device, st, ws, &px));
     return median_of_packed(px, dtype, device, st, ws, sigma);
 }
 
@@ -702,8 +702,8 @@ int fad_kad(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int
     KadWorkspace& ws = workspace(device);
 
     Packed px, py;
-    FAD_TRY(pack_set(0, x, n, ldx, d, dtype, on_device, device, st, ws, &px));
-    FAD_TRY(pack_set(1, y, m, ldy, d, dtype, on_device, device, st, ws, &py));
+    FAD_TRY(pack_set(0, x, n, ldx, d, dtype, on_device, st, ws, &px));
+    FAD_TRY(pack_set(1, y, m, ldy, d, dtype, on_device, st, ws, &py));
     double sigma = bandwidth;
     if (!(sigma > 0)) FAD_TRY(median_of_packed(px, dtype, device, st, ws, &sigma));
     if (!(sigma > 0) || !std::isfinite(sigma))
@@ -791,7 +791,7 @@ int fad_kad_individual(const void* x, int64_t n, int64_t ldx, const void* rows, 
 
     // the baseline: sigma and Kxx exactly as fad_kad finds them (the same launches, slots and fixed-order sum)
     Packed px;
-    FAD_TRY(pack_set(0, x, n, ldx, d, dtype, on_device, device, st, ws, &px));
+    FAD_TRY(pack_set(0, x, n, ldx, d, dtype, on_device, st, ws, &px));
     double sigma = bandwidth;
     if (!(sigma > 0)) FAD_TRY(median_of_packed(px, dtype, device, st, ws, &sigma));
     if (!(sigma > 0) || !std::isfinite(sigma))
@@ -825,7 +825,7 @@ int fad_kad_individual(const void* x, int64_t n, int64_t ldx, const void* rows, 
     // the songs: cross pass (X x Y) and band pass (pairs inside each song), per-column slots, one reduction per song
     if (n_rows > 0 && n_songs > 0) {
         Packed py;
-        FAD_TRY(pack_image(1, rows, n_rows, ldy, d, dtype, on_device, device, st, ws, &py));
+        FAD_TRY(pack_image(1, rows, n_rows, ldy, d, dtype, on_device, st, ws, &py));
         const int64_t TJ = kad::blocks(n_rows), m_pad = TJ * kTile;
         const int64_t rr = kad::cross_rows_per_unit(TI, TJ, kad::tiles_per_launch(depth, f32)), NR = kad::cross_ranges(TI, rr);
         std::vector<kad::Unit> bunits;

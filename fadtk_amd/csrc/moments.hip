@@ -62,7 +62,6 @@ struct fad_moments {
     hipEvent_t rs_reader = nullptr;        // ... and the handle's own event behind its last ASYNCHRONOUS reader (moments_mark_read): the next detached walk,
     bool rs_reader_set = false;            //     which rewrites the running sums on the side stream, waits for it
     bool staged_input = false;             // update_any is feeding host rows through the staging area: no detached walk over those
-    int r256_sl = 0;                       // FAD_MOMENTS_R256_SL (read at creation; experiments): split lanes of moments_reduce256, 0 = by the split count
     int tile256 = 1;                       // 0: FAD_MOMENTS_TILE256=0 (read at creation) keeps D >= 512 on the 128 x 128 kernel
     // the segment tables of the last fused update_segmented call, kept on the host: a caller feeding groups of the SAME file sizes
     // (30-second clips: every file 2250 frames) finds them on the device already -- no H2D copy in front of the tile kernel
@@ -145,7 +144,6 @@ static int ensure_kernel_attrs(int device) {
                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTrLds));
         }
     }
-    FAD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&moments_running_colsum_h16<32, 96, 5>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRsLds));
     FAD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&moments_running_colsum_h16<16, 192, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRsLds));
     FAD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&moments_running_colsum<raw_f16, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRunLds));
     FAD_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&moments_running_colsum<raw_f16, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRunLds));
@@ -342,10 +340,9 @@ static int update_tile256(int count, fad_moments* const* hs, const void* const* 
         hipLaunchKernelGGL((moments_tile256<FAD_F16, true>), dim3((unsigned)L.total), dim3(512), lds_bytes, st, L);
     }
     // split lanes per output group: one thread walks all splits of its four outputs with eight loads in flight.  Measured
-    // (scripts/probe_reduce_sl.py, guard + reduce): 2 sets x 43 splits 22.2 / 22.8 / 22.3 / 23.3 / 26.1 us at 1 / 2 / 4 / 8 / 16 lanes,
+    // (guard + reduce): 2 sets x 43 splits 22.2 / 22.8 / 22.3 / 23.3 / 26.1 us at 1 / 2 / 4 / 8 / 16 lanes,
     // 8 sets x 10 splits 26.5 / 28.3 / 32.3 / 37.6 / 58.9 us -- the LDS combine and the extra threads cost more than the shorter walks save.
     R.sl = (max_s > 128) ? 4 : 1;
-    if (h0->r256_sl == 1 || h0->r256_sl == 2 || h0->r256_sl == 4 || h0->r256_sl == 8 || h0->r256_sl == 16) R.sl = h0->r256_sl;
     const int G = 256 / R.sl;
     const int blocks = (int)cdiv((int64_t)R.nblk * 256, G) + (int)cdiv(d, 64);
     // 8 KiB of dynamic LDS the kernel never touches: 10 instead of 20 of its workgroups per CU.  Measured at config 3
@@ -364,14 +361,12 @@ static int update_tile256(int count, fad_moments* const* hs, const void* const* 
 // numpy's float32 running column sums (moments_kernels.h: moments_running_colsum) for the handles that asked for them: one launch for
 // all of them, in front of the update's other kernels (float64 frames: numpy's sum is the exact one to 1e-16 -- nothing to do)
 // The walk's stream: one per device (high priority: its 32 workgroups per matrix should be placed before the tile kernel's fill the
-// chip; they fit BESIDE a tile workgroup).  FAD_MOMENTS_RUNSUM_SIDE=0 (read once) keeps the walk in line on the caller's stream.
+// chip; they fit BESIDE a tile workgroup).  nullptr if the stream cannot be created: the walk then runs on the caller's stream.
 static hipStream_t runsum_side_stream(int device) {
     static std::mutex mu;
     static hipStream_t side[64] = {nullptr};
-    static int enabled = -1;
     std::lock_guard<std::mutex> lk(mu);
-    if (enabled < 0) { const char* e = getenv("FAD_MOMENTS_RUNSUM_SIDE"); enabled = (e && e[0] == '0') ? 0 : 1; }
-    if (!enabled || device < 0 || device >= 64) return nullptr;
+    if (device < 0 || device >= 64) return nullptr;
     if (!side[device]) {
         // (a CU-masked stream -- hipExtStreamCreateWithCUMask -- would keep the walk off some CUs, but it is a BLOCKING stream: it would
         //  synchronise with the legacy default stream most callers launch on.  The walk leaves CUs free by its grid instead: 16 workgroups
@@ -398,17 +393,10 @@ static hipEvent_t runsum_ring_event(int device) {
     return e;
 }
 
-// The float16 walk in one of its two shapes (moments_kernels.h): 16 columns per workgroup by default (FAD_MOMENTS_RUNSUM_COLS=32: the other).
-static int runsum_cols() {
-    static int cols = 0;
-    if (!cols) { const char* e = getenv("FAD_MOMENTS_RUNSUM_COLS"); cols = (e && atoi(e) == 32) ? 32 : 16; }
-    return cols;
-}
+// The float16 walk (moments_kernels.h): 16 columns per workgroup.
 static void launch_runsum_h16(const RunSumLaunch& L, int jobs, hipStream_t st, bool indexed = false) {
     if (indexed)
         hipLaunchKernelGGL((moments_running_colsum_h16<16, 192, 4, true>), dim3((unsigned)cdiv(L.d, 16), (unsigned)jobs), dim3(256), (RsShape<16, 192, 4>::lds), st, L);
-    else if (runsum_cols() == 32)
-        hipLaunchKernelGGL((moments_running_colsum_h16<32, 96, 5>), dim3((unsigned)cdiv(L.d, 32), (unsigned)jobs), dim3(256), (RsShape<32, 96, 5>::lds), st, L);
     else
         hipLaunchKernelGGL((moments_running_colsum_h16<16, 192, 4>), dim3((unsigned)cdiv(L.d, 16), (unsigned)jobs), dim3(256), (RsShape<16, 192, 4>::lds), st, L);
 }
@@ -688,7 +676,7 @@ static int update_device(fad_moments* h, const void* rows, int64_t n, int64_t ld
     return update_device_multi(1, &h, &rows, &n, &ld, dtype, st);
 }
 
-// Host rows -> HBM staging area of the handle in blocks of at most 1 GiB (host_to_device_2d: pinned, pipelined chunks), then
+// Host rows -> HBM staging area of the handle in blocks of at most 1 GiB (hipMemcpy2DAsync from the pageable rows), then
 // update_device on each block.  Nothing is synchronised: the copy of block k + 1 waits ON THE DEVICE for the kernels that
 // still read block k out of the same staging area.
 static int update_any(fad_moments* h, const void* rows, int64_t n, int64_t ld, int dtype, int on_device,
@@ -712,15 +700,14 @@ static int update_any(fad_moments* h, const void* rows, int64_t n, int64_t ld, i
         // (the host is inside the runtime's staged copy for its whole duration) runs while the device takes the moments -- and, for a
         // handle that carries numpy's running sums, the walk -- of piece p: only the last piece's kernels are left when the last byte has
         // crossed PCIe.  (One copy + one update: 2.04 ms of copy, then 0.07 + 0.37 ms of kernels for [100 000 x 512] float16.)
-        // Measured (scripts/probe_host_pieces.py, r05l): one piece 2.40 ms per update, 12 MB pieces 2.36, 24 MB pieces 2.24 (the copy alone: 2.04).
-        // FAD_H2D_PIECE_KB (default 24576; 0 = one piece, on the caller's stream).
-        static const int64_t piece_bytes = [] { const char* e = getenv("FAD_H2D_PIECE_KB"); return (int64_t)(e ? atoll(e) : 24576) * 1024; }();
-        int64_t piece_rows = (piece_bytes > 0) ? piece_bytes / (row_bytes > 0 ? row_bytes : 1) : m;
+        // Measured (r05l): one piece 2.40 ms per update, 12 MB pieces 2.36, 24 MB pieces 2.24 (the copy alone: 2.04).
+        constexpr int64_t kPieceBytes = (int64_t)24576 * 1024;
+        int64_t piece_rows = kPieceBytes / (row_bytes > 0 ? row_bytes : 1);
         piece_rows = (piece_rows / 256) * 256;
         if (piece_rows < 16 * (int64_t)h->d) piece_rows = 16 * (int64_t)h->d;     // (a piece keeps the kernels a whole update of its rows would get: >= 16 rows per column)
         if (piece_rows < 4096 || m < 2 * piece_rows) piece_rows = m;
         if (piece_rows == m) {
-            FAD_TRY(host_to_device_2d(h->stage.p, (size_t)row_bytes, src, (size_t)(ld * es), (size_t)row_bytes, (size_t)m, h->device, st));
+            FAD_HIP_TRY(hipMemcpy2DAsync(h->stage.p, (size_t)row_bytes, src, (size_t)(ld * es), (size_t)row_bytes, (size_t)m, hipMemcpyHostToDevice, st));
             FAD_TRY(update_device(h, h->stage.p, m, h->d, dtype, st));
         } else {
             if (!h->cp_st) {
@@ -736,7 +723,7 @@ static int update_any(fad_moments* h, const void* rows, int64_t n, int64_t ld, i
                 int64_t pm = (m - q0 < piece_rows) ? m - q0 : piece_rows;
                 if (m - q0 - pm < piece_rows / 2) pm = m - q0;                    // (no runt at the end)
                 char* dst = static_cast<char*>(h->stage.p) + q0 * row_bytes;
-                FAD_TRY(host_to_device_2d(dst, (size_t)row_bytes, src + q0 * ld * es, (size_t)(ld * es), (size_t)row_bytes, (size_t)pm, h->device, h->cp_st));
+                FAD_HIP_TRY(hipMemcpy2DAsync(dst, (size_t)row_bytes, src + q0 * ld * es, (size_t)(ld * es), (size_t)row_bytes, (size_t)pm, hipMemcpyHostToDevice, h->cp_st));
                 FAD_HIP_TRY(hipEventRecord(h->cp_ev[piece & 7], h->cp_st));
                 FAD_HIP_TRY(hipStreamWaitEvent(st, h->cp_ev[piece & 7], 0));
                 FAD_TRY(update_device(h, dst, pm, h->d, dtype, st));
@@ -744,7 +731,7 @@ static int update_any(fad_moments* h, const void* rows, int64_t n, int64_t ld, i
             }
         }
         // inputs above 1 GiB reuse the staging area: the runtime's pageable route makes no promise to order its staging copies
-        // behind the kernels that still read the previous block (the pinned routes of host_stage.cpp wait on the device)
+        // behind the kernels that still read the previous block
         if (r0 + m < n) FAD_HIP_TRY(hipStreamSynchronize(st));
     }
     return FAD_OK;
@@ -874,8 +861,6 @@ int fad_moments_create(int d, int device, fad_moments_t** out) {
     h->force_generic = fg && fg[0] == '1';
     const char* t2 = getenv("FAD_MOMENTS_TILE256");
     h->tile256 = !(t2 && t2[0] == '0');
-    const char* rs = getenv("FAD_MOMENTS_R256_SL");
-    h->r256_sl = rs ? atoi(rs) : 0;
     const char* nc = getenv("FAD_MOMENTS_CUS");        // plan for fewer CUs than the device has (a CU-masked stream)
     if (nc && atoi(nc) >= 8 && atoi(nc) < h->n_cu) h->n_cu = atoi(nc);
     *out = h;
@@ -1117,7 +1102,7 @@ static int update_segmented_impl(fad_moments_t* h, const void* rows, int64_t n, 
     if (!on_device) {      // one staged copy serves both kernels (bounded by caller: host blocks are per-batch)
         const int64_t row_bytes = (int64_t)h->d * es;
         FAD_TRY(h->stage.reserve((size_t)n * row_bytes + 16));
-        FAD_TRY(host_to_device_2d(h->stage.p, (size_t)row_bytes, rows, (size_t)(ld * es), (size_t)row_bytes, (size_t)n, h->device, st));
+        FAD_HIP_TRY(hipMemcpy2DAsync(h->stage.p, (size_t)row_bytes, rows, (size_t)(ld * es), (size_t)row_bytes, (size_t)n, hipMemcpyHostToDevice, st));
         drows = h->stage.p; dld = h->d;
     }
     double* dout = seg_sums;

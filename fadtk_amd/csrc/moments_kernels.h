@@ -1203,16 +1203,16 @@ __global__ __launch_bounds__(256) void moments_running_colsum(RunSumLaunch L) {
 // (moments_tile256<.., true>) was such a kernel -- with a walk workgroup on every CU even the launch that only reads its gate and exits
 // could not be placed, and the caller's stream stood still for 170-300 us per update (r05d) -- and is now held to 224 registers
 // (moments_tile256.h).  Workgroups whose columns share the rows' 128-byte lines are dealt to ONE XCD (b % 8).
-// Two shapes of the same kernel (FAD_MOMENTS_RUNSUM_COLS, read once): <16 columns, 192-row tiles, four tiles in flight> -- the default:
-// 9 cycles per row alone, 0.37 ms per 100 000 rows for up to eight matrices (d / 16 workgroups each: eight matrices of d = 512 put a
-// workgroup on every CU) -- and <32 columns, 96-row tiles, five tiles in flight>, which leaves half the chip alone but pays its per-tile
-// costs (the barrier, the first LDS reads of a tile) twice as often: 16-21 cycles per row (r05e, r05f).
+// The shape launched, <16 columns, 192-row tiles, four tiles in flight>: 9 cycles per row alone, 0.37 ms per 100 000 rows for up to eight
+// matrices (d / 16 workgroups each: eight matrices of d = 512 put a workgroup on every CU).  <32 columns, 96-row tiles, five tiles in
+// flight> leaves half the chip alone but pays its per-tile costs (the barrier, the first LDS reads of a tile) twice as often: 16-21
+// cycles per row (r05e, r05f).
 typedef _Float16 rs_h2 __attribute__((ext_vector_type(2)));
 template <int kRsCols, int kRsRows, int RING> struct RsShape {
     static constexpr int pitch = kRsRows + 4;                         // floats
     static constexpr size_t lds = (size_t)2 * kRsCols * pitch * sizeof(float);
 };
-constexpr size_t kRsLds = 25600;                                      // the larger of the two shapes' LDS (25 088 / 25 600 bytes)
+constexpr size_t kRsLds = RsShape<16, 192, 4>::lds;                   // 25 088 bytes
 template <int kRsCols, int kRsRows, int RING, bool IDX = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void moments_running_colsum_h16(RunSumLaunch L) {
     constexpr int kRsPitch = RsShape<kRsCols, kRsRows, RING>::pitch;

@@ -263,7 +263,7 @@ int fad_frechet_multi_end(fad_frechet_job_t* job, int count, double* out_fad, fa
  *   Newton-Schulz, one float64-accurate correction, accepted per song on a bound of what the correction neglects), with
  *   float16 frames also the covariances on the float16 matrix pipe; whatever that chain does not accept -- and every other D --
  *   the float64 Newton-Schulz routes.  Environment switches (tests, diagnosis): FAD_SONG_FAST=0 (float64 routes only),
- *   FAD_SONG_BIG=<smallest batch on 128 x 128 tiles>, FAD_SONG_RES=0, FAD_SONG_COV16=0, FAD_SONG_STATS16=0, FAD_FAST_TRACE=1.
+ *   FAD_SONG_BIG=<smallest batch on 128 x 128 tiles>, FAD_SONG_RES=0, FAD_FAST_TRACE=1.
  */
 int fad_frechet_batched_vs_baseline(int d, const double* mu_b, const double* cov_b,
                                     const void* rows, int64_t n_rows, int64_t ld, int dtype,

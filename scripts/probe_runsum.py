@@ -1,8 +1,7 @@
 #!/usr/bin/env python3
 """GPU probe: what numpy's float32 running column sums (fad_moments_set_reference_mean; csrc/moments_kernels.h:
-moments_running_colsum_h16) cost an update of S sets of [100000 x 512] float16 frames, with the walk on the device's side stream
-(default) and in line on the caller's stream (FAD_MOMENTS_RUNSUM_SIDE=0, read once per process: run the probe twice), and whether the
-mean it leads to is numpy's bit for bit on frames with an offset."""
+moments_running_colsum_h16) cost an update of S sets of [100000 x 512] float16 frames, with the walk on the device's side stream,
+and whether the mean it leads to is numpy's bit for bit on frames with an offset."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -11,7 +10,6 @@ from fadtk_amd import hip
 d, n = 512, 100000
 g = torch.Generator(device="cuda"); g.manual_seed(5)
 mats = [(torch.randn((n, d), generator=g, device="cuda") * 0.7 + 0.5).to(torch.float16) for _ in range(8)]
-side = os.environ.get("FAD_MOMENTS_RUNSUM_SIDE", "1")
 for sets in (2, 8):
     for ref in (0, 1):
         hs = [hip.Moments(d) for _ in range(sets)]
@@ -27,7 +25,7 @@ for sets in (2, 8):
             torch.cuda.synchronize(); t0 = time.perf_counter()
             hip.Moments.update_multi(hs, mats[:sets])
             torch.cuda.synchronize(); ts.append((time.perf_counter() - t0) * 1e3)
-        print(f"side={side} sets={sets} reference mean {'on ' if ref else 'off'}: update {np.median(ts):.3f} ms (min {min(ts):.3f})", flush=True)
+        print(f"sets={sets} reference mean {'on ' if ref else 'off'}: update {np.median(ts):.3f} ms (min {min(ts):.3f})", flush=True)
         if ref:
             mu = hs[0].finalize()[0]
             want = mats[0].cpu().numpy().mean(axis=0)                  # numpy: float32 running sum, float16 result

@@ -62,4 +62,4 @@ else:
         want_s = np.array(O.individual_scores(mu_b, cov_b, sg[-1:], run_sqrtm=True), dtype=np.float64)
         print("d", d, "oracle eig", want, "sqrtm(steep)", want_s)
         sc, st = hip.frechet_batched(mu_b, cov_b, rows, offs, mean_mode=1)
-        print("  fast", os.environ.get("FAD_SONG_FAST"), "sym", os.environ.get("FAD_SONG_SYM"), sc, st, "rel", np.abs(sc - want) / np.abs(want))
+        print("  fast", os.environ.get("FAD_SONG_FAST"), sc, st, "rel", np.abs(sc - want) / np.abs(want))
