@@ -19,6 +19,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 #include <vector>
 
 namespace fad {
@@ -123,12 +124,68 @@ __device__ __forceinline__ float tile_sum(const f32x16 (&acc)[2][2], float c, in
     return s;
 }
 
-template <int DT, int MODE>
-__global__ void __launch_bounds__(kThreads, 2) kad_pass_kernel(PassArgs p) {
-    extern __shared__ __attribute__((aligned(16))) char lds[];
+// The main loop of every pass: tile (I, J) -- row block I of `a` against column block J of `b` -- into the wave's accumulators, which
+// start at h[i] + h[j].  A barrier first (the previous tile is done with LDS), then h of the tile's rows and columns into LDS, where the
+// threads of the rows (tid < kTile) also run `row_lds(tid)`, a pass's own per-row LDS entry; then the k loop, 128 bytes of a row per
+// step: global -> registers (one step ahead) -> LDS (padded rows) -> chunk_mfma.
+template <int DT, typename RowLds>
+__device__ __forceinline__ void tile_mfma(const char* a, const char* b, const float* ha, const float* hb, int64_t pitch, int nchunks,
+                                          int64_t I, int64_t J, char* lds, RowLds&& row_lds, f32x16 (&acc)[2][2]) {
     char* la = lds;
     char* lb = lds + kOpBytes;
     float* lh = reinterpret_cast<float*>(lds + 2 * kOpBytes);                          // [0, 128): rows, [128, 256): columns
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
+    const char* ga = a + I * kTile * pitch;
+    const char* gb = b + J * kTile * pitch;
+
+    __syncthreads();                                                                  // the previous tile is done with LDS
+    if (tid < kTile) {
+        lh[tid] = ha[I * kTile + tid];
+        row_lds(tid);
+    } else {
+        lh[tid] = hb[J * kTile + tid - kTile];
+    }
+
+    // global -> registers: 128 rows x 128 bytes per operand = 1024 pieces of 16 B, 4 per thread
+    u32x4 ra[4], rb[4];
+    auto load = [&](int ch) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int row = (tid >> 3) + 32 * q, col = (tid & 7) * 16;
+            ra[q] = *reinterpret_cast<const u32x4*>(ga + row * pitch + ch * kChunk + col);
+            rb[q] = *reinterpret_cast<const u32x4*>(gb + row * pitch + ch * kChunk + col);
+        }
+    };
+    load(0);
+    __syncthreads();
+
+#pragma unroll
+    for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+        for (int bj = 0; bj < 2; ++bj) {
+            const float hc = lh[kTile + wn * 64 + bj * 32 + (lane & 31)];
+#pragma unroll
+            for (int g = 0; g < 16; ++g)
+                acc[bi][bj][g] = lh[wm * 64 + bi * 32 + (g & 3) + 8 * (g >> 2) + 4 * (lane >> 5)] + hc;
+        }
+
+    for (int ch = 0; ch < nchunks; ++ch) {
+        if (ch) __syncthreads();                                                      // everybody is through the last chunk
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int row = (tid >> 3) + 32 * q, col = (tid & 7) * 16;
+            *reinterpret_cast<u32x4*>(la + row * kLdsRow + col) = ra[q];
+            *reinterpret_cast<u32x4*>(lb + row * kLdsRow + col) = rb[q];
+        }
+        __syncthreads();
+        if (ch + 1 < nchunks) load(ch + 1);                                           // in flight under this chunk's MFMAs
+        chunk_mfma<DT>(la + wm * 64 * kLdsRow, lb + wn * 64 * kLdsRow, lane, acc);
+    }
+}
+
+template <int DT, int MODE>
+__global__ void __launch_bounds__(kThreads, 2) kad_pass_kernel(PassArgs p) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
     unsigned int* lhist = reinterpret_cast<unsigned int*>(lds + 2 * kOpBytes + 2 * kTile * 4);   // MODE_HIST: [2][kHistBins]
     double* lred = reinterpret_cast<double*>(lds + 2 * kOpBytes + 2 * kTile * 4);
 
@@ -144,49 +201,8 @@ __global__ void __launch_bounds__(kThreads, 2) kad_pass_kernel(PassArgs p) {
         const int64_t v = kad::slot_tile(L, p.cnt, &live);
         if (!live) continue;                                                          // uniform over the workgroup
         const kad::Tile t = p.tri ? kad::tri_tile(p.u0 + v, p.tiles_j) : kad::rect_tile(p.u0 + v, p.tiles_j);
-        const char* ga = p.a + t.I * kTile * p.pitch;
-        const char* gb = p.b + t.J * kTile * p.pitch;
-
-        __syncthreads();                                                              // the previous tile is done with LDS
-        if (tid < kTile) lh[tid] = p.ha[t.I * kTile + tid];
-        else lh[tid] = p.hb[t.J * kTile + tid - kTile];
-
-        // global -> registers: 128 rows x 128 bytes per operand = 1024 pieces of 16 B, 4 per thread
-        u32x4 ra[4], rb[4];
-        auto load = [&](int ch) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int row = (tid >> 3) + 32 * q, col = (tid & 7) * 16;
-                ra[q] = *reinterpret_cast<const u32x4*>(ga + row * p.pitch + ch * kChunk + col);
-                rb[q] = *reinterpret_cast<const u32x4*>(gb + row * p.pitch + ch * kChunk + col);
-            }
-        };
-        load(0);
-        __syncthreads();
-
         f32x16 acc[2][2];
-#pragma unroll
-        for (int bi = 0; bi < 2; ++bi)
-#pragma unroll
-            for (int bj = 0; bj < 2; ++bj) {
-                const float hc = lh[kTile + wn * 64 + bj * 32 + (lane & 31)];
-#pragma unroll
-                for (int g = 0; g < 16; ++g)
-                    acc[bi][bj][g] = lh[wm * 64 + bi * 32 + (g & 3) + 8 * (g >> 2) + 4 * (lane >> 5)] + hc;
-            }
-
-        for (int ch = 0; ch < p.nchunks; ++ch) {
-            if (ch) __syncthreads();                                                  // everybody is through the last chunk
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int row = (tid >> 3) + 32 * q, col = (tid & 7) * 16;
-                *reinterpret_cast<u32x4*>(la + row * kLdsRow + col) = ra[q];
-                *reinterpret_cast<u32x4*>(lb + row * kLdsRow + col) = rb[q];
-            }
-            __syncthreads();
-            if (ch + 1 < p.nchunks) load(ch + 1);                                     // in flight under this chunk's MFMAs
-            chunk_mfma<DT>(la + wm * 64 * kLdsRow, lb + wn * 64 * kLdsRow, lane, acc);
-        }
+        tile_mfma<DT>(p.a, p.b, p.ha, p.hb, p.pitch, p.nchunks, t.I, t.J, lds, [](int) {}, acc);
 
         const int rbase = wm * 64, cbase = wn * 64;
         if (MODE == MODE_SUM) {
@@ -284,8 +300,8 @@ __global__ void __launch_bounds__(256) kad_slots_sum_kernel(const double* __rest
 }
 
 // ------------------------------------------------------------------------------------------------- per-song passes
-// fad_kad_individual's cross (X x Y) and band (Y x Y inside each song) passes: the main loop of kad_pass_kernel, with an epilogue
-// that keeps per-column sums (kad_song_tiles.h).  In the 32 x 32 MFMA layout a lane owns its column, so a column's sum over a tile
+// fad_kad_individual's cross (X x Y) and band (Y x Y inside each song) passes: tile_mfma, with an epilogue that keeps per-column
+// sums (kad_song_tiles.h).  In the 32 x 32 MFMA layout a lane owns its column, so a column's sum over a tile
 // is 32 in-register adds per lane; the two lane halves and the two wm waves of a column meet once, at the end of a work unit.
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
@@ -339,9 +355,6 @@ __device__ __forceinline__ void col_sums(const f32x16 (&acc)[2][2], float c, int
 template <int DT, bool BAND>
 __global__ void __launch_bounds__(kThreads, 2) kad_cols_kernel(ColArgs p) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
-    char* la = lds;
-    char* lb = lds + kOpBytes;
-    float* lh = reinterpret_cast<float*>(lds + 2 * kOpBytes);                          // [0, 128): rows, [128, 256): columns
     int* lend = reinterpret_cast<int*>(lds + 2 * kOpBytes + 2 * kTile * 4);           // BAND: end of each row's song - J * 128, in [0, 128]
     double* lx = reinterpret_cast<double*>(lds + 2 * kOpBytes + 3 * kTile * 4);       // the wm = 1 waves' column sums of a unit
 
@@ -355,57 +368,16 @@ __global__ void __launch_bounds__(kThreads, 2) kad_cols_kernel(ColArgs p) {
         if (!live) continue;                                                          // uniform over the workgroup
         const int64_t u = p.u0 + v;
         const kad::Unit un = BAND ? p.units[u] : kad::cross_unit(u, p.TI, p.TJ, p.rr);
-        const char* gb = p.b + un.J * kTile * p.pitch;
         double dcol[2] = {0.0, 0.0};
 
         for (int64_t I = un.I0; I < un.I1; ++I) {
-            const char* ga = p.a + I * kTile * p.pitch;
-            __syncthreads();                                                          // the previous tile is done with LDS
-            if (tid < kTile) {
-                lh[tid] = p.ha[I * kTile + tid];
-                if (BAND) {
-                    const int64_t e = (int64_t)p.row_end[I * kTile + tid] - un.J * kTile;
-                    lend[tid] = e < 0 ? 0 : e > kTile ? kTile : (int)e;
-                }
-            } else {
-                lh[tid] = p.hb[un.J * kTile + tid - kTile];
-            }
-
-            u32x4 ra[4], rb[4];
-            auto load = [&](int ch) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int row = (tid >> 3) + 32 * q, col = (tid & 7) * 16;
-                    ra[q] = *reinterpret_cast<const u32x4*>(ga + row * p.pitch + ch * kChunk + col);
-                    rb[q] = *reinterpret_cast<const u32x4*>(gb + row * p.pitch + ch * kChunk + col);
-                }
-            };
-            load(0);
-            __syncthreads();
-
             f32x16 acc[2][2];
-#pragma unroll
-            for (int bi = 0; bi < 2; ++bi)
-#pragma unroll
-                for (int bj = 0; bj < 2; ++bj) {
-                    const float hc = lh[kTile + cbase + bj * 32 + (lane & 31)];
-#pragma unroll
-                    for (int g = 0; g < 16; ++g)
-                        acc[bi][bj][g] = lh[rbase + bi * 32 + (g & 3) + 8 * (g >> 2) + 4 * (lane >> 5)] + hc;
+            tile_mfma<DT>(p.a, p.b, p.ha, p.hb, p.pitch, p.nchunks, I, un.J, lds, [&](int r) {
+                if constexpr (BAND) {
+                    const int64_t e = (int64_t)p.row_end[I * kTile + r] - un.J * kTile;
+                    lend[r] = e < 0 ? 0 : e > kTile ? kTile : (int)e;
                 }
-
-            for (int ch = 0; ch < p.nchunks; ++ch) {
-                if (ch) __syncthreads();
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int row = (tid >> 3) + 32 * q, col = (tid & 7) * 16;
-                    *reinterpret_cast<u32x4*>(la + row * kLdsRow + col) = ra[q];
-                    *reinterpret_cast<u32x4*>(lb + row * kLdsRow + col) = rb[q];
-                }
-                __syncthreads();
-                if (ch + 1 < p.nchunks) load(ch + 1);
-                chunk_mfma<DT>(la + rbase * kLdsRow, lb + cbase * kLdsRow, lane, acc);
-            }
+            }, acc);
 
             if (BAND) {
                 const bool diag = I == un.J;
@@ -444,12 +416,7 @@ __global__ void __launch_bounds__(256) kad_row_end_kernel(const int64_t* __restr
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= m_pad) return;
     if (i >= m) { row_end[i] = 0; return; }
-    int64_t lo = 0, hi = n_songs;                                                     // offsets[lo] <= i < offsets[hi]
-    while (hi - lo > 1) {
-        const int64_t mid = lo + (hi - lo) / 2;
-        if (offsets[mid] <= i) lo = mid; else hi = mid;
-    }
-    row_end[i] = (int)offsets[lo + 1];
+    row_end[i] = (int)offsets[kad::song_of_row(offsets, n_songs, i) + 1];
 }
 
 // One workgroup per song: r_xy(j) = sum over the cross slot rows, r_yy(j) = sum over the band units of j's column block, both in a
@@ -575,50 +542,49 @@ static int pack_set(int slot, const void* x, int64_t n, int64_t ld, int64_t d, i
     return FAD_OK;
 }
 
-template <int MODE>
-static int launch_pass(int dtype, PassArgs p, int64_t grid, hipStream_t st) {
-    const size_t lds = MODE == MODE_SUM ? kLdsSum : kLdsHist;
+// f(std::integral_constant<int, DT>{}) for the rows' dtype: the one place a pass's kernel instantiation is chosen
+template <typename F>
+static int with_dtype(int dtype, F&& f) {
     switch (dtype) {
-        case FAD_F16: kad_pass_kernel<FAD_F16, MODE><<<(unsigned)grid, kThreads, lds, st>>>(p); break;
-        case FAD_BF16: kad_pass_kernel<FAD_BF16, MODE><<<(unsigned)grid, kThreads, lds, st>>>(p); break;
-        default: kad_pass_kernel<FAD_F32, MODE><<<(unsigned)grid, kThreads, lds, st>>>(p); break;
+        case FAD_F16: f(std::integral_constant<int, FAD_F16>{}); break;
+        case FAD_BF16: f(std::integral_constant<int, FAD_BF16>{}); break;
+        default: f(std::integral_constant<int, FAD_F32>{}); break;
     }
     FAD_HIP_TRY(hipGetLastError());
     return FAD_OK;
 }
 
-// Launch plan of one pass: (u0, cnt, grid) per launch.
-struct Launch { int64_t u0, cnt, grid; };
-static std::vector<Launch> plan(int64_t total, int64_t depth, bool f32, bool hist, int device) {
-    std::vector<Launch> out;
-    const int64_t per = kad::tiles_per_launch(depth, f32, hist);
-    for (int64_t u0 = 0; u0 < total; u0 += per) {
-        const int64_t cnt = std::min(per, total - u0);
-        out.push_back(Launch{u0, cnt, kad::launch_grid(cnt, grid_cap(device))});
-    }
-    return out;
+// the rows of `a` against those of `b`, over the triangle (tri: b is a) or the rectangle; each launch sets u0 and cnt
+static PassArgs pass_args(const Packed& a, const Packed& b, bool tri, float c) {
+    PassArgs p{};
+    p.a = a.img; p.b = b.img; p.ha = a.h; p.hb = b.h; p.pitch = a.pitch; p.n_a = a.n; p.n_b = b.n;
+    p.tiles_j = kad::blocks(b.n); p.tri = tri; p.nchunks = a.nchunks; p.c = c;
+    return p;
+}
+
+static std::vector<kad::Launch> pass_launches(const PassArgs& p, int dtype, bool hist, int device) {
+    const int64_t total = p.tri ? kad::tri_tiles(p.tiles_j) : kad::blocks(p.n_a) * p.tiles_j;
+    return kad::launches(total, kad::tiles_per_launch(p.pitch / (int64_t)dtype_size(dtype), dtype == FAD_F32, hist), grid_cap(device));
 }
 
 static int median_of_packed(const Packed& x, int dtype, int device, hipStream_t st, KadWorkspace& ws, double* sigma) {
-    const int64_t T = kad::blocks(x.n), P = x.n * (x.n - 1) / 2;
-    unsigned long long* hist_d = reinterpret_cast<unsigned long long*>(static_cast<double*>(ws.small.p) + 4096);
-    const auto launches = plan(kad::tri_tiles(T), x.pitch / (int64_t)dtype_size(dtype), dtype == FAD_F32, true, device);
+    const int64_t P = x.n * (x.n - 1) / 2;
+    PassArgs p = pass_args(x, x, true, 0.f);
+    p.hist = reinterpret_cast<unsigned long long*>(static_cast<double*>(ws.small.p) + 4096);
+    const auto launches = pass_launches(p, dtype, true, device);
     static const int shifts[3] = {21, 10, 0}, widths[3] = {11, 11, 10};
     uint64_t rank[2] = {(uint64_t)((P - 1) / 2), (uint64_t)(P / 2)};
     unsigned int pref[2] = {0, 0};
     std::vector<unsigned long long> hist(2 * kHistBins);
     for (int pass = 0; pass < 3; ++pass) {
-        FAD_HIP_TRY(hipMemsetAsync(hist_d, 0, 2 * kHistBins * sizeof(unsigned long long), st));
-        PassArgs p{};
-        p.a = p.b = x.img; p.ha = p.hb = x.h; p.pitch = x.pitch; p.n_a = p.n_b = x.n; p.tiles_j = T; p.tri = 1;
-        p.nchunks = x.nchunks; p.hist = hist_d;
+        FAD_HIP_TRY(hipMemsetAsync(p.hist, 0, 2 * kHistBins * sizeof(unsigned long long), st));
         p.pref0 = pref[0]; p.pref1 = pref[1]; p.two = pref[0] != pref[1];
         p.lo_shift = shifts[pass]; p.bits = widths[pass]; p.hi_shift = shifts[pass] + widths[pass];
-        for (const Launch& l : launches) {
+        for (const kad::Launch& l : launches) {
             p.u0 = l.u0; p.cnt = l.cnt;
-            FAD_TRY(launch_pass<MODE_HIST>(dtype, p, l.grid, st));
+            FAD_TRY(with_dtype(dtype, [&](auto dt) { kad_pass_kernel<dt, MODE_HIST><<<(unsigned)l.grid, kThreads, kLdsHist, st>>>(p); }));
         }
-        FAD_HIP_TRY(hipMemcpyAsync(hist.data(), hist_d, hist.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        FAD_HIP_TRY(hipMemcpyAsync(hist.data(), p.hist, hist.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
         FAD_HIP_TRY(hipStreamSynchronize(st));
         const bool two = p.two;
         for (int t = 0; t < 2; ++t) {
@@ -642,26 +608,47 @@ static int median_of_packed(const Packed& x, int dtype, int device, hipStream_t 
     return FAD_OK;
 }
 
-template <bool BAND>
-static int launch_cols(int dtype, const ColArgs& p, int64_t grid, hipStream_t st) {
-    switch (dtype) {
-        case FAD_F16: kad_cols_kernel<FAD_F16, BAND><<<(unsigned)grid, kThreads, kLdsCols, st>>>(p); break;
-        case FAD_BF16: kad_cols_kernel<FAD_BF16, BAND><<<(unsigned)grid, kThreads, kLdsCols, st>>>(p); break;
-        default: kad_cols_kernel<FAD_F32, BAND><<<(unsigned)grid, kThreads, kLdsCols, st>>>(p); break;
+// N sum passes into consecutive slot ranges, then sums_d[q] = pass q's slots summed in a fixed order (enqueued, not read back).
+// fad_kad runs XX, YY and XY; fad_kad_individual XX alone, so its Kxx comes from the same launches, slots and sum as fad_kad's.
+template <int N>
+static int sum_passes(const PassArgs (&passes)[N], int dtype, int device, hipStream_t st, KadWorkspace& ws, double* sums_d) {
+    std::vector<kad::Launch> launches[N];
+    int64_t off[N + 1] = {0};
+    for (int q = 0; q < N; ++q) {
+        launches[q] = pass_launches(passes[q], dtype, false, device);
+        off[q + 1] = off[q];
+        for (const kad::Launch& l : launches[q]) off[q + 1] += l.grid;
     }
+    FAD_TRY(ws.slots.reserve((size_t)off[N] * sizeof(double)));
+    int64_t* off_d = reinterpret_cast<int64_t*>(static_cast<double*>(ws.small.p) + 8);
+    FAD_HIP_TRY(hipMemcpyAsync(off_d, off, sizeof(off), hipMemcpyHostToDevice, st));
+    for (int q = 0; q < N; ++q) {
+        PassArgs p = passes[q];
+        p.slots = static_cast<double*>(ws.slots.p) + off[q];
+        for (const kad::Launch& l : launches[q]) {
+            p.u0 = l.u0; p.cnt = l.cnt;
+            FAD_TRY(with_dtype(dtype, [&](auto dt) { kad_pass_kernel<dt, MODE_SUM><<<(unsigned)l.grid, kThreads, kLdsSum, st>>>(p); }));
+            p.slots += l.grid;
+        }
+    }
+    kad_slots_sum_kernel<<<N, 256, 0, st>>>(static_cast<const double*>(ws.slots.p), off_d, sums_d);
     FAD_HIP_TRY(hipGetLastError());
     return FAD_OK;
 }
 
-// the launches of a column pass of `total` units of at most `unit_tiles` tiles each
-static std::vector<Launch> plan_units(int64_t total, int64_t unit_tiles, int64_t depth, bool f32, int device) {
-    std::vector<Launch> out;
-    const int64_t per = kad::units_per_launch(unit_tiles, depth, f32);
-    for (int64_t u0 = 0; u0 < total; u0 += per) {
-        const int64_t cnt = std::min(per, total - u0);
-        out.push_back(Launch{u0, cnt, kad::launch_grid(cnt, grid_cap(device))});
-    }
-    return out;
+// sigma = `bandwidth`, or the median pairwise distance of x when it is 0, and c = log2(e) / sigma^2 as the kernels' float32
+static int resolve_sigma(const Packed& x, double bandwidth, int dtype, int device, hipStream_t st, KadWorkspace& ws, const char* who,
+                         double* sigma, float* c) {
+    *sigma = bandwidth;
+    if (!(*sigma > 0)) FAD_TRY(median_of_packed(x, dtype, device, st, ws, sigma));
+    if (!(*sigma > 0) || !std::isfinite(*sigma))
+        return set_error(FAD_ERR_INVALID, "%s: bandwidth %g (the median pairwise distance of the baseline when none is given) must be > 0"
+                         " -- are all baseline rows identical?", who, *sigma);
+    const double cd = 1.4426950408889634 / (*sigma * *sigma);
+    if (!(cd > 0) || !std::isfinite(cd) || !std::isfinite((float)cd) || (float)cd == 0.f)
+        return set_error(FAD_ERR_INVALID, "%s: bandwidth %g is outside the float32 range of the kernel", who, *sigma);
+    *c = (float)cd;
+    return FAD_OK;
 }
 
 static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
@@ -704,50 +691,16 @@ int fad_kad(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int
     Packed px, py;
     FAD_TRY(pack_set(0, x, n, ldx, d, dtype, on_device, st, ws, &px));
     FAD_TRY(pack_set(1, y, m, ldy, d, dtype, on_device, st, ws, &py));
-    double sigma = bandwidth;
-    if (!(sigma > 0)) FAD_TRY(median_of_packed(px, dtype, device, st, ws, &sigma));
-    if (!(sigma > 0) || !std::isfinite(sigma))
-        return set_error(FAD_ERR_INVALID, "fad_kad: bandwidth %g (the median pairwise distance of the baseline when none is given) must be > 0"
-                         " -- are all baseline rows identical?", sigma);
-    const double cd = 1.4426950408889634 / (sigma * sigma);
-    if (!(cd > 0) || !std::isfinite(cd) || !std::isfinite((float)cd) || (float)cd == 0.f)
-        return set_error(FAD_ERR_INVALID, "fad_kad: bandwidth %g is outside the float32 range of the kernel", sigma);
+    double sigma;
+    float c;
+    FAD_TRY(resolve_sigma(px, bandwidth, dtype, device, st, ws, "fad_kad", &sigma, &c));
 
     // passes: XX and YY over their triangles, XY over the rectangle with the larger set as the row operand
     const bool x_rows = n != m ? n > m : px.norm_sum >= py.norm_sum;
-    const Packed& ra = x_rows ? px : py;
-    const Packed& rb = x_rows ? py : px;
-    const int64_t depth = px.pitch / (int64_t)dtype_size(dtype);
-    struct PassDef { const Packed* a; const Packed* b; bool tri; int64_t total, tj; };
-    const PassDef defs[3] = {{&px, &px, true, kad::tri_tiles(kad::blocks(n)), kad::blocks(n)},
-                             {&py, &py, true, kad::tri_tiles(kad::blocks(m)), kad::blocks(m)},
-                             {&ra, &rb, false, kad::blocks(ra.n) * kad::blocks(rb.n), kad::blocks(rb.n)}};
-    std::vector<Launch> launches[3];
-    int64_t off[4] = {0, 0, 0, 0};
-    for (int q = 0; q < 3; ++q) {
-        launches[q] = plan(defs[q].total, depth, dtype == FAD_F32, false, device);
-        off[q + 1] = off[q];
-        for (const Launch& l : launches[q]) off[q + 1] += l.grid;
-    }
-    FAD_TRY(ws.slots.reserve((size_t)off[3] * sizeof(double)));
-    double* small = static_cast<double*>(ws.small.p);
-    int64_t* off_d = reinterpret_cast<int64_t*>(small + 8);
-    double* sums_d = small + 16;
-    FAD_HIP_TRY(hipMemcpyAsync(off_d, off, sizeof(off), hipMemcpyHostToDevice, st));
-    for (int q = 0; q < 3; ++q) {
-        PassArgs p{};
-        p.a = defs[q].a->img; p.b = defs[q].b->img; p.ha = defs[q].a->h; p.hb = defs[q].b->h; p.pitch = px.pitch;
-        p.n_a = defs[q].a->n; p.n_b = defs[q].b->n; p.tiles_j = defs[q].tj; p.tri = defs[q].tri; p.nchunks = px.nchunks;
-        p.c = (float)cd;
-        double* slots = static_cast<double*>(ws.slots.p) + off[q];
-        for (const Launch& l : launches[q]) {
-            p.u0 = l.u0; p.cnt = l.cnt; p.slots = slots;
-            FAD_TRY(launch_pass<MODE_SUM>(dtype, p, l.grid, st));
-            slots += l.grid;
-        }
-    }
-    kad_slots_sum_kernel<<<3, 256, 0, st>>>(static_cast<const double*>(ws.slots.p), off_d, sums_d);
-    FAD_HIP_TRY(hipGetLastError());
+    const PassArgs passes[3] = {pass_args(px, px, true, c), pass_args(py, py, true, c),
+                                pass_args(x_rows ? px : py, x_rows ? py : px, false, c)};
+    double* sums_d = static_cast<double*>(ws.small.p) + 16;
+    FAD_TRY(sum_passes(passes, dtype, device, st, ws, sums_d));
     double sums[3];
     FAD_HIP_TRY(hipMemcpyAsync(sums, sums_d, sizeof(sums), hipMemcpyDeviceToHost, st));
     FAD_HIP_TRY(hipStreamSynchronize(st));
@@ -792,41 +745,19 @@ int fad_kad_individual(const void* x, int64_t n, int64_t ldx, const void* rows, 
     // the baseline: sigma and Kxx exactly as fad_kad finds them (the same launches, slots and fixed-order sum)
     Packed px;
     FAD_TRY(pack_set(0, x, n, ldx, d, dtype, on_device, st, ws, &px));
-    double sigma = bandwidth;
-    if (!(sigma > 0)) FAD_TRY(median_of_packed(px, dtype, device, st, ws, &sigma));
-    if (!(sigma > 0) || !std::isfinite(sigma))
-        return set_error(FAD_ERR_INVALID, "fad_kad_individual: bandwidth %g (the median pairwise distance of the baseline when none is "
-                         "given) must be > 0 -- are all baseline rows identical?", sigma);
-    const double cd = 1.4426950408889634 / (sigma * sigma);
-    if (!(cd > 0) || !std::isfinite(cd) || !std::isfinite((float)cd) || (float)cd == 0.f)
-        return set_error(FAD_ERR_INVALID, "fad_kad_individual: bandwidth %g is outside the float32 range of the kernel", sigma);
-    const bool f32 = dtype == FAD_F32;
-    const int64_t depth = px.pitch / (int64_t)dtype_size(dtype), TI = kad::blocks(n);
-    {
-        const auto launches = plan(kad::tri_tiles(TI), depth, f32, false, device);
-        int64_t off[2] = {0, 0};
-        for (const Launch& l : launches) off[1] += l.grid;
-        FAD_TRY(ws.slots.reserve((size_t)off[1] * sizeof(double)));
-        PassArgs p{};
-        p.a = p.b = px.img; p.ha = p.hb = px.h; p.pitch = px.pitch; p.n_a = p.n_b = n; p.tiles_j = TI; p.tri = 1; p.nchunks = px.nchunks;
-        p.c = (float)cd;
-        double* slots = static_cast<double*>(ws.slots.p);
-        for (const Launch& l : launches) {
-            p.u0 = l.u0; p.cnt = l.cnt; p.slots = slots;
-            FAD_TRY(launch_pass<MODE_SUM>(dtype, p, l.grid, st));
-            slots += l.grid;
-        }
-        int64_t* off_d = reinterpret_cast<int64_t*>(static_cast<double*>(ws.small.p) + 8);
-        FAD_HIP_TRY(hipMemcpyAsync(off_d, off, sizeof(off), hipMemcpyHostToDevice, st));
-        kad_slots_sum_kernel<<<1, 256, 0, st>>>(static_cast<const double*>(ws.slots.p), off_d, static_cast<double*>(ws.small.p) + 16);
-        FAD_HIP_TRY(hipGetLastError());
-    }
+    double sigma;
+    float c;
+    FAD_TRY(resolve_sigma(px, bandwidth, dtype, device, st, ws, "fad_kad_individual", &sigma, &c));
+    const PassArgs xx[1] = {pass_args(px, px, true, c)};
+    double* sxx_d = static_cast<double*>(ws.small.p) + 16;
+    FAD_TRY(sum_passes(xx, dtype, device, st, ws, sxx_d));
 
     // the songs: cross pass (X x Y) and band pass (pairs inside each song), per-column slots, one reduction per song
     if (n_rows > 0 && n_songs > 0) {
         Packed py;
         FAD_TRY(pack_image(1, rows, n_rows, ldy, d, dtype, on_device, st, ws, &py));
-        const int64_t TJ = kad::blocks(n_rows), m_pad = TJ * kTile;
+        const bool f32 = dtype == FAD_F32;
+        const int64_t depth = px.pitch / (int64_t)dtype_size(dtype), TI = kad::blocks(n), TJ = kad::blocks(n_rows), m_pad = TJ * kTile;
         const int64_t rr = kad::cross_rows_per_unit(TI, TJ, kad::tiles_per_launch(depth, f32)), NR = kad::cross_ranges(TI, rr);
         std::vector<kad::Unit> bunits;
         std::vector<int64_t> bstart;
@@ -861,18 +792,18 @@ int fad_kad_individual(const void* x, int64_t n, int64_t ldx, const void* rows, 
         FAD_HIP_TRY(hipGetLastError());
 
         ColArgs p{};
-        p.b = py.img; p.hb = py.h; p.pitch = px.pitch; p.nchunks = px.nchunks; p.c = (float)cd;
+        p.b = py.img; p.hb = py.h; p.pitch = px.pitch; p.nchunks = px.nchunks; p.c = c;
         p.a = px.img; p.ha = px.h; p.TI = TI; p.TJ = TJ; p.rr = rr;
         p.slots = static_cast<double*>(ws.cross.p); p.slot_pitch = m_pad;
-        for (const Launch& l : plan_units(NR * TJ, rr, depth, f32, device)) {
+        for (const kad::Launch& l : kad::launches(NR * TJ, kad::units_per_launch(rr, depth, f32), grid_cap(device))) {
             p.u0 = l.u0; p.cnt = l.cnt;
-            FAD_TRY(launch_cols<false>(dtype, p, l.grid, st));
+            FAD_TRY(with_dtype(dtype, [&](auto dt) { kad_cols_kernel<dt, false><<<(unsigned)l.grid, kThreads, kLdsCols, st>>>(p); }));
         }
         p.a = py.img; p.ha = py.h; p.units = bunits_d; p.row_end = row_end_d;
         p.slots = static_cast<double*>(ws.band.p); p.slot_pitch = kTile;
-        for (const Launch& l : plan_units(U, kad::kBandPiece, depth, f32, device)) {
+        for (const kad::Launch& l : kad::launches(U, kad::units_per_launch(kad::kBandPiece, depth, f32), grid_cap(device))) {
             p.u0 = l.u0; p.cnt = l.cnt;
-            FAD_TRY(launch_cols<true>(dtype, p, l.grid, st));
+            FAD_TRY(with_dtype(dtype, [&](auto dt) { kad_cols_kernel<dt, true><<<(unsigned)l.grid, kThreads, kLdsCols, st>>>(p); }));
         }
         kad_song_reduce_kernel<<<(unsigned)n_songs, 256, 0, st>>>(static_cast<const double*>(ws.cross.p), NR, m_pad,
                                                                   static_cast<const double*>(ws.band.p), bstart_d, py.h, off_d, (double)n,
@@ -888,7 +819,7 @@ int fad_kad_individual(const void* x, int64_t n, int64_t ldx, const void* rows, 
         }
     }
     double sxx;
-    FAD_HIP_TRY(hipMemcpyAsync(&sxx, static_cast<double*>(ws.small.p) + 16, sizeof(double), hipMemcpyDeviceToHost, st));
+    FAD_HIP_TRY(hipMemcpyAsync(&sxx, sxx_d, sizeof(double), hipMemcpyDeviceToHost, st));
     FAD_HIP_TRY(hipStreamSynchronize(st));
 
     base->kxx_mean = 2.0 * sxx / ((double)n * (double)(n - 1));

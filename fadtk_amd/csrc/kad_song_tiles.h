@@ -54,8 +54,8 @@ KAD_HD inline bool band_pair_counted(int64_t I, int64_t J, int r, int c, int64_t
     return j < end_i && (I < J || c > r);
 }
 
-// host only: the song that holds row `row` (offsets non-decreasing, offsets[0] = 0 <= row < offsets[n_songs]): the last s with offsets[s] <= row.
-inline int64_t song_of_row(const int64_t* offsets, int64_t n_songs, int64_t row) {
+// the song that holds row `row` (offsets non-decreasing, offsets[0] = 0 <= row < offsets[n_songs]): the last s with offsets[s] <= row
+KAD_HD inline int64_t song_of_row(const int64_t* offsets, int64_t n_songs, int64_t row) {
     int64_t lo = 0, hi = n_songs;                 // offsets[lo] <= row < offsets[hi]
     while (hi - lo > 1) {
         const int64_t mid = lo + (hi - lo) / 2;

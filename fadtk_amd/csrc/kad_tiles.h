@@ -13,6 +13,7 @@
 
 #include <cmath>
 #include <cstdint>
+#include <vector>
 
 #if defined(__HIPCC__)
 #define KAD_HD __host__ __device__
@@ -60,6 +61,17 @@ KAD_HD inline int64_t slot_tile(int64_t L, int64_t cnt, bool* live) {
 KAD_HD inline int64_t launch_grid(int64_t cnt, int64_t cap) {
     const int64_t s = launch_slots(cnt);
     return s < cap ? s : cap;
+}
+
+// host only: the launches of a pass of `total` tiles (or work units, kad_song_tiles.h), `per_launch` at most each, and their grids
+struct Launch { int64_t u0, cnt, grid; };
+inline std::vector<Launch> launches(int64_t total, int64_t per_launch, int64_t cap) {
+    std::vector<Launch> out;
+    for (int64_t u0 = 0; u0 < total; u0 += per_launch) {
+        const int64_t cnt = per_launch < total - u0 ? per_launch : total - u0;
+        out.push_back(Launch{u0, cnt, launch_grid(cnt, cap)});
+    }
+    return out;
 }
 
 // Tiles per launch.  A tile costs its MFMA k loop -- `depth` units, 16x that for the float32 MFMA (a sixteenth of the 16-bit rate) --

@@ -640,6 +640,25 @@ def _kad_rows(x, what: str):
     return K.rows_view(x)
 
 
+def _kad_pair(x, y, what: str, device: int):
+    """-> (_kad_rows(x), _kad_rows(y)); a numpy set next to a torch CUDA one (or a CPU tensor next to a CUDA one) is copied to the device."""
+    if K._is_torch(x) != K._is_torch(y) or (K._is_torch(x) and x.is_cuda != y.is_cuda):
+        import torch
+        dev = torch.device("cuda", device)
+        x = x if K._is_torch(x) else torch.from_numpy(np.ascontiguousarray(x))
+        y = y if K._is_torch(y) else torch.from_numpy(np.ascontiguousarray(y))
+        x, y = x.to(dev), y.to(dev)
+    return _kad_rows(x, "x"), _kad_rows(y, what)
+
+
+def _kad_bandwidth(bandwidth: Optional[float]) -> float:
+    """-> the C ABI's bandwidth argument: 0 for None (the median), else a value > 0."""
+    bw = 0.0 if bandwidth is None else float(bandwidth)
+    if bandwidth is not None and not bw > 0:
+        raise ValueError(f"KAD: bandwidth must be > 0, got {bandwidth}")
+    return bw
+
+
 def kad_median_distance(x, device: int = 0) -> float:
     """``fad_kad_median_distance``: np.median(scipy.spatial.distance.pdist(x)) of one set of rows (numpy on the host, or a torch CUDA
     tensor used in place on torch's current stream)."""
@@ -656,22 +675,13 @@ def kad(x, y, bandwidth: Optional[float] = None, device: int = 0) -> dict:
     (mmd2, kxx_mean, kyy_mean, kxy_mean, bandwidth, n, m).  ``bandwidth=None``: the median pairwise distance of x.
     Both sets are numpy arrays or both torch CUDA tensors of one dtype (float16 / bfloat16 / float32)."""
     lib = K.load_library()
-    if K._is_torch(x) != K._is_torch(y) or (K._is_torch(x) and x.is_cuda != y.is_cuda):
-        import torch
-        dev = torch.device("cuda", device)
-        x = x if K._is_torch(x) else torch.from_numpy(np.ascontiguousarray(x))
-        y = y if K._is_torch(y) else torch.from_numpy(np.ascontiguousarray(y))
-        x, y = x.to(dev), y.to(dev)
-    px, n, d, ldx, cx, dev_x, kx = _kad_rows(x, "x")
-    py, m, dy, ldy, cy, dev_y, ky = _kad_rows(y, "y")
+    (px, n, d, ldx, cx, dev_x, kx), (py, m, dy, ldy, cy, dev_y, ky) = _kad_pair(x, y, "y", device)
     if d != dy:
         raise ValueError(f"KAD: x has D = {d}, y has D = {dy}")
     if cx != cy:
         raise ValueError("KAD: x and y must have the same dtype")
     res = K.FadKadResult()
-    bw = 0.0 if bandwidth is None else float(bandwidth)
-    if bandwidth is not None and not bw > 0:
-        raise ValueError(f"KAD: bandwidth must be > 0, got {bandwidth}")
+    bw = _kad_bandwidth(bandwidth)
     K.check(lib.fad_kad(px, n, ldx, py, m, ldy, d, cx, dev_x, bw, C.byref(res), int(device), K.current_stream_ptr(device)), "fad_kad")
     return res.as_dict()
 
@@ -682,14 +692,7 @@ def kad_individual(x, rows, offsets: Sequence[int], bandwidth: Optional[float] =
     ``status`` [S] (NaN where status is FAD_ERR_TOO_FEW_ROWS or FAD_ERR_NOT_FINITE), plus ``kxx_mean``, ``bandwidth`` and ``n``.
     x and rows are both numpy arrays or both torch CUDA tensors of one dtype (float16 / bfloat16 / float32)."""
     lib = K.load_library()
-    if K._is_torch(x) != K._is_torch(rows) or (K._is_torch(x) and x.is_cuda != rows.is_cuda):
-        import torch
-        dev = torch.device("cuda", device)
-        x = x if K._is_torch(x) else torch.from_numpy(np.ascontiguousarray(x))
-        rows = rows if K._is_torch(rows) else torch.from_numpy(np.ascontiguousarray(rows))
-        x, rows = x.to(dev), rows.to(dev)
-    px, n, d, ldx, cx, dev_x, kx = _kad_rows(x, "x")
-    py, m, dy, ldy, cy, dev_y, ky = _kad_rows(rows, "rows")
+    (px, n, d, ldx, cx, dev_x, kx), (py, m, dy, ldy, cy, dev_y, ky) = _kad_pair(x, rows, "rows", device)
     if m > 0 and d != dy:
         raise ValueError(f"KAD: x has D = {d}, the songs have D = {dy}")
     if m > 0 and cx != cy:
@@ -698,9 +701,7 @@ def kad_individual(x, rows, offsets: Sequence[int], bandwidth: Optional[float] =
     if off.ndim != 1 or off.shape[0] < 1:
         raise ValueError("KAD: offsets must be a 1-D sequence of S + 1 row indices")
     S = off.shape[0] - 1
-    bw = 0.0 if bandwidth is None else float(bandwidth)
-    if bandwidth is not None and not bw > 0:
-        raise ValueError(f"KAD: bandwidth must be > 0, got {bandwidth}")
+    bw = _kad_bandwidth(bandwidth)
     out = {k: np.full(S, np.nan) for k in ("mmd2", "kyy_mean", "kxy_mean")}
     out["status"] = np.zeros(S, dtype=np.int32)
     res = K.FadKadResult()

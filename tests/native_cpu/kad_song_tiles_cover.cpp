@@ -14,12 +14,12 @@ using namespace fad::kad;
 static int fails = 0;
 #define CHECK(c, ...) do { if (!(c)) { if (fails++ < 20) { printf("FAIL %s:%d: ", __FILE__, __LINE__); printf(__VA_ARGS__); printf("\n"); } } } while (0)
 
-// every unit a pass's launches hand out, as the workgroups of each launch meet them; `tiles(u)` is a unit's tile count
+// every unit a pass's launches (the host's launch cut) hand out, as the workgroups of each launch meet them; `tiles(u)` is a unit's
+// tile count
 template <typename T, typename F>
 static void walk_units(int64_t total, int64_t per_launch, int64_t cap, int64_t tile_cap, T&& tiles, F&& take) {
-    for (int64_t u0 = 0; u0 < total; u0 += per_launch) {
-        const int64_t cnt = per_launch < total - u0 ? per_launch : total - u0;
-        const int64_t G = launch_grid(cnt, cap);
+    for (const Launch& l : launches(total, per_launch, cap)) {
+        const int64_t u0 = l.u0, cnt = l.cnt, G = l.grid;
         CHECK(G % kXcds == 0 && G >= kXcds && G <= launch_slots(cnt), "grid %lld for %lld units", (long long)G, (long long)cnt);
         int64_t launch_tiles = 0;
         for (int64_t w = 0; w < G; ++w)

@@ -13,12 +13,11 @@ using namespace fad::kad;
 static int fails = 0;
 #define CHECK(c, ...) do { if (!(c)) { if (fails++ < 20) { printf("FAIL %s:%d: ", __FILE__, __LINE__); printf(__VA_ARGS__); printf("\n"); } } } while (0)
 
-// every (I, J) a pass's launches hand out, in the order the workgroups of each launch would meet them
+// every (I, J) a pass's launches (the host's launch cut) hand out, in the order the workgroups of each launch would meet them
 template <typename F>
 static void walk(int64_t total, int64_t per_launch, int64_t cap, F&& take) {
-    for (int64_t u0 = 0; u0 < total; u0 += per_launch) {
-        const int64_t cnt = per_launch < total - u0 ? per_launch : total - u0;
-        const int64_t G = launch_grid(cnt, cap);
+    for (const Launch& l : launches(total, per_launch, cap)) {
+        const int64_t u0 = l.u0, cnt = l.cnt, G = l.grid;
         CHECK(G % kXcds == 0 && G >= kXcds && G <= launch_slots(cnt), "grid %lld for %lld tiles", (long long)G, (long long)cnt);
         std::vector<int64_t> lo(kXcds, -1), hi(kXcds, -1);
         for (int64_t w = 0; w < G; ++w)
