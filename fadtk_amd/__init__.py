@@ -21,6 +21,9 @@ def __getattr__(name):
     if name in ("KernelAudioDistance", "calc_kernel_audio_distance", "calc_kernel_audio_distance_individual"):      # lazy: `python -m fadtk_amd.kad` runs the module itself
         from . import kad
         return getattr(kad, name)
+    if name in ("PrecisionRecall", "calc_precision_recall_density_coverage"):      # lazy, as KAD's
+        from . import prdc
+        return getattr(prdc, name)
     if name == "cache_embedding_files":
         from .fad_batch import cache_embedding_files
         return cache_embedding_files

@@ -54,6 +54,18 @@ class FadKadResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class FadPrdcResult(C.Structure):
+    _fields_ = [("precision", C.c_double), ("recall", C.c_double), ("density", C.c_double), ("coverage", C.c_double),
+                ("n", C.c_int64), ("m", C.c_int64), ("k", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class FadPrdcDetail(C.Structure):
+    _fields_ = [("radius2_x", C.c_void_p), ("radius2_y", C.c_void_p), ("balls_y", C.c_void_p), ("flags_x", C.c_void_p)]
+
+
 _P = C.c_void_p
 _I64 = C.c_int64
 # name -> (restype, argtypes)     -- one entry per declaration in include/fad_hip.h
@@ -111,6 +123,8 @@ SIGNATURES = {
                           C.c_int, _P]),
     "fad_kad_individual": (C.c_int, [_P, _I64, _I64, _P, _I64, _I64, C.POINTER(_I64), _I64, _I64, C.c_int, C.c_int, C.c_double,
                                      C.POINTER(FadKadResult), _P, _P, _P, _P, C.c_int, _P]),
+    "fad_prdc": (C.c_int, [_P, _I64, _I64, _P, _I64, _I64, _I64, C.c_int, C.c_int, C.c_int, C.POINTER(FadPrdcResult),
+                           C.POINTER(FadPrdcDetail), C.c_int, _P]),
 }
 
 _lib = None

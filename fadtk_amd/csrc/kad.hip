@@ -1,5 +1,6 @@
 // Kernel Audio Distance: the unbiased Gaussian-kernel MMD^2 between two sets of embedding rows, and the median pairwise distance
-// of one set (the default bandwidth).  DESIGN.md 4.6.
+// of one set (the default bandwidth).  DESIGN.md 4.6.  Per-song KAD (4.7) and the k-NN precision / recall / density / coverage (4.8)
+// run on the same main loop.
 //
 // Every pass is one GEMM-shaped walk over 128 x 128 tiles of a pair space (kad_tiles.h) whose n x m matrix is never stored:
 //   - pack:   each set is copied once into a zero-padded [n_pad x dp] image of its own dtype (dp: D rounded up to 128 bytes, n_pad:
@@ -463,13 +464,254 @@ __global__ void __launch_bounds__(256) kad_song_reduce_kernel(const double* __re
     }
 }
 
+// ---------------------------------------------------------------------------------- precision, recall, density, coverage
+// fad_prdc's passes: tile_mfma with two more epilogues, both on d^2 = max(-2 S', 0) as the median's histogram pass forms it.
+//   radius: X x X (and Y x Y) over the full rectangle, per-column top-k.  A lane keeps the k smallest d^2 of each of its two columns in
+//           registers (topk_insert); self is excluded by index on the diagonal tiles; padding rows give d^2 = +inf and never enter.  At
+//           a unit's end the four lists of a column (two lane halves, two wm waves) merge into one list of k floats per (R, column)
+//           slot; prdc_radius_reduce_kernel merges a column's NR slots into r^2.
+//   cross:  X rows x Y columns, P1 = d^2 < r_X^2(i) (rows' radii staged in LDS by tile_mfma's row_lds hook) and P2 = d^2 < r_Y^2(j)
+//           (the lane's column radii in registers).  Column counts of P1 per (R, column) slot, as kad_cols_kernel's sums; per row the
+//           OR over columns of P2 (bit 0) and P1 (bit 1) by one ballot per accumulator element and integer atomics.
+// Integers and float32 radii only: the same bits on every run.
+constexpr int kMaxK = 16;
+
+struct PrdcArgs {
+    const char* a; const char* b;              // row operand, column operand (the same set in a radius pass)
+    const float* ha; const float* hb;
+    int64_t pitch;
+    int nchunks, k;
+    int64_t u0, cnt;                           // the launch's units [u0, u0 + cnt)
+    int64_t TI, TJ, rr;                        // the unit map (kad::cross_unit)
+    float* lists; int64_t list_pitch;          // radius: lists[(R * list_pitch + j) * k + q]
+    const float* ra; const float* rb;          // cross: r^2 of the rows (0 on padding rows), of the columns
+    int* counts; int64_t count_pitch;          // cross: counts[R * count_pitch + j]
+    int* flags;                                // cross: per row of `a`, bit 0 recalled, bit 1 covered
+};
+
+// v into a lane's list t of the k smallest values seen (descending: t[0] is the k-th smallest; t[k .. 15] stay -inf):
+// t[q] <- med3(t[q + 1], t[q], v) drops t[0] and puts v in its place in order; a v >= t[0] leaves the list as it is.  Fixed register
+// indices, no scratch.
+__device__ __forceinline__ void topk_insert(float (&t)[kMaxK], float v) {
+#pragma unroll
+    for (int q = 0; q < kMaxK - 1; ++q) t[q] = __builtin_amdgcn_fmed3f(t[q + 1], t[q], v);
+    t[kMaxK - 1] = fminf(t[kMaxK - 1], v);
+}
+
+__device__ __forceinline__ void topk_init(float (&t)[kMaxK], int k) {
+#pragma unroll
+    for (int q = 0; q < kMaxK; ++q) t[q] = q < k ? INFINITY : -INFINITY;
+}
+
+// the wave's 64 rows of a tile into the lane's two column lists; DIAG: a tile I == J, where the pair of a row with itself is skipped
+template <bool DIAG>
+__device__ __forceinline__ void topk_tile(const f32x16 (&acc)[2][2], int rbase, int cbase, int lane, float (&t)[2][kMaxK]) {
+    int lrow = rbase + 4 * (lane >> 5), lcol = cbase + (lane & 31);
+    if (DIAG) asm volatile("" : "+v"(lrow), "+v"(lcol));         // per tile, not hoisted out of the tile loop as lane masks (tile_sum)
+#pragma unroll
+    for (int bj = 0; bj < 2; ++bj)
+#pragma unroll
+        for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+            for (int g = 0; g < 16; ++g) {
+                float d2 = fmaxf(-2.f * acc[bi][bj][g], 0.f);
+                if (DIAG) d2 = lcol + bj * 32 == lrow + bi * 32 + (g & 3) + 8 * (g >> 2) ? INFINITY : d2;
+                if (__ballot(d2 < t[bj][0])) topk_insert(t[bj], d2);                   // wave-uniform skip
+            }
+}
+
+template <int DT>
+__global__ void __launch_bounds__(kThreads, 2) prdc_radius_kernel(PrdcArgs p) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    float* lx = reinterpret_cast<float*>(lds + 2 * kOpBytes + 2 * kTile * 4);       // the wm = 1 waves' lists of a unit [128][kMaxK]
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
+    const int rbase = wm * 64, cbase = wn * 64;
+    const int64_t G = gridDim.x, nslots = kad::launch_slots(p.cnt);
+
+    for (int64_t L = blockIdx.x; L < nslots; L += G) {
+        bool live;
+        const int64_t v = kad::slot_tile(L, p.cnt, &live);
+        if (!live) continue;                                                          // uniform over the workgroup
+        const int64_t u = p.u0 + v;
+        const kad::Unit un = kad::cross_unit(u, p.TI, p.TJ, p.rr);
+        float t[2][kMaxK];
+        topk_init(t[0], p.k);
+        topk_init(t[1], p.k);
+
+        for (int64_t I = un.I0; I < un.I1; ++I) {
+            f32x16 acc[2][2];
+            tile_mfma<DT>(p.a, p.b, p.ha, p.hb, p.pitch, p.nchunks, I, un.J, lds, [](int) {}, acc);
+            if (I == un.J) topk_tile<true>(acc, rbase, cbase, lane, t);
+            else topk_tile<false>(acc, rbase, cbase, lane, t);
+        }
+
+        // a column: the two lane halves, then the wm = 0 and wm = 1 waves
+#pragma unroll
+        for (int bj = 0; bj < 2; ++bj) {
+            float o[kMaxK];
+#pragma unroll
+            for (int q = 0; q < kMaxK; ++q) o[q] = __shfl_xor(t[bj][q], 32, 64);
+#pragma unroll
+            for (int q = 0; q < kMaxK; ++q) topk_insert(t[bj], q < p.k ? o[q] : INFINITY);
+        }
+        if (wm == 1 && lane < 32) {
+#pragma unroll
+            for (int bj = 0; bj < 2; ++bj)
+#pragma unroll
+                for (int q = 0; q < kMaxK; ++q) lx[(cbase + bj * 32 + lane) * kMaxK + q] = t[bj][q];
+        }
+        __syncthreads();
+        if (wm == 0 && lane < 32) {
+#pragma unroll
+            for (int bj = 0; bj < 2; ++bj) {
+                const int c = cbase + bj * 32 + lane;
+#pragma unroll
+                for (int q = 0; q < kMaxK; ++q) topk_insert(t[bj], q < p.k ? lx[c * kMaxK + q] : INFINITY);
+                float* out = p.lists + ((u / p.TJ) * p.list_pitch + un.J * kTile + c) * p.k;
+#pragma unroll
+                for (int q = 0; q < kMaxK; ++q)
+                    if (q < p.k) out[q] = t[bj][q];
+            }
+        }
+    }
+}
+
+constexpr size_t kLdsRadius = 2 * kOpBytes + 2 * kTile * 4 + kTile * kMaxK * sizeof(float);
+
+template <int DT>
+__global__ void __launch_bounds__(kThreads, 2) prdc_cross_kernel(PrdcArgs p) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    float* lrad = reinterpret_cast<float*>(lds + 2 * kOpBytes + 2 * kTile * 4);     // r_X^2 of the tile's rows
+    int* lcnt = reinterpret_cast<int*>(lds + 2 * kOpBytes + 3 * kTile * 4);         // the wm = 1 waves' column counts of a unit
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
+    const int rbase = wm * 64, cbase = wn * 64;
+    const int64_t G = gridDim.x, nslots = kad::launch_slots(p.cnt);
+
+    for (int64_t L = blockIdx.x; L < nslots; L += G) {
+        bool live;
+        const int64_t v = kad::slot_tile(L, p.cnt, &live);
+        if (!live) continue;                                                          // uniform over the workgroup
+        const int64_t u = p.u0 + v;
+        const kad::Unit un = kad::cross_unit(u, p.TI, p.TJ, p.rr);
+        float ry[2];
+        int cnt[2] = {0, 0};
+#pragma unroll
+        for (int bj = 0; bj < 2; ++bj) ry[bj] = p.rb[un.J * kTile + cbase + bj * 32 + (lane & 31)];
+
+        for (int64_t I = un.I0; I < un.I1; ++I) {
+            f32x16 acc[2][2];
+            tile_mfma<DT>(p.a, p.b, p.ha, p.hb, p.pitch, p.nchunks, I, un.J, lds, [&](int r) { lrad[r] = p.ra[I * kTile + r]; }, acc);
+
+            int lrow = rbase + 4 * (lane >> 5);
+            asm volatile("" : "+v"(lrow));                    // per tile, not hoisted out of the tile loop (tile_sum)
+            // bit rl of the wave's rows rbase + rl: some column of the wave passes P1 (cov) / P2 (rec).  In the 32 x 32 layout the 32
+            // columns of a row sit in one lane half, so a ballot's low and high words are the rows of lane halves 0 and 1.
+            uint64_t cov = 0, rec = 0;
+#pragma unroll
+            for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const f32x4 rx = *reinterpret_cast<const f32x4*>(lrad + lrow + bi * 32 + 8 * q);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int g = 4 * q + e, rl = bi * 32 + e + 8 * q;
+                        uint64_t b1 = 0, b2 = 0;
+#pragma unroll
+                        for (int bj = 0; bj < 2; ++bj) {
+                            const float d2 = fmaxf(-2.f * acc[bi][bj][g], 0.f);
+                            const bool p1 = d2 < rx[e], p2 = d2 < ry[bj];
+                            cnt[bj] += p1;
+                            b1 |= __ballot(p1);
+                            b2 |= __ballot(p2);
+                        }
+                        cov |= (uint64_t)((uint32_t)b1 != 0) << rl | (uint64_t)((b1 >> 32) != 0) << (rl + 4);
+                        rec |= (uint64_t)((uint32_t)b2 != 0) << rl | (uint64_t)((b2 >> 32) != 0) << (rl + 4);
+                    }
+                }
+            if (cov | rec) {                                                          // uniform; lane l takes row rbase + l
+                const int f = (int)((rec >> lane) & 1) | (int)((cov >> lane) & 1) << 1;
+                if (f) atomicOr(&p.flags[I * kTile + rbase + lane], f);
+            }
+        }
+
+#pragma unroll
+        for (int bj = 0; bj < 2; ++bj) cnt[bj] += __shfl_xor(cnt[bj], 32, 64);
+        if (wm == 1 && lane < 32) {
+#pragma unroll
+            for (int bj = 0; bj < 2; ++bj) lcnt[cbase + bj * 32 + lane] = cnt[bj];
+        }
+        __syncthreads();
+        if (wm == 0 && lane < 32) {
+            int* slot = p.counts + (u / p.TJ) * p.count_pitch + un.J * kTile;
+#pragma unroll
+            for (int bj = 0; bj < 2; ++bj) slot[cbase + bj * 32 + lane] = cnt[bj] + lcnt[cbase + bj * 32 + lane];
+        }
+    }
+}
+
+constexpr size_t kLdsCross = 2 * kOpBytes + 4 * kTile * 4;
+
+// r2[j] = the k-th smallest of the NR lists of column j (j < n), 0 on the padding columns
+__global__ void __launch_bounds__(256) prdc_radius_reduce_kernel(const float* __restrict__ lists, int64_t nr, int64_t pitch, int k, int64_t n,
+                                                                 float* __restrict__ r2) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= pitch) return;
+    if (j >= n) { r2[j] = 0.f; return; }
+    float t[kMaxK];
+    topk_init(t, k);
+    for (int64_t R = 0; R < nr; ++R) {
+        const float* l = lists + (R * pitch + j) * k;
+#pragma unroll
+        for (int q = 0; q < kMaxK; ++q) topk_insert(t, q < k ? l[q] : INFINITY);
+    }
+    r2[j] = t[0];
+}
+
+// balls[j] = column j's count slots summed (j < m)
+__global__ void __launch_bounds__(256) prdc_balls_kernel(const int* __restrict__ counts, int64_t nr, int64_t pitch, int64_t m,
+                                                         int* __restrict__ balls) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= m) return;
+    int s = 0;
+    for (int64_t R = 0; R < nr; ++R) s += counts[R * pitch + j];
+    balls[j] = s;
+}
+
+// one workgroup: [0] columns with balls > 0, [1] the sum of balls, [2] rows with bit 0 (recalled), [3] rows with bit 1 (covered)
+__global__ void __launch_bounds__(1024) prdc_stats_kernel(const int* __restrict__ balls, int64_t m, const int* __restrict__ flags, int64_t n,
+                                                          unsigned long long* __restrict__ out) {
+    __shared__ unsigned long long red[4][1024];
+    unsigned long long s[4] = {0, 0, 0, 0};
+    for (int64_t j = threadIdx.x; j < m; j += 1024) {
+        const int b = balls[j];
+        s[0] += b > 0;
+        s[1] += (unsigned long long)b;
+    }
+    for (int64_t i = threadIdx.x; i < n; i += 1024) {
+        const int f = flags[i];
+        s[2] += f & 1;
+        s[3] += (f >> 1) & 1;
+    }
+    for (int q = 0; q < 4; ++q) red[q][threadIdx.x] = s[q];
+    __syncthreads();
+    for (int w = 512; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w)
+            for (int q = 0; q < 4; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x < 4) out[threadIdx.x] = red[threadIdx.x][0];
+}
+
 // ------------------------------------------------------------------------------------------------------------------ host side
 struct KadWorkspace {
     DevBuf raw[2], img[2], h[2], slots, small;       // small: info, pass offsets, pass sums, histograms
     DevBuf cross, band, songs;                       // fad_kad_individual: column slots of the two passes, song tables and outputs
+    DevBuf lists, prdc;                              // fad_prdc: the radius passes' top-k slots; radii, counts, flags and totals
     void release_all() {
         for (int i = 0; i < 2; ++i) { raw[i].release(); img[i].release(); h[i].release(); }
-        slots.release(); small.release(); cross.release(); band.release(); songs.release();
+        slots.release(); small.release(); cross.release(); band.release(); songs.release(); lists.release(); prdc.release();
     }
 };
 
@@ -653,6 +895,33 @@ static int resolve_sigma(const Packed& x, double bandwidth, int dtype, int devic
 
 static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
+// A PRDC pass over the rectangle of `rows` x `cols` (fad_prdc): units of rr row blocks, NR row ranges, per-launch units
+struct PrdcPlan { int64_t TI, TJ, rr, NR, per_launch; };
+static PrdcPlan prdc_plan(const Packed& rows, const Packed& cols, int dtype, int64_t epilogue) {
+    PrdcPlan q;
+    const int64_t per = kad::tiles_per_launch_for(rows.pitch / (int64_t)dtype_size(dtype), dtype == FAD_F32, epilogue);
+    q.TI = kad::blocks(rows.n); q.TJ = kad::blocks(cols.n);
+    q.rr = kad::prdc_rows_per_unit(q.TI, q.TJ, per);
+    q.NR = kad::cross_ranges(q.TI, q.rr);
+    q.per_launch = kad::prdc_units_per_launch(q.rr, per);
+    return q;
+}
+
+// r2[j] (TJ * 128 entries, 0 on the padding rows) = the k-th smallest d^2 from row j of x to the other rows of x
+static int radius_pass(const Packed& x, int k, int dtype, int device, hipStream_t st, float* lists, float* r2) {
+    const PrdcPlan q = prdc_plan(x, x, dtype, kad::kTopkEpilogue);
+    PrdcArgs p{};
+    p.a = p.b = x.img; p.ha = p.hb = x.h; p.pitch = x.pitch; p.nchunks = x.nchunks; p.k = k;
+    p.TI = q.TI; p.TJ = q.TJ; p.rr = q.rr; p.lists = lists; p.list_pitch = q.TJ * kTile;
+    for (const kad::Launch& l : kad::launches(q.NR * q.TJ, q.per_launch, grid_cap(device))) {
+        p.u0 = l.u0; p.cnt = l.cnt;
+        FAD_TRY(with_dtype(dtype, [&](auto dt) { prdc_radius_kernel<dt><<<(unsigned)l.grid, kThreads, kLdsRadius, st>>>(p); }));
+    }
+    prdc_radius_reduce_kernel<<<(unsigned)cdiv(p.list_pitch, 256), 256, 0, st>>>(lists, q.NR, p.list_pitch, k, x.n, r2);
+    FAD_HIP_TRY(hipGetLastError());
+    return FAD_OK;
+}
+
 }  // namespace
 
 }  // namespace fad
@@ -829,6 +1098,89 @@ int fad_kad_individual(const void* x, int64_t n, int64_t ldx, const void* rows, 
     base->m = n_rows;
     for (int64_t s = 0; s < n_songs; ++s)
         out_mmd2[s] = out_status[s] == FAD_OK ? base->kxx_mean + out_kyy_mean[s] - 2.0 * out_kxy_mean[s] : NAN;
+    return FAD_OK;
+}
+
+int fad_prdc(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype, int on_device, int k,
+             fad_prdc_result_t* out, fad_prdc_detail_t* detail, int device, void* stream) {
+    using namespace fad;
+    if (!out) return set_error(FAD_ERR_INVALID, "fad_prdc: NULL output");
+    if (k < 1 || k > kMaxK) return set_error(FAD_ERR_INVALID, "fad_prdc: k = %d is outside 1 .. %d", k, kMaxK);
+    if (!x || !y) return set_error(FAD_ERR_INVALID, "fad_prdc: NULL rows");
+    // dtype, d and ld as fad_kad checks them; the row counts are checked against k below
+    FAD_TRY(check_rows(x, std::max<int64_t>(n, 2), ldx, d, dtype, "fad_prdc (x)"));
+    FAD_TRY(check_rows(y, std::max<int64_t>(m, 2), ldy, d, dtype, "fad_prdc (y)"));
+    if (n <= k || m <= k)
+        return set_error(FAD_ERR_TOO_FEW_ROWS, "fad_prdc: k = %d needs more than k rows per set, got %lld and %lld", k, (long long)n,
+                         (long long)m);
+    if (n > INT32_MAX - kTile || m > INT32_MAX - kTile)
+        return set_error(FAD_ERR_INVALID, "fad_prdc: %lld and %lld rows (at most %d per set)", (long long)n, (long long)m, INT32_MAX - kTile);
+    FAD_TRY(check_device(device));
+    DeviceGuard g(device);
+    if (!g.ok) return set_error(FAD_ERR_HIP, "hipSetDevice(%d) failed", device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    KadWorkspace& ws = workspace(device);
+
+    Packed px, py;
+    FAD_TRY(pack_set(0, x, n, ldx, d, dtype, on_device, st, ws, &px));
+    FAD_TRY(pack_set(1, y, m, ldy, d, dtype, on_device, st, ws, &py));
+    const PrdcPlan qx = prdc_plan(px, px, dtype, kad::kTopkEpilogue), qy = prdc_plan(py, py, dtype, kad::kTopkEpilogue);
+    const PrdcPlan qc = prdc_plan(px, py, dtype, kad::kFlagEpilogue);
+    const int64_t n_pad = qx.TJ * kTile, m_pad = qy.TJ * kTile;
+
+    // radii x | radii y | flags | balls | totals | count slots
+    size_t at[7];
+    at[0] = 0;
+    at[1] = at[0] + align256((size_t)n_pad * sizeof(float));
+    at[2] = at[1] + align256((size_t)m_pad * sizeof(float));
+    at[3] = at[2] + align256((size_t)n_pad * sizeof(int));
+    at[4] = at[3] + align256((size_t)m_pad * sizeof(int));
+    at[5] = at[4] + align256(4 * sizeof(unsigned long long));
+    at[6] = at[5] + align256((size_t)(qc.NR * m_pad) * sizeof(int));
+    FAD_TRY(ws.prdc.reserve(at[6]));
+    FAD_TRY(ws.lists.reserve((size_t)std::max(qx.NR * n_pad, qy.NR * m_pad) * (size_t)k * sizeof(float)));
+    char* pb = static_cast<char*>(ws.prdc.p);
+    float* r2x = reinterpret_cast<float*>(pb + at[0]);
+    float* r2y = reinterpret_cast<float*>(pb + at[1]);
+    int* flags = reinterpret_cast<int*>(pb + at[2]);
+    int* balls = reinterpret_cast<int*>(pb + at[3]);
+    unsigned long long* totals = reinterpret_cast<unsigned long long*>(pb + at[4]);
+    float* lists = static_cast<float*>(ws.lists.p);
+
+    FAD_TRY(radius_pass(px, k, dtype, device, st, lists, r2x));
+    FAD_TRY(radius_pass(py, k, dtype, device, st, lists, r2y));
+    FAD_HIP_TRY(hipMemsetAsync(flags, 0, (size_t)n_pad * sizeof(int), st));
+
+    PrdcArgs p{};
+    p.a = px.img; p.ha = px.h; p.b = py.img; p.hb = py.h; p.pitch = px.pitch; p.nchunks = px.nchunks; p.k = k;
+    p.TI = qc.TI; p.TJ = qc.TJ; p.rr = qc.rr; p.ra = r2x; p.rb = r2y;
+    p.counts = reinterpret_cast<int*>(pb + at[5]); p.count_pitch = m_pad; p.flags = flags;
+    for (const kad::Launch& l : kad::launches(qc.NR * qc.TJ, qc.per_launch, grid_cap(device))) {
+        p.u0 = l.u0; p.cnt = l.cnt;
+        FAD_TRY(with_dtype(dtype, [&](auto dt) { prdc_cross_kernel<dt><<<(unsigned)l.grid, kThreads, kLdsCross, st>>>(p); }));
+    }
+    prdc_balls_kernel<<<(unsigned)cdiv(m, 256), 256, 0, st>>>(p.counts, qc.NR, m_pad, m, balls);
+    FAD_HIP_TRY(hipGetLastError());
+    prdc_stats_kernel<<<1, 1024, 0, st>>>(balls, m, flags, n, totals);
+    FAD_HIP_TRY(hipGetLastError());
+
+    unsigned long long tot[4];
+    FAD_HIP_TRY(hipMemcpyAsync(tot, totals, sizeof(tot), hipMemcpyDeviceToHost, st));
+    if (detail) {
+        if (detail->radius2_x) FAD_HIP_TRY(hipMemcpyAsync(detail->radius2_x, r2x, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, st));
+        if (detail->radius2_y) FAD_HIP_TRY(hipMemcpyAsync(detail->radius2_y, r2y, (size_t)m * sizeof(float), hipMemcpyDeviceToHost, st));
+        if (detail->balls_y) FAD_HIP_TRY(hipMemcpyAsync(detail->balls_y, balls, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, st));
+        if (detail->flags_x) FAD_HIP_TRY(hipMemcpyAsync(detail->flags_x, flags, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
+    }
+    FAD_HIP_TRY(hipStreamSynchronize(st));
+
+    out->precision = (double)tot[0] / (double)m;
+    out->density = (double)tot[1] / ((double)k * (double)m);
+    out->recall = (double)tot[2] / (double)n;
+    out->coverage = (double)tot[3] / (double)n;
+    out->n = n;
+    out->m = m;
+    out->k = k;
     return FAD_OK;
 }
 

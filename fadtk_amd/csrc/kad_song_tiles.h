@@ -46,6 +46,19 @@ KAD_HD inline int64_t units_per_launch(int64_t unit_tiles, int64_t depth, bool f
     return t < 1 ? 1 : t;
 }
 
+// PRDC's radius (X x X, Y x Y) and cross (X x Y) passes use the cross map over their rectangles, with units short
+// enough that one launch holds at least kPrdcLaunchUnits of them (at n = 10^6 the plain cross map would give a launch fewer units than
+// the device has workgroup slots).  `per_launch` is kad::tiles_per_launch_for with the pass's epilogue weight.
+constexpr int64_t kPrdcLaunchUnits = 2048;
+KAD_HD inline int64_t prdc_rows_per_unit(int64_t TI, int64_t TJ, int64_t per_launch) {
+    const int64_t cap = per_launch / kPrdcLaunchUnits;
+    return cross_rows_per_unit(TI, TJ, cap < 1 ? 1 : cap);
+}
+KAD_HD inline int64_t prdc_units_per_launch(int64_t rr, int64_t per_launch) {
+    const int64_t t = per_launch / rr;
+    return t < 1 ? 1 : t;
+}
+
 // The pair (i, j) at local (r, c) of band tile (I, J), I <= J: counted when j > i and j lies before the end of i's song.
 // `end_i` is offsets[song(i) + 1] for a row of Y, and 0 for a padding row (i >= M): songs are contiguous, so i < j < end_i is
 // exactly "same song".  The kernel holds end_i - J * 128 per row and compares it to c.

@@ -80,11 +80,17 @@ inline std::vector<Launch> launches(int64_t total, int64_t per_launch, int64_t c
 // about 2.3x the slowest sum pass per tile, the LDS atomics of the first pass contending on a few bins).  Longest single launches
 // measured on an MI355X: n = 10^6 at D = 128 / 64, 35 ms (sums) and 17 ms (histogram); 90 % identical rows, every
 // count in one bin, 28 ms (histogram) -- no launch holds the GPU anywhere near 100 ms, n = 10^6 cuts into tens of launches per pass.
-constexpr int64_t kSumEpilogue = 128, kHistEpilogue = 2048;
-KAD_HD inline int64_t tiles_per_launch(int64_t depth, bool f32, bool hist = false) {
-    const int64_t cost = (f32 ? 16 * depth : depth) + (hist ? kHistEpilogue : kSumEpilogue);
+// PRDC's passes weigh their own epilogues: kTopkEpilogue for the radius pass's per-column top-k (a compare and a
+// wave-uniform skip per pair, a 16-step insertion where a value enters), kFlagEpilogue for the cross pass's two threshold tests, counts
+// and ballots per pair.
+constexpr int64_t kSumEpilogue = 128, kHistEpilogue = 2048, kTopkEpilogue = 1024, kFlagEpilogue = 512;
+KAD_HD inline int64_t tiles_per_launch_for(int64_t depth, bool f32, int64_t epilogue) {
+    const int64_t cost = (f32 ? 16 * depth : depth) + epilogue;
     const int64_t t = ((int64_t)1 << 30) / cost;
     return t < 64 ? 64 : t;
+}
+KAD_HD inline int64_t tiles_per_launch(int64_t depth, bool f32, bool hist = false) {
+    return tiles_per_launch_for(depth, f32, hist ? kHistEpilogue : kSumEpilogue);
 }
 
 // the pair (i, j) of rows inside tile (I, J) at local (r, c): counted or not

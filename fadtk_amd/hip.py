@@ -711,3 +711,36 @@ def kad_individual(x, rows, offsets: Sequence[int], bandwidth: Optional[float] =
             "fad_kad_individual")
     out.update(kxx_mean=res.kxx_mean, bandwidth=res.bandwidth, n=res.n)
     return out
+
+
+# ------------------------------------------------------------------------ precision, recall, density, coverage (k-NN manifold metrics)
+PRDC_MAX_K = 16
+
+
+def prdc(x, y, k: int = 5, device: int = 0, details: bool = False) -> dict:
+    """``fad_prdc``: precision, recall, density and coverage of the rows of y (evaluation) against the rows of x (baseline) with k
+    neighbours -> dict of the four values and n, m, k.  ``details=True`` adds the per-row arrays of ``fad_prdc_detail``:
+    ``radius2_x`` [n] and ``radius2_y`` [m] (float32 squared k-NN radii), ``balls_y`` [m] and ``flags_x`` [n] (int32; bit 0 recalled,
+    bit 1 covered).  Both sets are numpy arrays or both torch CUDA tensors of one dtype (float16 / bfloat16 / float32)."""
+    k = int(k)
+    if not 1 <= k <= PRDC_MAX_K:
+        raise ValueError(f"PRDC: k must be in 1 .. {PRDC_MAX_K}, got {k}")
+    lib = K.load_library()
+    (px, n, d, ldx, cx, dev_x, kx), (py, m, dy, ldy, cy, dev_y, ky) = _kad_pair(x, y, "y", device)
+    if d != dy:
+        raise ValueError(f"PRDC: x has D = {d}, y has D = {dy}")
+    if cx != cy:
+        raise ValueError("PRDC: x and y must have the same dtype")
+    if n <= k or m <= k:
+        raise ValueError(f"PRDC with k = {k} needs more than {k} rows per set, got {n} and {m}")
+    res = K.FadPrdcResult()
+    det, arrays = None, {}
+    if details:
+        arrays = {"radius2_x": np.zeros(n, np.float32), "radius2_y": np.zeros(m, np.float32), "balls_y": np.zeros(m, np.int32),
+                  "flags_x": np.zeros(n, np.int32)}
+        det = K.FadPrdcDetail(*(a.ctypes.data for a in arrays.values()))
+    K.check(lib.fad_prdc(px, n, ldx, py, m, ldy, d, cx, dev_x, k, C.byref(res), C.byref(det) if det is not None else None, int(device),
+                         K.current_stream_ptr(device)), "fad_prdc")
+    out = res.as_dict()
+    out.update(arrays)
+    return out

@@ -348,6 +348,33 @@ int fad_kad_individual(const void* x, int64_t n, int64_t ldx, const void* rows, 
                        fad_kad_result_t* base, double* out_mmd2, double* out_kyy_mean, double* out_kxy_mean,
                        int32_t* out_status, int device, void* stream);
 
+/* ------------------------------------------------------------------ precision, recall, density, coverage (k-NN manifold metrics)
+ * Not in the reference: Kynkaanniemi et al. 2019 (precision, recall) and Naeem et al. 2020 (density, coverage) between the baseline
+ * ("real") rows x [n x d] and the evaluation ("fake") rows y [m x d], with k neighbours, Euclidean distances compared squared:
+ *   r_X(i) = the k-th smallest distance from x_i to the OTHER rows of x (self excluded by index, so a duplicate row is a neighbour at
+ *            distance 0); r_Y(j) likewise within y;
+ *   precision = #{j : some i has d(x_i, y_j) < r_X(i)} / m        recall   = #{i : some j has d(x_i, y_j) < r_Y(j)} / n
+ *   density   = sum_j #{i : d(x_i, y_j) < r_X(i)} / (k m)          coverage = #{i : some j has d(x_i, y_j) < r_X(i)} / n
+ * All comparisons strict, as in the authors' `prdc` package (its radius is the (k+1)-th smallest of a row holding self at 0).  Every
+ * decision is taken on the float32 d^2 = |a|^2 + |b|^2 - 2 a.b (products on the matrix cores, clamped at 0), so a pair within rounding of
+ * a radius may fall the other way from a float64 evaluation; integer-valued rows are exact.  Rows are float16, bfloat16 or float32,
+ * host or device per on_device, 1 <= d <= 2048, ld >= d.  k outside 1 .. 16 or an unknown dtype -> FAD_ERR_INVALID; n <= k or m <= k ->
+ * FAD_ERR_TOO_FEW_ROWS (argument errors come before any device call); a NaN/Inf row norm -> FAD_ERR_NOT_FINITE.  n, m < 2^31 - 128.
+ * Integer counts: the same result on every run.  Work goes on `stream`; the call synchronises it. */
+typedef struct fad_prdc_result {
+    double precision, recall, density, coverage;
+    int64_t n, m, k;
+} fad_prdc_result_t;
+/* optional per-row outputs on the host, any of them NULL */
+typedef struct fad_prdc_detail {
+    float* radius2_x;   /* [n] r_X(i)^2 as the comparisons used it (float32) */
+    float* radius2_y;   /* [m] */
+    int32_t* balls_y;   /* [m] #{i : d^2(x_i, y_j) < r_X(i)^2} */
+    int32_t* flags_x;   /* [n] bit 0: recalled (P2 for some j), bit 1: covered (P1 for some j) */
+} fad_prdc_detail_t;
+int fad_prdc(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype,
+             int on_device, int k, fad_prdc_result_t* out, fad_prdc_detail_t* detail /* may be NULL */, int device, void* stream);
+
 /* ------------------------------------------------------------------ diagnostics (NOT part of the drop-in surface)
  * Nothing in fadtk corresponds to these two calls and no binding of the reference needs them: they exist for bench.py's
  * roofline object (HIP events around the tile kernel on the stream it is launched on) and for the GPU tests that check
