@@ -406,7 +406,8 @@ int fad_logmel_htsat(const float* wav, const int64_t* offsets, int64_t n_clips, 
     std::vector<int64_t> base(n_clips, 0), frames(n_clips);
     for (int64_t c = 0; c < n_clips; ++c) {
         const int64_t n = offsets[c + 1] - offsets[c];
-        if (n < 2) return set_error(FAD_ERR_SHAPE, "clip %lld has %lld samples; reflect padding needs at least 2", (long long)c, (long long)n);
+        if (n <= 512)           // one reflection of the 512-sample pad; torch.stft(center=True, pad_mode="reflect") refuses these too
+            return set_error(FAD_ERR_SHAPE, "clip %lld has %lld samples; reflect padding by 512 needs more than 512", (long long)c, (long long)n);
         if (1 + n / 480 != n_frames_out)
             return set_error(FAD_ERR_SHAPE, "clip %lld yields %lld frames, expected %lld (pad or cut clips to one length)",
                              (long long)c, (long long)(1 + n / 480), (long long)n_frames_out);

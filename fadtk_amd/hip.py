@@ -597,7 +597,9 @@ def logmel_whisper(clips, n_mels: int = 80, device: int = 0):
 
 
 def logmel_htsat(clips, device: int = 0):
-    """48 kHz mono clips of ONE common length -> [n_clips, 1 + n/480, 64] float32 (dB log-mel)."""
+    """48 kHz mono clips of ONE common length -> [n_clips, 1 + n/480, 64] float32 (dB log-mel).  Clips of 512 samples or
+    fewer are refused (AssertionError, FAD_ERR_SHAPE): the centred STFT reflects 512 samples at each end, which needs a longer
+    clip -- torch.stft(center=True, pad_mode="reflect") on the reference's path refuses them too."""
     lib = K.load_library()
     K.require_gpu(device)
     ptr, off, on_dev, keep = _clips_view(clips, device)

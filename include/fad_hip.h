@@ -287,7 +287,8 @@ int fad_frechet_batched_vs_baseline(int d, const double* mu_b, const double* cov
  *          (clip max - 8), (x + 4) / 4.   out [n_clips][n_mels][3000].
  * HTSAT   (48 kHz): centred reflect STFT 1024 / hop 480, power, 64 Slaney mels 50-14000 Hz,
  *          10 log10(max(.,1e-10)).  Every clip must give n_frames_out = 1 + n_samples/480 frames.
- *          out [n_clips][n_frames_out][64].
+ *          Clips of 512 samples or fewer -> FAD_ERR_SHAPE: the 512-sample reflect pad must be shorter
+ *          than the clip (torch.stft's rule on the reference's path).  out [n_clips][n_frames_out][64].
  */
 int64_t fad_logmel_vggish_num_examples(int64_t n_samples);
 int fad_logmel_vggish(const float* wav, const int64_t* offsets, int64_t n_clips, float* out,
