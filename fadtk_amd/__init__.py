@@ -18,7 +18,8 @@ def __getattr__(name):
                 "W2V2Model", "HuBERTModel", "WavLMModel", "MERTModel"):
         from . import model_loader
         return getattr(model_loader, name)
-    if name in ("KernelAudioDistance", "calc_kernel_audio_distance", "calc_kernel_audio_distance_individual"):      # lazy: `python -m fadtk_amd.kad` runs the module itself
+    if name in ("KernelAudioDistance", "calc_kernel_audio_distance", "calc_kernel_audio_distance_individual",
+                "calc_kernel_audio_distance_uncertainty", "KadUncertainty"):      # lazy: `python -m fadtk_amd.kad` runs the module itself
         from . import kad
         return getattr(kad, name)
     if name in ("PrecisionRecall", "calc_precision_recall_density_coverage"):      # lazy, as KAD's

@@ -1,6 +1,6 @@
 // Kernel Audio Distance: the unbiased Gaussian-kernel MMD^2 between two sets of embedding rows, and the median pairwise distance
-// of one set (the default bandwidth).  DESIGN.md 4.6.  Per-song KAD (4.7) and the k-NN precision / recall / density / coverage (4.8)
-// run on the same main loop.
+// of one set (the default bandwidth).  DESIGN.md 4.6.  Per-song KAD (4.7), the k-NN precision / recall / density / coverage (4.8) and
+// KAD's standard errors (4.9) run on the same main loop.
 //
 // Every pass is one GEMM-shaped walk over 128 x 128 tiles of a pair space (kad_tiles.h) whose n x m matrix is never stored:
 //   - pack:   each set is copied once into a zero-padded [n_pad x dp] image of its own dtype (dp: D rounded up to 128 bytes, n_pad:
@@ -17,6 +17,7 @@
 #include "fad_common.h"
 #include "kad_tiles.h"
 #include "kad_song_tiles.h"
+#include "kad_unc_tiles.h"
 
 #include <algorithm>
 #include <cmath>
@@ -321,7 +322,8 @@ struct ColArgs {
 
 // k(S') of the wave's 64 rows of a tile added into the lane's two columns (cbase + 32 bj + lane % 32); MASK 0: every pair, 1: a
 // diagonal tile (column > row), 2: a band tile holding more than one song (column < end of the row's song, and on a diagonal tile
-// column > row).  Masks are selects: a NaN row that the clamp turned into k = 1 still adds nothing where it is masked.
+// column > row), 3: a diagonal tile of a full square (column != row).  Masks are selects: a NaN row that the clamp turned into k = 1
+// still adds nothing where it is masked.
 template <int MASK>
 __device__ __forceinline__ void col_sums(const f32x16 (&acc)[2][2], float c, int rbase, int cbase, int lane, const int* lend, bool diag,
                                          double (&dcol)[2]) {
@@ -347,6 +349,7 @@ __device__ __forceinline__ void col_sums(const f32x16 (&acc)[2][2], float c, int
                 const int r = lrow + bi * 32 + (g & 3) + 8 * (g >> 2), col = lcol + bj * 32;
                 if (MASK == 1) e = col > r ? e : 0.f;
                 if (MASK == 2) e = (col < le[bi][g >> 2][g & 3] && (!diag || col > r)) ? e : 0.f;
+                if (MASK == 3) e = col != r ? e : 0.f;
                 s += e;
             }
         dcol[bj] += (double)s;
@@ -462,6 +465,185 @@ __global__ void __launch_bounds__(256) kad_song_reduce_kernel(const double* __re
             kyy[s] = 2.0 * ry[0] / (md * (md - 1.0));
         }
     }
+}
+
+// ---------------------------------------------------------------------------------------- KAD standard errors
+// fad_kad_uncertainty's pass: Z x Z over the units of kad_unc_tiles.h, tile_mfma with col_sums -- every pair on an off-diagonal tile,
+// column != row on a diagonal one -- one float64 slot per (unit, column).  Then four small float64 kernels, each in a fixed order:
+// the row sums and projections a, b per row of Z; per-set means and the spread of b; the centred cross products of a in partial sums
+// over fixed row ranges; those partials summed.
+template <int DT>
+__global__ void __launch_bounds__(kThreads, 2) kad_unc_cols_kernel(ColArgs p) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    double* lx = reinterpret_cast<double*>(lds + 2 * kOpBytes + 2 * kTile * 4);       // the wm = 1 waves' column sums of a unit
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
+    const int rbase = wm * 64, cbase = wn * 64;
+    const int64_t G = gridDim.x, nslots = kad::launch_slots(p.cnt);
+
+    for (int64_t L = blockIdx.x; L < nslots; L += G) {
+        bool live;
+        const int64_t v = kad::slot_tile(L, p.cnt, &live);
+        if (!live) continue;                                                          // uniform over the workgroup
+        const int64_t u = p.u0 + v;
+        const kad::Unit un = p.units[u];
+        double dcol[2] = {0.0, 0.0};
+
+        for (int64_t I = un.I0; I < un.I1; ++I) {
+            f32x16 acc[2][2];
+            tile_mfma<DT>(p.a, p.b, p.ha, p.hb, p.pitch, p.nchunks, I, un.J, lds, [](int) {}, acc);
+            if (I == un.J) col_sums<3>(acc, p.c, rbase, cbase, lane, nullptr, true, dcol);
+            else col_sums<0>(acc, p.c, rbase, cbase, lane, nullptr, false, dcol);
+        }
+
+        // a column: the two lane halves, then the wm = 0 and wm = 1 waves, in this order (kad_cols_kernel)
+#pragma unroll
+        for (int bj = 0; bj < 2; ++bj) dcol[bj] += __shfl_xor(dcol[bj], 32, 64);
+        if (wm == 1 && lane < 32) {
+#pragma unroll
+            for (int bj = 0; bj < 2; ++bj) lx[cbase + bj * 32 + lane] = dcol[bj];
+        }
+        __syncthreads();
+        if (wm == 0 && lane < 32) {
+            double* slot = p.slots + u * kTile;
+#pragma unroll
+            for (int bj = 0; bj < 2; ++bj) slot[cbase + bj * 32 + lane] = dcol[bj] + lx[cbase + bj * 32 + lane];
+        }
+    }
+}
+
+constexpr size_t kLdsUnc = 2 * kOpBytes + 2 * kTile * 4 + kTile * sizeof(double);
+
+// the sets of an uncertainty call as the reduction kernels see them (passed by value)
+struct UncSets {
+    int64_t n, TX;
+    int S;
+    int64_t blk[kad::kUncMaxSets + 1];         // first row block of each set in Z (blk[S] = TZ)
+    int64_t m[kad::kUncMaxSets];
+    int64_t yoff[kad::kUncMaxSets + 1];        // first row of each set in the concatenated per-row outputs
+};
+
+// v summed over the workgroup's 256 threads in a fixed order (all threads get it); `red` is 256 doubles of LDS
+__device__ __forceinline__ double block_sum256(double v, double* red) {
+    __syncthreads();                                                                  // red is free
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    return red[0];
+}
+
+// One thread per column j of Z: its segments' unit slots summed in unit order, then
+//   j = row i of X:        rxx[i] = sum_{j != i} k(x_i, x_j),  a[s * n + i] = rxx[i] / (n - 1) - sum_l k(x_i, y^s_l) / m_s
+//   j = row l of set s:    ryy[l'] = sum_{l2 != l} k(y_l, y_l2),  ryx[l'] = sum_i k(x_i, y_l),  b[l'] = ryy / (m_s - 1) - ryx / n
+// (l' = yoff[s] + l); padding columns write nothing.
+__global__ void __launch_bounds__(256) kad_unc_rows_kernel(const double* __restrict__ slots, const int64_t* __restrict__ seg_start,
+                                                           UncSets q, double* __restrict__ a, double* __restrict__ b,
+                                                           double* __restrict__ rxx, double* __restrict__ ryy, double* __restrict__ ryx) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x, J = j / kTile, c = j % kTile;
+    if (J >= q.blk[q.S]) return;
+    auto seg_sum = [&](int g) {
+        const int64_t k = kad::unc_segment(J, g, q.TX, q.S);
+        double s = 0.0;
+        for (int64_t u = seg_start[k]; u < seg_start[k + 1]; ++u) s += slots[u * kTile + c];
+        return s;
+    };
+    const double n = (double)q.n;
+    if (J < q.TX) {
+        if (j >= q.n) return;
+        const double xx = seg_sum(0), mx = xx / (n - 1.0);
+        rxx[j] = xx;
+        for (int s = 0; s < q.S; ++s) a[s * q.n + j] = mx - seg_sum(s + 1) / (double)q.m[s];
+    } else {
+        int s = 0;
+        while (J >= q.blk[s + 1]) ++s;
+        const int64_t l = j - q.blk[s] * kTile;
+        if (l >= q.m[s]) return;
+        const double yy = seg_sum(s + 1), yx = seg_sum(0);
+        const int64_t o = q.yoff[s] + l;
+        ryy[o] = yy;
+        ryx[o] = yx;
+        b[o] = yy / ((double)q.m[s] - 1.0) - yx / n;
+    }
+}
+
+// Workgroup s < S: stats[5 s ..] = mean a^s, mean b^s, sum (b^s - mean b^s)^2, sum ryy, sum ryx over set s.  Workgroup S:
+// stats[5 S] = sum rxx.  Every sum in a fixed order.
+__global__ void __launch_bounds__(256) kad_unc_sets_kernel(const double* __restrict__ a, const double* __restrict__ b,
+                                                           const double* __restrict__ rxx, const double* __restrict__ ryy,
+                                                           const double* __restrict__ ryx, UncSets q, double* __restrict__ stats) {
+    __shared__ double red[256];
+    const int s = blockIdx.x;
+    if (s == q.S) {
+        double v = 0.0;
+        for (int64_t i = threadIdx.x; i < q.n; i += 256) v += rxx[i];
+        v = block_sum256(v, red);
+        if (threadIdx.x == 0) stats[5 * q.S] = v;
+        return;
+    }
+    const int64_t m = q.m[s];
+    const double* as = a + s * q.n;
+    const double* bs = b + q.yoff[s];
+    double va = 0.0, vb = 0.0, vyy = 0.0, vyx = 0.0;
+    for (int64_t i = threadIdx.x; i < q.n; i += 256) va += as[i];
+    for (int64_t l = threadIdx.x; l < m; l += 256) {
+        vb += bs[l];
+        vyy += ryy[q.yoff[s] + l];
+        vyx += ryx[q.yoff[s] + l];
+    }
+    const double ma = block_sum256(va, red) / (double)q.n;
+    const double mb = block_sum256(vb, red) / (double)m;
+    const double syy = block_sum256(vyy, red), syx = block_sum256(vyx, red);
+    double vv = 0.0;
+    for (int64_t l = threadIdx.x; l < m; l += 256) {
+        const double e = bs[l] - mb;
+        vv += e * e;
+    }
+    vv = block_sum256(vv, red);
+    if (threadIdx.x == 0) {
+        stats[5 * s + 0] = ma;
+        stats[5 * s + 1] = mb;
+        stats[5 * s + 2] = vv;
+        stats[5 * s + 3] = syy;
+        stats[5 * s + 4] = syx;
+    }
+}
+
+// Workgroup (w, y) of a fixed grid of W x ceil(S^2 / 256): the row tiles w, w + W, ... of 32 rows of X, and the pairs
+// p = 256 y + thread: part[w][p = s S + t] = sum over its rows of (a^s_i - mean a^s)(a^t_i - mean a^t), rows in order.  s and t
+// swapped multiply the same two values: the matrix comes out symmetric.
+constexpr int kUncCovRows = 32;
+__global__ void __launch_bounds__(256) kad_unc_cov_kernel(const double* __restrict__ a, const double* __restrict__ stats, UncSets q,
+                                                          double* __restrict__ part) {
+    __shared__ double la[kUncCovRows * kad::kUncMaxSets];
+    const int S = q.S, P = S * S, p = blockIdx.y * 256 + threadIdx.x, s = p / S, u = p % S;
+    double acc = 0.0;
+    const int64_t tiles = (q.n + kUncCovRows - 1) / kUncCovRows;
+    for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+        __syncthreads();                                                              // la is free
+        for (int idx = threadIdx.x; idx < kUncCovRows * S; idx += 256) {
+            const int r = idx % kUncCovRows, c = idx / kUncCovRows;
+            const int64_t i = t * kUncCovRows + r;
+            la[r * S + c] = i < q.n ? a[c * q.n + i] - stats[5 * c] : 0.0;
+        }
+        __syncthreads();
+        if (p < P) {
+#pragma unroll 8
+            for (int r = 0; r < kUncCovRows; ++r) acc += la[r * S + s] * la[r * S + u];
+        }
+    }
+    if (p < P) part[(int64_t)blockIdx.x * P + p] = acc;
+}
+
+// out[p] = the W partials of pair p summed in order
+__global__ void __launch_bounds__(256) kad_unc_cov_sum_kernel(const double* __restrict__ part, int64_t W, int P, double* __restrict__ out) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= P) return;
+    double s = 0.0;
+    for (int64_t w = 0; w < W; ++w) s += part[w * P + p];
+    out[p] = s;
 }
 
 // ---------------------------------------------------------------------------------- precision, recall, density, coverage
@@ -709,9 +891,11 @@ struct KadWorkspace {
     DevBuf raw[2], img[2], h[2], slots, small;       // small: info, pass offsets, pass sums, histograms
     DevBuf cross, band, songs;                       // fad_kad_individual: column slots of the two passes, song tables and outputs
     DevBuf lists, prdc;                              // fad_prdc: the radius passes' top-k slots; radii, counts, flags and totals
+    DevBuf unc_slots, unc;                           // fad_kad_uncertainty: column slots of the pass; unit tables and per-row outputs
     void release_all() {
         for (int i = 0; i < 2; ++i) { raw[i].release(); img[i].release(); h[i].release(); }
         slots.release(); small.release(); cross.release(); band.release(); songs.release(); lists.release(); prdc.release();
+        unc_slots.release(); unc.release();
     }
 };
 
@@ -1098,6 +1282,158 @@ int fad_kad_individual(const void* x, int64_t n, int64_t ldx, const void* rows, 
     base->m = n_rows;
     for (int64_t s = 0; s < n_songs; ++s)
         out_mmd2[s] = out_status[s] == FAD_OK ? base->kxx_mean + out_kyy_mean[s] - 2.0 * out_kxy_mean[s] : NAN;
+    return FAD_OK;
+}
+
+int fad_kad_uncertainty(const void* x, int64_t n, int64_t ldx, const void* const* ys, const int64_t* ms, const int64_t* ldys, int n_sets,
+                        int64_t d, int dtype, int on_device, double bandwidth, fad_kad_result_t* out, double* cov, double* proj_x,
+                        double* proj_y, int device, void* stream) {
+    using namespace fad;
+    if (!out || !cov) return set_error(FAD_ERR_INVALID, "fad_kad_uncertainty: NULL output");
+    if (n_sets < 1 || n_sets > kad::kUncMaxSets)
+        return set_error(FAD_ERR_INVALID, "fad_kad_uncertainty: %d evaluation sets (1 .. %d)", n_sets, kad::kUncMaxSets);
+    if (!ys || !ms || !ldys) return set_error(FAD_ERR_INVALID, "fad_kad_uncertainty: NULL set table");
+    FAD_TRY(check_rows(x, n, ldx, d, dtype, "fad_kad_uncertainty (x)"));
+    for (int s = 0; s < n_sets; ++s) FAD_TRY(check_rows(ys[s], ms[s], ldys[s], d, dtype, "fad_kad_uncertainty (a set)"));
+    if (std::isnan(bandwidth) || std::isinf(bandwidth))
+        return set_error(FAD_ERR_INVALID, "fad_kad_uncertainty: bandwidth %g is not finite", bandwidth);
+    FAD_TRY(check_device(device));
+    DeviceGuard g(device);
+    if (!g.ok) return set_error(FAD_ERR_HIP, "hipSetDevice(%d) failed", device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    KadWorkspace& ws = workspace(device);
+    const int S = n_sets;
+
+    // Z: X, then every set from a tile boundary, in one image (kad_unc_tiles.h)
+    UncSets q{};
+    q.n = n; q.S = S;
+    const std::vector<int64_t> blk = kad::unc_blocks(n, ms, S);
+    q.TX = blk[0];
+    q.yoff[0] = 0;
+    for (int s = 0; s < S; ++s) { q.blk[s] = blk[(size_t)s]; q.m[s] = ms[s]; q.yoff[s + 1] = q.yoff[s] + ms[s]; }
+    q.blk[S] = blk[(size_t)S];
+    const int64_t TZ = q.blk[S], z_pad = TZ * kTile, M = q.yoff[S];
+    const size_t es = dtype_size(dtype);
+    const int64_t dp = depth_elems(d, dtype), pitch = dp * (int64_t)es;
+    FAD_TRY(ws.img[0].reserve((size_t)(z_pad * pitch)));
+    FAD_TRY(ws.h[0].reserve((size_t)z_pad * sizeof(float)));
+    FAD_TRY(ws.small.reserve(4096 * sizeof(double) + 2 * kHistBins * sizeof(unsigned long long)));
+    if (!on_device) FAD_TRY(ws.raw[0].reserve((size_t)((n + M) * d) * es));
+    char* zimg = static_cast<char*>(ws.img[0].p);
+    float* zh = static_cast<float*>(ws.h[0].p);
+    double* info_d = static_cast<double*>(ws.small.p) + 1024;                          // [2 (S + 1)]: norm sum, non-finite rows
+    int64_t staged = 0;
+    for (int s = -1; s < S; ++s) {                                                     // s = -1: X
+        const void* src = s < 0 ? x : ys[s];
+        int64_t rn = s < 0 ? n : ms[s], ld = s < 0 ? ldx : ldys[s];
+        const int64_t r0 = (s < 0 ? 0 : q.blk[s]) * kTile, r_pad = kad::blocks(rn) * kTile;
+        if (!on_device) {
+            char* raw = static_cast<char*>(ws.raw[0].p) + (size_t)(staged * d) * es;
+            FAD_HIP_TRY(hipMemcpy2DAsync(raw, (size_t)d * es, src, (size_t)ld * es, (size_t)d * es, (size_t)rn, hipMemcpyHostToDevice, st));
+            src = raw;
+            ld = d;
+            staged += rn;
+        }
+        const dim3 grid((unsigned)cdiv(r_pad, 4));
+        char* img = zimg + r0 * pitch;
+        switch (dtype) {
+            case FAD_F16: kad_pack_kernel<_Float16><<<grid, 256, 0, st>>>(static_cast<const _Float16*>(src), rn, ld, d, reinterpret_cast<_Float16*>(img), dp, r_pad, zh + r0); break;
+            case FAD_BF16: kad_pack_kernel<__bf16><<<grid, 256, 0, st>>>(static_cast<const __bf16*>(src), rn, ld, d, reinterpret_cast<__bf16*>(img), dp, r_pad, zh + r0); break;
+            default: kad_pack_kernel<float><<<grid, 256, 0, st>>>(static_cast<const float*>(src), rn, ld, d, reinterpret_cast<float*>(img), dp, r_pad, zh + r0); break;
+        }
+        FAD_HIP_TRY(hipGetLastError());
+        kad_norm_info_kernel<<<1, 256, 0, st>>>(zh + r0, rn, info_d + 2 * (s + 1));
+        FAD_HIP_TRY(hipGetLastError());
+    }
+    std::vector<double> info((size_t)(2 * (S + 1)));
+    FAD_HIP_TRY(hipMemcpyAsync(info.data(), info_d, info.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    FAD_HIP_TRY(hipStreamSynchronize(st));
+    for (int s = -1; s < S; ++s)
+        if (info[(size_t)(2 * (s + 1) + 1)] != 0.0)
+            return set_error(FAD_ERR_NOT_FINITE, "KAD: %lld of %lld rows of %s have a NaN/Inf norm", (long long)info[(size_t)(2 * (s + 1) + 1)],
+                             (long long)(s < 0 ? n : ms[s]), s < 0 ? "the baseline" : "an evaluation set");
+
+    const Packed px{zimg, zh, n, pitch, (int)(pitch / kChunk), info[0]};
+    double sigma;
+    float c;
+    FAD_TRY(resolve_sigma(px, bandwidth, dtype, device, st, ws, "fad_kad_uncertainty", &sigma, &c));
+
+    // the pass: units, slots and per-row tables
+    const bool f32 = dtype == FAD_F32;
+    const int64_t rr = kad::unc_rows_per_unit(kad::unc_tiles(blk), kad::tiles_per_launch_for(dp, f32, kad::kUncEpilogue));
+    std::vector<kad::Unit> units;
+    std::vector<int64_t> seg_start;
+    kad::unc_units(blk, rr, &units, &seg_start);
+    const int64_t U = (int64_t)units.size();
+    const int64_t W = std::min<int64_t>(256, cdiv(n, kUncCovRows)), P = (int64_t)S * S;
+
+    // units | seg_start | a [S n] | b [M] | rxx [n] | ryy [M] | ryx [M] | stats [5 S + 1] | cov partials [W P] | cov sums [P]
+    size_t at[11];
+    at[0] = 0;
+    at[1] = at[0] + align256((size_t)U * sizeof(kad::Unit));
+    at[2] = at[1] + align256(seg_start.size() * sizeof(int64_t));
+    at[3] = at[2] + align256((size_t)(S * n) * sizeof(double));
+    at[4] = at[3] + align256((size_t)M * sizeof(double));
+    at[5] = at[4] + align256((size_t)n * sizeof(double));
+    at[6] = at[5] + align256((size_t)M * sizeof(double));
+    at[7] = at[6] + align256((size_t)M * sizeof(double));
+    at[8] = at[7] + align256((size_t)(5 * S + 1) * sizeof(double));
+    at[9] = at[8] + align256((size_t)(W * P) * sizeof(double));
+    at[10] = at[9] + align256((size_t)P * sizeof(double));
+    FAD_TRY(ws.unc.reserve(at[10]));
+    FAD_TRY(ws.unc_slots.reserve((size_t)(U * kTile) * sizeof(double)));
+    char* ub = static_cast<char*>(ws.unc.p);
+    kad::Unit* units_d = reinterpret_cast<kad::Unit*>(ub + at[0]);
+    int64_t* seg_d = reinterpret_cast<int64_t*>(ub + at[1]);
+    double* a_d = reinterpret_cast<double*>(ub + at[2]);
+    double* b_d = reinterpret_cast<double*>(ub + at[3]);
+    double* rxx_d = reinterpret_cast<double*>(ub + at[4]);
+    double* ryy_d = reinterpret_cast<double*>(ub + at[5]);
+    double* ryx_d = reinterpret_cast<double*>(ub + at[6]);
+    double* stats_d = reinterpret_cast<double*>(ub + at[7]);
+    double* part_d = reinterpret_cast<double*>(ub + at[8]);
+    double* covs_d = reinterpret_cast<double*>(ub + at[9]);
+    double* slots = static_cast<double*>(ws.unc_slots.p);
+    FAD_HIP_TRY(hipMemcpyAsync(units_d, units.data(), (size_t)U * sizeof(kad::Unit), hipMemcpyHostToDevice, st));
+    FAD_HIP_TRY(hipMemcpyAsync(seg_d, seg_start.data(), seg_start.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+
+    ColArgs p{};
+    p.a = p.b = zimg; p.ha = p.hb = zh; p.pitch = pitch; p.nchunks = px.nchunks; p.c = c;
+    p.units = units_d; p.slots = slots; p.slot_pitch = kTile;
+    for (const kad::Launch& l : kad::launches(U, kad::unc_units_per_launch(rr, dp, f32), grid_cap(device))) {
+        p.u0 = l.u0; p.cnt = l.cnt;
+        FAD_TRY(with_dtype(dtype, [&](auto dt) { kad_unc_cols_kernel<dt><<<(unsigned)l.grid, kThreads, kLdsUnc, st>>>(p); }));
+    }
+    kad_unc_rows_kernel<<<(unsigned)cdiv(z_pad, 256), 256, 0, st>>>(slots, seg_d, q, a_d, b_d, rxx_d, ryy_d, ryx_d);
+    FAD_HIP_TRY(hipGetLastError());
+    kad_unc_sets_kernel<<<(unsigned)(S + 1), 256, 0, st>>>(a_d, b_d, rxx_d, ryy_d, ryx_d, q, stats_d);
+    FAD_HIP_TRY(hipGetLastError());
+    kad_unc_cov_kernel<<<dim3((unsigned)W, (unsigned)cdiv(P, 256)), 256, 0, st>>>(a_d, stats_d, q, part_d);
+    FAD_HIP_TRY(hipGetLastError());
+    kad_unc_cov_sum_kernel<<<(unsigned)cdiv(P, 256), 256, 0, st>>>(part_d, W, (int)P, covs_d);
+    FAD_HIP_TRY(hipGetLastError());
+
+    std::vector<double> stats((size_t)(5 * S + 1)), covs((size_t)P);
+    FAD_HIP_TRY(hipMemcpyAsync(stats.data(), stats_d, stats.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    FAD_HIP_TRY(hipMemcpyAsync(covs.data(), covs_d, covs.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (proj_x) FAD_HIP_TRY(hipMemcpyAsync(proj_x, a_d, (size_t)(S * n) * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (proj_y) FAD_HIP_TRY(hipMemcpyAsync(proj_y, b_d, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, st));
+    FAD_HIP_TRY(hipStreamSynchronize(st));
+
+    const double nd = (double)n, kxx = stats[(size_t)(5 * S)] / (nd * (nd - 1.0)), cx = 4.0 / (nd * (nd - 1.0));
+    for (int s = 0; s < S; ++s) {
+        const double* t = stats.data() + 5 * s;
+        const double md = (double)ms[s];
+        out[s].mmd2 = t[0] + t[1];
+        out[s].kxx_mean = kxx;
+        out[s].kyy_mean = t[3] / (md * (md - 1.0));
+        out[s].kxy_mean = t[4] / (nd * md);
+        out[s].bandwidth = sigma;
+        out[s].n = n;
+        out[s].m = ms[s];
+        for (int u = 0; u < S; ++u) cov[s * S + u] = cx * covs[(size_t)(s * S + u)];
+        cov[s * S + s] += 4.0 / (md * (md - 1.0)) * t[2];
+    }
     return FAD_OK;
 }
 

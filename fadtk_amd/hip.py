@@ -715,6 +715,52 @@ def kad_individual(x, rows, offsets: Sequence[int], bandwidth: Optional[float] =
     return out
 
 
+KAD_MAX_SETS = 64
+
+
+def kad_uncertainty(x, ys: Sequence, bandwidth: Optional[float] = None, device: int = 0, rows: bool = False) -> dict:
+    """``fad_kad_uncertainty``: KAD between the baseline rows x and each evaluation set ys[s] (1 <= S <= 64), one sigma for all
+    (``bandwidth=None``: the median pairwise distance of x), with the first-order covariance of the S estimates -> dict of float64
+    arrays ``mmd2``, ``kyy_mean``, ``kxy_mean``, ``stderr`` [S] and ``cov`` [S, S], plus ``kxx_mean``, ``bandwidth``, ``n`` and ``m``
+    [S] (int64).  ``rows=True`` adds the per-row projections ``proj_x`` [S, n] (a^s_i) and ``proj_y`` (a list of [m_s] arrays, b^s_l).
+    A first-order (Hoeffding-projection) estimate: meaningful for sets that differ from the baseline; for a set with the baseline's own
+    distribution it understates the spread (include/fad_hip.h).  x and every set are numpy arrays, or all torch CUDA tensors, of one
+    dtype (float16 / bfloat16 / float32)."""
+    ys = list(ys)
+    if not 1 <= len(ys) <= KAD_MAX_SETS:
+        raise ValueError(f"KAD uncertainty takes 1 .. {KAD_MAX_SETS} evaluation sets, got {len(ys)}")
+    lib = K.load_library()
+    views = []
+    for s, y in enumerate(ys):
+        vx, vy = _kad_pair(x, y, f"ys[{s}]", device)
+        views.append(vy)
+    px, n, d, ldx, cx, dev_x, kx = vx
+    S = len(ys)
+    for s, (py, m, dy, ldy, cy, dev_y, ky) in enumerate(views):
+        if d != dy:
+            raise ValueError(f"KAD: x has D = {d}, ys[{s}] has D = {dy}")
+        if cx != cy or dev_x != dev_y:
+            raise ValueError("KAD: x and every set must have the same dtype and live on the same side (host or device)")
+    ptrs = (C.c_void_p * S)(*[v[0] for v in views])
+    ms = np.array([v[1] for v in views], dtype=np.int64)
+    lds = np.array([v[3] for v in views], dtype=np.int64)
+    bw = _kad_bandwidth(bandwidth)
+    res = (K.FadKadResult * S)()
+    cov = np.zeros((S, S))
+    proj_x = np.zeros((S, n)) if rows else None
+    proj_y = np.zeros(int(ms.sum())) if rows else None
+    K.check(lib.fad_kad_uncertainty(px, n, ldx, ptrs, ms.ctypes.data_as(C.POINTER(C.c_int64)), lds.ctypes.data_as(C.POINTER(C.c_int64)),
+                                    S, d, cx, dev_x, bw, res, cov.ctypes.data, proj_x.ctypes.data if rows else None,
+                                    proj_y.ctypes.data if rows else None, int(device), K.current_stream_ptr(device)), "fad_kad_uncertainty")
+    out = {k: np.array([getattr(r, k) for r in res]) for k in ("mmd2", "kyy_mean", "kxy_mean")}
+    out.update(stderr=np.sqrt(np.diag(cov)), cov=cov, kxx_mean=res[0].kxx_mean, bandwidth=res[0].bandwidth, n=int(res[0].n),
+               m=np.array([r.m for r in res], dtype=np.int64))
+    if rows:
+        out["proj_x"] = proj_x
+        out["proj_y"] = np.split(proj_y, np.cumsum(ms)[:-1])
+    return out
+
+
 # ------------------------------------------------------------------------ precision, recall, density, coverage (k-NN manifold metrics)
 PRDC_MAX_K = 16
 

@@ -15,13 +15,18 @@ Per song (``--indiv``): KAD between the baseline and each file of the evaluation
 one batched GPU call (``fad_kad_individual``); ``path,score`` lines sorted by |score|, like fadtk's per-song FAD.
 
     python -m fadtk_amd.kad <model> <baseline_dir> <eval_dir> [csv] [--bandwidth S] [--scale F] [-w N] [--indiv]
+
+Several evaluation sets against one baseline, with standard errors and paired comparisons (``fad_kad_uncertainty``, a first-order
+estimate): ``calc_kernel_audio_distance_uncertainty`` / ``KernelAudioDistance.score_many``, and ``python -m fadtk_amd.kad_compare``.
 """
 from __future__ import annotations
 
 import logging
+import math
 import time
 import traceback
 from argparse import ArgumentParser
+from dataclasses import dataclass, field
 from pathlib import Path
 from typing import Optional, Sequence, Union
 
@@ -105,6 +110,65 @@ def calc_kernel_audio_distance_individual(x, songs: Sequence, bandwidth: Optiona
     return (values, res) if details else values
 
 
+@dataclass
+class KadUncertainty:
+    """KAD of S evaluation sets against one baseline with the first-order covariance of the estimates (``fad_kad_uncertainty``).
+    ``values`` [S] = scale * MMD^2, ``stderr`` [S] = |scale| * sqrt(cov_ss), ``cov`` [S, S] = scale^2 * cov.  A first-order
+    (Hoeffding-projection) estimate: meaningful when the sets differ from the baseline; when a set has the baseline's distribution it
+    understates the spread, so it is not a test of "same distribution"."""
+    values: np.ndarray
+    stderr: np.ndarray
+    cov: np.ndarray
+    bandwidth: float
+    scale: float
+    details: dict = field(repr=False, default_factory=dict)
+
+    def compare(self):
+        """-> (z, p), both [S, S]: z[s, t] = (values[s] - values[t]) / sqrt(cov_ss + cov_tt - 2 cov_st), the paired difference of
+        sets s and t in standard errors, and its two-sided p = erfc(|z| / sqrt 2).  The diagonal (and a pair whose difference has no
+        spread) gives z = 0, p = 1."""
+        S = len(self.values)
+        z, p = np.zeros((S, S)), np.ones((S, S))
+        for s in range(S):
+            for t in range(S):
+                var = self.cov[s, s] + self.cov[t, t] - 2.0 * self.cov[s, t]
+                if s != t and var > 0:
+                    z[s, t] = (self.values[s] - self.values[t]) / math.sqrt(var)
+                    p[s, t] = math.erfc(abs(z[s, t]) / math.sqrt(2.0))
+        return z, p
+
+
+def calc_kernel_audio_distance_uncertainty(x, ys: Sequence, bandwidth: Optional[float] = None, scale: float = 1.0, device: int = 0,
+                                           rows: bool = False) -> KadUncertainty:
+    """KAD between the rows of x (baseline) and each evaluation set in ``ys`` (1 .. 64 of them), one sigma for all (``bandwidth=None``:
+    the median pairwise distance of x), with standard errors and the covariance of the S estimates, in one GPU call
+    (``fad_kad_uncertainty``).  ``scale`` multiplies values and stderr by |scale| (the values by scale) and cov by scale^2;
+    ``compare()`` of the result gives the paired z and p matrices.  numpy arrays or torch CUDA tensors of float16 / bfloat16 /
+    float32; mixed dtypes are cast to float32.  ``rows=True`` keeps the per-row projections in ``details``.  The estimate is
+    first-order: see KadUncertainty."""
+    from . import hip
+    sx = _shape_of(x)
+    if len(sx) != 2 or sx[0] < 2:
+        raise ValueError(f"KAD needs a 2-D baseline of at least 2 rows, got shape {sx}")
+    ys = list(ys)
+    for sh in (_shape_of(y) for y in ys):
+        if len(sh) != 2 or sh[1] != sx[1]:
+            raise ValueError(f"KAD: an evaluation set of shape {sh} against a baseline of D = {sx[1]}")
+        if sh[0] < 2:
+            raise ValueError(f"KAD needs at least 2 rows per set, got {sh[0]}")
+    if hip.K._is_torch(x):
+        if len({x.dtype, *(y.dtype for y in ys)}) > 1:
+            x, ys = x.float(), [y.float() for y in ys]
+    else:
+        x, ys = np.asarray(x), [np.asarray(y) for y in ys]
+        if len({x.dtype, *(y.dtype for y in ys)}) > 1:
+            x, ys = x.astype(np.float32), [y.astype(np.float32) for y in ys]
+    res = hip.kad_uncertainty(x, ys, bandwidth=bandwidth, device=device, rows=rows)
+    scale = float(scale)
+    return KadUncertainty(values=scale * res["mmd2"], stderr=abs(scale) * res["stderr"], cov=scale * scale * res["cov"],
+                          bandwidth=res["bandwidth"], scale=scale, details=res)
+
+
 class KernelAudioDistance:
     """KAD between two directories of audio, over the embedding caches FrechetAudioDistance writes and reads."""
 
@@ -133,6 +197,16 @@ class KernelAudioDistance:
         if x.dtype != y.dtype:
             x, y = x.astype(np.float32), y.astype(np.float32)
         return calc_kernel_audio_distance(x, y, bandwidth=bandwidth, scale=scale, device=self.device_index, details=details)
+
+    def score_many(self, baseline: PathLike, eval_dirs: Sequence[PathLike], bandwidth: Optional[float] = None,
+                   scale: float = 1.0) -> KadUncertainty:
+        """KAD of every directory in ``eval_dirs`` against one baseline, with standard errors and their covariance, in one GPU call
+        (calc_kernel_audio_distance_uncertainty); ``compare()`` of the result gives the paired z / p matrices."""
+        x = self.load_rows(baseline)
+        ys = [self.load_rows(e) for e in eval_dirs]
+        if len({x.dtype, *(y.dtype for y in ys)}) > 1 or x.dtype == np.float64:      # one dtype; float64 caches are narrowed
+            x, ys = x.astype(np.float32), [y.astype(np.float32) for y in ys]
+        return calc_kernel_audio_distance_uncertainty(x, ys, bandwidth=bandwidth, scale=scale, device=self.device_index)
 
     def score_individual(self, baseline: PathLike, eval_dir: PathLike, csv_name: Union[Path, str], bandwidth: Optional[float] = None,
                          scale: float = 1.0) -> Path:

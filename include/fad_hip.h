@@ -348,6 +348,30 @@ int fad_kad_individual(const void* x, int64_t n, int64_t ldx, const void* rows, 
                        const int64_t* offsets, int64_t n_songs, int64_t d, int dtype, int on_device, double bandwidth,
                        fad_kad_result_t* base, double* out_mmd2, double* out_kyy_mean, double* out_kxy_mean,
                        int32_t* out_status, int device, void* stream);
+/* ------------------------------------------------------------------ KAD standard errors, paired comparison of sets
+ * One baseline x [n x d] and S evaluation sets ys[s] [ms[s] x ldys[s]] (1 <= S <= 64), one sigma for all (bandwidth <= 0: the median
+ * distance of x, as fad_kad resolves it).  With k as above, for every row i of x and row l of set s:
+ *   mxx(i) = sum_{j != i} k(x_i, x_j) / (n - 1)          mxs(i) = sum_l k(x_i, y^s_l) / m_s
+ *   mss(l) = sum_{l' != l} k(y^s_l, y^s_l') / (m_s - 1)   msx(l) = sum_i k(x_i, y^s_l) / n
+ *   a^s_i = mxx(i) - mxs(i)                               b^s_l = mss(l) - msx(l)
+ *   MMD^2_s   = mean_i a^s_i + mean_l b^s_l     (= Kxx + Kyy - 2 Kxy: the quantity fad_kad returns)
+ *   cov[s][t] = 4 / (n (n - 1)) sum_i (a^s_i - mean a^s)(a^t_i - mean a^t)  +  [s = t] 4 / (m_s (m_s - 1)) sum_l (b^s_l - mean b^s)^2
+ *   stderr_s  = sqrt(cov[s][s])
+ * cov is the FIRST-ORDER (Hoeffding-projection) covariance of the S unbiased estimates, which share x and are otherwise independent
+ * (the covariance of the relative-similarity test of Bounliphone et al., ICLR 2016).  A paired comparison of sets s and t is
+ * z = (MMD^2_s - MMD^2_t) / sqrt(cov_ss + cov_tt - 2 cov_st), two-sided p = erfc(|z| / sqrt 2).  The estimate is meaningful when the
+ * sets differ from the baseline (any generative model).  When a set has x's distribution the U-statistic is degenerate and the
+ * estimate understates the spread: this is NOT a test of "same distribution".  m_s >= 2 is all that is required; small sets simply
+ * get a poor estimate.
+ * out[s]: mmd2, kxx_mean (the same bits in every out[s]: one fixed-order sum), kyy_mean, kxy_mean, bandwidth, n and m = m_s.  cov
+ * [S x S] row-major; proj_x [S x n] a^s_i and proj_y [sum m_s] b^s_l (set after set) when not NULL.  All outputs are host pointers;
+ * rows are host or device per on_device, one dtype (float16, bfloat16 or float32), 1 <= d <= 2048.  Argument errors come before any
+ * device call: dtype, d, ld < d, n or m_s < 2 -> FAD_ERR_TOO_FEW_ROWS, S outside 1 .. 64, a non-finite bandwidth; a NaN/Inf row norm
+ * -> FAD_ERR_NOT_FINITE.  Float64 sums in a fixed order, no float atomics: the same bits on every run.  Synchronises `stream`. */
+int fad_kad_uncertainty(const void* x, int64_t n, int64_t ldx, const void* const* ys, const int64_t* ms, const int64_t* ldys,
+                        int n_sets, int64_t d, int dtype, int on_device, double bandwidth, fad_kad_result_t* out /* [n_sets] */,
+                        double* cov /* [n_sets * n_sets] */, double* proj_x /* [n_sets * n] or NULL */,
+                        double* proj_y /* [sum m_s] or NULL */, int device, void* stream);
 
 /* ------------------------------------------------------------------ precision, recall, density, coverage (k-NN manifold metrics)
  * Not in the reference: Kynkaanniemi et al. 2019 (precision, recall) and Naeem et al. 2020 (density, coverage) between the baseline
