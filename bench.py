@@ -3,6 +3,14 @@
 
     python bench.py --gpus N --steps K --warmup W        (N>1: launched by torch.distributed.run)
                     [--dump-outputs DIR]                 (the last timed step's score, its terms and both sets' mu / Sigma -> DIR/*.npy)
+                    [--full]                             (everything else the benchmark measures and checks: see below)
+
+A plain run does what its headline needs and nothing more: set-up, warm-up, the K timed steps, --dump-outputs, the JSON line
+(`value`, `ms_per_step` and what the timed loop itself recorded: `roofline` from the tile kernel's events inside it,
+`step_ms_spread`, `host_ms_per_step`) -- what --timed-only gave before --full existed.  Every side block -- repeats, the
+same-pair and other-layout loops, `value_realistic`, the untimed breakdown, the golden-pair parity, `extra`, `cpu_baseline`, the
+all-reduce alone -- runs only with --full, as it did by default before; --timed-only, --no-extras, --no-cpu-baseline and
+--no-realistic trim a --full run as they did, --realistic-only implies --full.
 
 Workload (BASELINE.json configs[2], "C3"): two synthetic float16 embedding matrices of
 [100000 x 512] per GPU, RESIDENT IN HBM when the timed region starts.  One *step* is one pass of the
@@ -20,7 +28,7 @@ i.e. exactly one FAD score over the union of all ranks' rows.  With N GPUs every
 100k-row shard of both sets (weak scaling: rows grow with N), so `value` is reported in
 config-3-sized score workloads per second:  value = N * K / seconds  (at N=1: plain FAD scores/s).
 
-Rank 0 prints ONE JSON line with the driver's fields plus
+Rank 0 prints ONE JSON line with the driver's fields plus (a plain run: `roofline` alone, from the timed loop's own events)
   roofline          dominant kernel (moments tile kernel): achieved TFLOP/s from ALGORITHMIC flops
                     2 sets x 2*N*D^2 per launch / mean launch duration (HIP events on the launch stream,
                     recorded inside the timed region by the library), vs the dense fp16 MFMA peak
@@ -705,7 +713,7 @@ def torchrun_command(gpus, argv):
             "--master-port", os.environ.get("MASTER_PORT", "29541"), str(Path(__file__).resolve()), *argv]
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -724,7 +732,7 @@ def main():
                          "waits for another stream's workgroups to leave the CUs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--realistic-only", action="store_true",
-                    help="profiling aid: the timed loop and the `value_realistic` block, nothing else (implies --timed-only for the other side blocks)")
+                    help="profiling aid: the timed loop and the `value_realistic` block, nothing else (implies --full, and --timed-only for the other side blocks)")
     ap.add_argument("--no-realistic", action="store_true", help="skip the `value_realistic` block (k^-1 spectra, offset frames, reference-order means)")
     ap.add_argument("--no-extras", action="store_true", help="skip the untimed side measurements (used under rocprofv3 "
                                                              "so that the kernel statistics hold the config-3 launches only)")
@@ -750,14 +758,25 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last of them computed (score, its terms, both sets' mu and Sigma) "
                          "as DIR/<name>.npy, float64 (rank 0)")
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="run every side measurement and check as well (repeat and other-layout blocks, value_realistic, breakdown, "
+                         "golden-pair parity, extras, CPU baseline, all-reduce alone); without it a run is set-up, warm-up, the timed "
+                         "steps, --dump-outputs and the line, as --timed-only")
+    args = ap.parse_args(argv)
     if int(args.batch) > 0 and not int(args.group) and not args.multi_stream:
         args.single_stream = True                                        # the batched schedule's default layout
     args.lane_streams = not args.single_stream
     if args.realistic_only:
+        args.full = args.timed_only = True
+    if not args.full:                                                    # a plain run: the headline and nothing else
         args.timed_only = True
     if args.timed_only:
         args.no_extras = True; args.no_cpu_baseline = True
+    return args
+
+
+def main():
+    args = parse_args()
     if (args.gpus > 1 or os.environ.get("FAD_BENCH_FORCE_DIST") == "1") and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         # started from a plain shell: launch the ranks ourselves (the driver's N > 1 command goes through torch.distributed.run and
         # arrives here with WORLD_SIZE set)
@@ -1119,9 +1138,9 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-        # the exchange of the path by itself: the in-place all-reduce of one moments launch's packed statistics, nothing else on the GPU
+        # the exchange of the path by itself (--full): the in-place all-reduce of one moments launch's packed statistics, nothing else on the GPU
         try:
-            buf = (gshared[0][0].buffer if (BATCH and MG > 1) else lanes[0].shared.buffer) if BATCH else None
+            buf = (gshared[0][0].buffer if (BATCH and MG > 1) else lanes[0].shared.buffer) if (BATCH and args.full) else None
             if buf is not None:
                 nb = int(buf.numel()) * buf.element_size()
                 for _ in range(3):
@@ -1439,7 +1458,7 @@ def main():
         "fad": fad0, "fad_pair": ("pair 0 = the golden G7 pair (tests/golden/recipes.c3_pair, numpy seeds 10 / 11)" if not args.timed_only else "last timed step"),
         "parity_rel_err_vs_golden_g7": ((abs(fad0 - float(golden_g7()[1]["fad"])) / float(golden_g7()[1]["fad"]))
                                         if (not args.timed_only and not distributed and golden_g7()[1] is not None) else None),
-        "fad_last_timed_step": fad, "timed_only": bool(args.timed_only), "chain_cus_per_xcd": int(args.chain_cus), "group": G, "batched_chains": BATCH,
+        "fad_last_timed_step": fad, "timed_only": bool(args.timed_only), "full": bool(args.full), "chain_cus_per_xcd": int(args.chain_cus), "group": G, "batched_chains": BATCH,
         "newton_schulz_iters": diag["iters"], "ns_converged": diag["converged"],
         "frames_per_s": n_gpus * args.steps * 2 * N_ROWS / elapsed,
         "value_repeat_median": float(np.median([n_gpus * args.steps / t for t in repeat_s])) if repeat_s else None,

@@ -3,6 +3,7 @@
 # Usage on the GPU box: bash scripts/pmc_tile.sh ; summaries land in gpurun_out/pmc_tile_<pass>.csv
 # SQ counters only: passes with TA_* / TCP_* / TD_* counters never returned on this image (killed by the timeout).
 export TMPDIR=/tmp HSA_ENABLE_IPC_MODE_LEGACY=0
+root=$(cd "$(dirname "$0")/.." && pwd)                # the repository root
 out=$GRAFT_REPO_ROOT/gpurun_out
 mkdir -p $out
 i=0
@@ -10,7 +11,7 @@ while read -r counters; do
   [ -z "$counters" ] && continue
   i=$((i+1))
   rm -rf $out/pmct_$i
-  (cd /tmp && timeout 240 rocprofv3 --kernel-trace --pmc $counters -d $out/pmct_$i -o b -- python $GRAFT_REPO_ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras > /dev/null 2>&1); echo "pass $i rc=$? : $counters"
+  (cd /tmp && timeout 240 rocprofv3 --kernel-trace --pmc $counters -d $out/pmct_$i -o b -- python $root/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-extras > /dev/null 2>&1); echo "pass $i rc=$? : $counters"
   db=$(find $out/pmct_$i -name "*.db" | head -1)
   [ -n "$db" ] && python $GRAFT_REPO_ROOT/scripts/rocpd_summary.py pmc "$db" | grep -E "^kernel|moments_tile_h16" > $out/pmc_tile_$i.csv
   cat $out/pmc_tile_$i.csv

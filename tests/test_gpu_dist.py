@@ -138,7 +138,7 @@ def test_bench_multi_rank_path_on_one_gpu(tmp_path):
     from fadtk_amd import hip
     env = dict(os.environ, FAD_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), RANK="0", WORLD_SIZE="1",
                LOCAL_RANK="0", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-extras"],
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extras"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.strip().split("\n") if ln.startswith("{")]
@@ -209,6 +209,26 @@ def test_bench_dump_outputs_holds_the_last_timed_step(tmp_path):
         np.testing.assert_allclose(got[f"mu_{tag}"], x.mean(axis=0), rtol=0, atol=1e-7)
         cov = np.cov(x, rowvar=False)
         np.testing.assert_allclose(got[f"cov_{tag}"], cov, rtol=0, atol=2e-6 * np.abs(cov).max())
+
+
+def test_bench_plain_run_prints_the_headline_and_runs_no_side_block():
+    """A plain `bench.py --gpus 1 --steps K --warmup W` (no --full): the line carries the headline and the timed loop's own figures,
+    and none of the side blocks ran -- no repeats, no realistic loop, no breakdown, no extras, no CPU baseline."""
+    import json
+    import subprocess
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "1"],
+                       env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"), capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.strip().split("\n") if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+        assert key in out, key
+    assert out["steps"] == 5 and out["warmup"] == 1 and out["value"] > 0 and out["ms_per_step"] > 0
+    assert out["full"] is False and out["timed_only"] is True
+    assert out["roofline"]["kernel_ms"] > 0 and np.isfinite(out["fad_last_timed_step"])
+    assert out["value_repeat_median"] is None and out["realistic"] is None and out["latency_ms_blocking"] is None
+    assert "extra" not in out and "cpu_baseline" not in out and out["parity_rel_err_vs_golden_g7"] is None
 
 
 def test_fused_stats_cli_under_torchrun_with_rccl(tmp_path):

@@ -151,6 +151,23 @@ def test_bench_gpus_n_builds_the_torchrun_command_itself():
     assert bench.torchrun_command(8, ["--gpus", "8"])[4] == "--nproc-per-node=8"
 
 
+def test_bench_plain_run_is_timed_only_and_full_keeps_the_side_blocks():
+    """`bench.py --gpus 1 --steps K --warmup W` runs set-up, warm-up and the timed steps only (what --timed-only did); --full runs
+    every side block as the default did before the option, and --timed-only / --no-extras / --no-cpu-baseline still trim it."""
+    sys.path.insert(0, str(ROOT))
+    import bench
+    plain = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert not plain.full and plain.timed_only and plain.no_extras and plain.no_cpu_baseline
+    assert (plain.steps, plain.warmup, plain.batch, plain.dump_outputs) == (20, 5, 16, None)
+    full = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
+    assert full.full and not full.timed_only and not full.no_extras and not full.no_cpu_baseline and not full.no_realistic
+    trimmed = bench.parse_args(["--full", "--no-extras"])
+    assert trimmed.full and not trimmed.timed_only and trimmed.no_extras and not trimmed.no_cpu_baseline
+    assert bench.parse_args(["--full", "--timed-only"]).timed_only
+    realistic = bench.parse_args(["--realistic-only"])
+    assert realistic.full and realistic.realistic_only and realistic.timed_only
+
+
 def test_tile256_role_tables_cover_the_upper_triangle(tmp_path):
     """fadtk_amd/csrc/tile256_roles.h (shared by the 256-column-slab moments kernel, its planner and its reduce): every 32 x 32
     block on or above the diagonal is owned by exactly one wave of one work item (two on a Z item's triangle), for 1..8 superblocks,
