@@ -125,6 +125,8 @@ SIGNATURES = {
                                      C.POINTER(FadKadResult), _P, _P, _P, _P, C.c_int, _P]),
     "fad_kad_uncertainty": (C.c_int, [_P, _I64, _I64, C.POINTER(_P), C.POINTER(_I64), C.POINTER(_I64), C.c_int, _I64, C.c_int, C.c_int,
                                       C.c_double, C.POINTER(FadKadResult), _P, _P, _P, C.c_int, _P]),
+    "fad_kad_permutation_test": (C.c_int, [_P, _I64, _I64, _P, _I64, _I64, _I64, C.c_int, C.c_int, C.c_double, _P, _I64, C.c_int,
+                                           C.POINTER(FadKadResult), _P, C.POINTER(C.c_double), C.c_int, _P]),
     "fad_prdc": (C.c_int, [_P, _I64, _I64, _P, _I64, _I64, _I64, C.c_int, C.c_int, C.c_int, C.POINTER(FadPrdcResult),
                            C.POINTER(FadPrdcDetail), C.c_int, _P]),
 }

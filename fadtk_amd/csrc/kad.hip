@@ -18,6 +18,7 @@
 #include "kad_tiles.h"
 #include "kad_song_tiles.h"
 #include "kad_unc_tiles.h"
+#include "kad_perm_tiles.h"
 
 #include <algorithm>
 #include <cmath>
@@ -646,6 +647,252 @@ __global__ void __launch_bounds__(256) kad_unc_cov_sum_kernel(const double* __re
     out[p] = s;
 }
 
+// ------------------------------------------------------------------------------------- KAD permutation test
+// fad_kad_permutation_test's pass: Z's upper tile triangle once per permutation group (kad_perm_tiles.h), tile_mfma, then per wave its
+// 64 x 64 part of the kernel tile as the A operand of a second product.  In the 32 x 32 accumulator layout lane (j, h) holds column j
+// and rows (g & 3) + 8 (g >> 2) + 4 h in register g, so registers 8s .. 8s + 7 converted to f16 are k-step s of an A operand whose k
+// index is the tile's row (cdna_hip_programming.md: "An accumulator tile as the next MFMA's operand"):
+//   V^T[j, p] = sum_{i < j} k'_ij u_p(i),   k'_ij = f16(k_ij - c0) (0 below the diagonal of a diagonal tile)
+// with B the labels of the tile's rows for 32 labellings p in the same permuted k order.  Labels enter as the f16 bit pattern 0x0400
+// (2^-14) rather than 1.0, so a fragment is a shift and a mask of a prepared label word (kad_perm_rowbits_kernel); every product is
+// scaled by the same power of two, undone in float64.  The output has the labelling on the lane and column j in the registers, so
+// sum_j u_p(j) V^T[j, p] is a select against a wave-wide mask per register (the column words of kad_perm_colbits_kernel, loaded as
+// scalars) and an add, into one float per lane per word.  float32 over one tile, float64 from there on; the lane halves and the waves
+// meet once per workgroup at the launch's end, in a fixed order.  Padding rows and columns carry label 0, so their k - c0 = -c0
+// never counts.
+#define kConst __attribute__((address_space(4)))  // the constant address space: a uniform address there is a scalar load
+constexpr uint32_t kLabelOne = 0x04000400u;    // a label pair of 1s as two f16 of 2^-14
+constexpr double kLabelScale = 16384.0;        // 2^14
+
+struct PermArgs {
+    const char* z; const float* h;             // Z's image and -|row|^2 / 2 (-inf on the padding rows)
+    int64_t pitch;
+    int nchunks, nw;                           // nw: words of the launch's group
+    float c, c0;                               // log2(e) / sigma^2, the shift
+    int64_t TZ, u0, cnt;                       // the triangle and the launch's tiles [u0, u0 + cnt)
+    const uint32_t* rowbits;                   // the group's row words: [nw][NWZ][32] (kad_perm_rowbits_kernel)
+    const uint32_t* colbits;                   // the group's column words: [nw][z_pad] (kad_perm_colbits_kernel)
+    int64_t nwz, z_pad;
+    double* slots;                             // the group's slots: [group slots][32 nw], added into
+};
+
+template <int DT>
+__global__ void __launch_bounds__(kThreads, 2) kad_perm_kernel(PermArgs p) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), wm = wave >> 1, wn = wave & 1;
+    const int rbase = wm * 64, cbase = wn * 64, hh = lane >> 5, pl = lane & 31;
+    const int64_t G = gridDim.x, nslots = kad::launch_slots(p.cnt);
+    double dq[kad::kPermWords];
+#pragma unroll
+    for (int w = 0; w < kad::kPermWords; ++w) dq[w] = 0.0;
+
+    for (int64_t L = blockIdx.x; L < nslots; L += G) {
+        bool live;
+        const int64_t v = kad::slot_tile(L, p.cnt, &live);
+        if (!live) continue;                                                          // uniform over the workgroup
+        const kad::Tile t = kad::tri_tile(p.u0 + v, p.TZ);
+        f32x16 acc[2][2];
+        tile_mfma<DT>(p.z, p.z, p.h, p.h, p.pitch, p.nchunks, t.I, t.J, lds, [](int) {}, acc);
+
+        // the A operands: k - c0 in f16, [bi][bj][k-step s]; a diagonal tile counts column > row only (tile_sum's mask)
+        const bool diag = t.I == t.J;
+        int lrow = rbase + 4 * hh - (cbase + pl);
+        asm volatile("" : "+v"(lrow));                        // per tile, not hoisted out of the tile loop as lane masks (tile_sum)
+        f16x8 af[2][2][2];
+#pragma unroll
+        for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+            for (int bj = 0; bj < 2; ++bj)
+#pragma unroll
+                for (int g = 0; g < 16; ++g) {
+                    float x = acc[bi][bj][g] * p.c, w;                                // as tile_sum: the clamp in asm
+                    asm("v_min_f32 %0, 0, %1" : "=v"(w) : "v"(x));
+                    float e = __builtin_amdgcn_exp2f(w) - p.c0;
+                    if (diag) e = (bj * 32 - bi * 32 - (g & 3) - 8 * (g >> 2)) > lrow ? e : 0.f;
+                    af[bi][bj][g >> 3][g & 7] = (_Float16)e;
+                }
+
+        // the second product, word by word: B from the row words of the wave's 64 rows, the masked column sum from the column words
+        // The word strides, opaque per tile and the pointers advanced word by word: the 64 per-word offsets are not hoisted out of the
+        // tile loop into SGPRs (spilled).
+        const int64_t b0 = t.I * 4 + wm * 2;                                          // the wave's first 32-row word of Z
+        int64_t rstride = p.z_pad, cstride = p.z_pad;                                 // [nwz][32] row words, z_pad column words
+        int nw = p.nw;
+        asm volatile("" : "+s"(rstride), "+s"(cstride), "+s"(nw));
+        const uint32_t* rw = p.rowbits + b0 * 32 + pl;
+        int64_t cb = t.J * kTile + cbase;                                             // uniform: scalar loads from the constant space
+#pragma unroll
+        for (int w = 0; w < kad::kPermWords; ++w, rw += rstride, cb += cstride) {
+            if (w >= nw) continue;                                                    // uniform
+            u32x4 bf[2][2];                                                           // [bi][s]
+#pragma unroll
+            for (int bi = 0; bi < 2; ++bi) {
+                const uint32_t th = rw[bi * 32] >> (8 * hh);
+#pragma unroll
+                for (int s = 0; s < 2; ++s)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) bf[bi][s][q] = (th << (10 - (4 * s + q))) & kLabelOne;
+            }
+            float sq = 0.f;
+#pragma unroll
+            for (int bj = 0; bj < 2; ++bj) {
+                // opaque per (word, bj): the 32 column words are loaded here, not hoisted out of the loop as 2048 SGPRs (spilled)
+                int64_t co = cb + bj * 32;
+                asm volatile("" : "+s"(co));
+                const kConst uint32_t* cw = (const kConst uint32_t*)p.colbits + co;
+                f32x16 v2 = {};
+#pragma unroll
+                for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+                    for (int s = 0; s < 2; ++s)
+                        v2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[bi][bj][s], __builtin_bit_cast(f16x8, bf[bi][s]), v2, 0, 0, 0);
+#pragma unroll
+                for (int g = 0; g < 16; ++g) {
+                    const int jl = (g & 3) + 8 * (g >> 2);
+                    const uint64_t mask = (uint64_t)cw[jl] | (uint64_t)cw[jl + 4] << 32;     // lane half 0: column jl, half 1: jl + 4
+                    sq += __builtin_amdgcn_inverse_ballot_w64(mask) ? v2[g] : 0.f;
+                }
+            }
+            dq[w] += (double)sq;
+        }
+    }
+
+    // a labelling: the two lane halves, then the four waves in order, into the workgroup's slot (LDS of the tiles is free after the barrier)
+    double* lq = reinterpret_cast<double*>(lds);                                      // [4][32 kPermWords]
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < kad::kPermWords; ++w) {
+        if (w >= p.nw) continue;
+        const double s = dq[w] + __shfl_xor(dq[w], 32, 64);
+        if (lane < 32) lq[wave * 32 * kad::kPermWords + w * 32 + pl] = s;
+    }
+    __syncthreads();
+    double* slot = p.slots + (int64_t)blockIdx.x * 32 * p.nw;                      // the group's slot w: launches add in order
+    for (int i = tid; i < 32 * p.nw; i += kThreads) {
+        const int o = 32 * kad::kPermWords;
+        slot[i] += ((lq[i] + lq[o + i]) + lq[2 * o + i]) + lq[3 * o + i];
+    }
+}
+
+constexpr size_t kLdsPerm = 2 * kOpBytes + 2 * kTile * 4;
+static_assert(4 * 32 * kad::kPermWords * sizeof(double) <= kLdsPerm, "the slot reduction reuses the tiles' LDS");
+
+// Row words: for labelling word w (labellings 32w .. 32w + 31), 32-row word b of Z and labelling 32w + l, the 32 labels of the rows of
+// word b rearranged for the B fragments: pair k = 4s + q (k-step s, elements 2q, 2q + 1) of lane half h holds rows
+// r = 16s + 8(q >> 1) + 4h + 2(q & 1) and r + 1; their labels go to bits k + 8h and 16 + k + 8h.  Labellings >= n_lab are all 0.
+__global__ void __launch_bounds__(256) kad_perm_rowbits_kernel(const uint32_t* __restrict__ lab, int64_t n_lab, int64_t nwz, int64_t W,
+                                                               uint32_t* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= W * nwz * 32) return;
+    const int64_t l = i % 32, b = (i / 32) % nwz, w = i / (32 * nwz), pz = 32 * w + l;
+    const uint32_t x = pz < n_lab ? lab[pz * nwz + b] : 0u;
+    uint32_t t = 0;
+    for (int hh = 0; hh < 2; ++hh)
+        for (int k = 0; k < 8; ++k) {
+            const int s = k >> 2, q = k & 3, r = 16 * s + 8 * (q >> 1) + 4 * hh + 2 * (q & 1);
+            t |= ((x >> r) & 1u) << (k + 8 * hh) | ((x >> (r + 1)) & 1u) << (16 + k + 8 * hh);
+        }
+    out[i] = t;
+}
+
+// Column words: out[w * z_pad + j] bit l = the label of row j of Z in labelling 32w + l.  One wave per (w, pair of 32-row words): lane
+// (l, half) reads the word of labelling 32w + l, and one ballot per bit position transposes 64 rows.
+__global__ void __launch_bounds__(256) kad_perm_colbits_kernel(const uint32_t* __restrict__ lab, int64_t n_lab, int64_t nwz, int64_t W,
+                                                               uint32_t* __restrict__ out) {
+    const int64_t wv = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), npair = (nwz + 1) / 2;
+    if (wv >= W * npair) return;                                                      // uniform over the wave
+    const int lane = threadIdx.x & 63, l = lane & 31;
+    const int64_t w = wv / npair, b = 2 * (wv % npair) + (lane >> 5), pz = 32 * w + l;
+    const uint32_t x = (pz < n_lab && b < nwz) ? lab[pz * nwz + b] : 0u;
+    uint32_t mine = 0;
+    for (int r = 0; r < 32; ++r) {
+        const uint64_t m = __ballot((x >> r) & 1u);
+        if (l == r) mine = lane < 32 ? (uint32_t)m : (uint32_t)(m >> 32);
+    }
+    if (b < nwz) out[w * nwz * 32 + b * 32 + l] = mine;
+}
+
+// bad[0] += labellings 1 .. n_lab - 1 whose ones are not exactly n or that set a bit at or past N (integer atomics)
+__global__ void __launch_bounds__(256) kad_perm_check_kernel(const uint32_t* __restrict__ lab, int64_t nwz, int64_t N, int64_t n,
+                                                             unsigned long long* __restrict__ bad) {
+    __shared__ long long red[256];
+    const int64_t pz = 1 + blockIdx.x;
+    long long ones = 0, stray = 0;
+    for (int64_t b = threadIdx.x; b < nwz; b += 256) {
+        const uint32_t x = lab[pz * nwz + b];
+        const int64_t lo = 32 * b;
+        const uint32_t valid = lo + 32 <= N ? 0xffffffffu : lo >= N ? 0u : (1u << (N - lo)) - 1u;
+        ones += __popc(x & valid);
+        stray += (x & ~valid) != 0;
+    }
+    red[threadIdx.x] = ones + (stray << 40);
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && red[0] != n) atomicAdd(bad, 1ull);
+}
+
+// r[j] = sum over j's column segment of the uncertainty pass's unit slots, in unit order (j < N; 0 on the padding rows)
+__global__ void __launch_bounds__(256) kad_perm_rows_kernel(const double* __restrict__ slots, const int64_t* __restrict__ seg_start,
+                                                            int64_t N, int64_t z_pad, double* __restrict__ r) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= z_pad) return;
+    const int64_t J = j / kTile, c = j % kTile;
+    double s = 0.0;
+    if (j < N)
+        for (int64_t u = seg_start[J]; u < seg_start[J + 1]; ++u) s += slots[u * kTile + c];
+    r[j] = s;
+}
+
+// tot[0] = sum of r in a fixed order (one workgroup)
+__global__ void __launch_bounds__(256) kad_perm_total_kernel(const double* __restrict__ r, int64_t N, double* __restrict__ tot) {
+    __shared__ double red[256];
+    double s = 0.0;
+    for (int64_t j = threadIdx.x; j < N; j += 256) s += r[j];
+    s = block_sum256(s, red);
+    if (threadIdx.x == 0) tot[0] = s;
+}
+
+// the groups of a call as the statistics kernel sees them: first word, words and float64 slot offset of each group
+struct PermGroup { int64_t w0, nw, slot_off, nslots; };
+
+// One workgroup per labelling pz (0: the observed one): q = 2^15 * (its group's slots summed in order) + c0 n (n - 1), R = sum of r over its
+// rows, then Sxx = q, Sxy = R - q, Syy = T - 2R + q and t.  Every sum in a fixed order.  obs[0 .. 2] = Sxx, Syy, Sxy of labelling 0.
+__global__ void __launch_bounds__(256) kad_perm_stats_kernel(const double* __restrict__ slots, const PermGroup* __restrict__ groups, int ng,
+                                                             const uint32_t* __restrict__ lab, int64_t nwz, const double* __restrict__ r,
+                                                             const double* __restrict__ tot, double c0, int64_t n, int64_t m,
+                                                             double* __restrict__ t_out, double* __restrict__ obs) {
+    __shared__ double red[256];
+    const int64_t pz = blockIdx.x, w = pz / 32;
+    int g = 0;
+    while (g + 1 < ng && groups[g + 1].w0 <= w) ++g;
+    const PermGroup gr = groups[g];
+    const int64_t width = 32 * gr.nw, li = pz - 32 * gr.w0;
+    double sq = 0.0;
+    for (int64_t s = threadIdx.x; s < gr.nslots; s += 256) sq += slots[gr.slot_off + s * width + li];
+    sq = block_sum256(sq, red);
+    double sr = 0.0;
+    for (int64_t b = threadIdx.x; b < nwz; b += 256) {
+        uint32_t x = lab[pz * nwz + b];
+        while (x) {
+            const int k = __ffs(x) - 1;
+            sr += r[32 * b + k];
+            x &= x - 1;
+        }
+    }
+    sr = block_sum256(sr, red);
+    if (threadIdx.x == 0) {
+        const double nd = (double)n, md = (double)m, T = tot[0];
+        const double q = 2.0 * kLabelScale * sq + c0 * nd * (nd - 1.0);
+        const double sxx = q, sxy = sr - q, syy = T - 2.0 * sr + q;
+        t_out[pz] = sxx / (nd * (nd - 1.0)) + syy / (md * (md - 1.0)) - 2.0 * sxy / (nd * md);
+        if (pz == 0) { obs[0] = sxx; obs[1] = syy; obs[2] = sxy; }
+    }
+}
+
 // ---------------------------------------------------------------------------------- precision, recall, density, coverage
 // fad_prdc's passes: tile_mfma with two more epilogues, both on d^2 = max(-2 S', 0) as the median's histogram pass forms it.
 //   radius: X x X (and Y x Y) over the full rectangle, per-column top-k.  A lane keeps the k smallest d^2 of each of its two columns in
@@ -892,10 +1139,11 @@ struct KadWorkspace {
     DevBuf cross, band, songs;                       // fad_kad_individual: column slots of the two passes, song tables and outputs
     DevBuf lists, prdc;                              // fad_prdc: the radius passes' top-k slots; radii, counts, flags and totals
     DevBuf unc_slots, unc;                           // fad_kad_uncertainty: column slots of the pass; unit tables and per-row outputs
+    DevBuf perm_lab, perm_rows, perm_cols, perm;     // fad_kad_permutation_test: labellings, row and column words; slots and tables
     void release_all() {
         for (int i = 0; i < 2; ++i) { raw[i].release(); img[i].release(); h[i].release(); }
         slots.release(); small.release(); cross.release(); band.release(); songs.release(); lists.release(); prdc.release();
-        unc_slots.release(); unc.release();
+        unc_slots.release(); unc.release(); perm_lab.release(); perm_rows.release(); perm_cols.release(); perm.release();
     }
 };
 
@@ -1517,6 +1765,212 @@ int fad_prdc(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, in
     out->n = n;
     out->m = m;
     out->k = k;
+    return FAD_OK;
+}
+
+int fad_kad_permutation_test(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype,
+                             int on_device, double bandwidth, const uint32_t* labels, int64_t n_perm, int labels_on_device,
+                             fad_kad_result_t* observed, double* null_out, double* p_value, int device, void* stream) {
+    using namespace fad;
+    if (!observed || !null_out || !p_value) return set_error(FAD_ERR_INVALID, "fad_kad_permutation_test: NULL output");
+    FAD_TRY(check_rows(x, n, ldx, d, dtype, "fad_kad_permutation_test (x)"));
+    FAD_TRY(check_rows(y, m, ldy, d, dtype, "fad_kad_permutation_test (y)"));
+    if (n_perm < 1 || n_perm > kad::kPermMax)
+        return set_error(FAD_ERR_INVALID, "fad_kad_permutation_test: %lld permutations (1 .. %lld)", (long long)n_perm, (long long)kad::kPermMax);
+    if (!labels) return set_error(FAD_ERR_INVALID, "fad_kad_permutation_test: NULL labels");
+    const int64_t N = n + m;
+    if (N > INT32_MAX - kTile) return set_error(FAD_ERR_INVALID, "fad_kad_permutation_test: %lld rows in all (at most %d)", (long long)N, INT32_MAX - kTile);
+    if (std::isnan(bandwidth) || std::isinf(bandwidth))
+        return set_error(FAD_ERR_INVALID, "fad_kad_permutation_test: bandwidth %g is not finite", bandwidth);
+    const int64_t nwl = cdiv(N, 32);                                                   // words per labelling in the ABI
+    if (!labels_on_device) {
+        const uint32_t tail = N % 32 ? (1u << (N % 32)) - 1u : 0xffffffffu;
+        for (int64_t q = 0; q < n_perm; ++q) {
+            const uint32_t* row = labels + q * nwl;
+            int64_t ones = 0;
+            for (int64_t b = 0; b < nwl; ++b) ones += __builtin_popcount(row[b]);
+            if (ones != n || (row[nwl - 1] & ~tail))
+                return set_error(FAD_ERR_INVALID, "fad_kad_permutation_test: labelling %lld has %lld ones%s; every labelling needs exactly n = %lld"
+                                 " and no bit at or past N = %lld", (long long)q, (long long)ones, (row[nwl - 1] & ~tail) ? " and a bit past N" : "",
+                                 (long long)n, (long long)N);
+        }
+    }
+    FAD_TRY(check_device(device));
+    DeviceGuard g(device);
+    if (!g.ok) return set_error(FAD_ERR_HIP, "hipSetDevice(%d) failed", device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    KadWorkspace& ws = workspace(device);
+
+    // Z = [X; Y] in one image, contiguously: kad_pack_kernel at row 0 (n rows, no padding) and at row n (Y, then Z's padding rows)
+    const size_t es = dtype_size(dtype);
+    const int64_t TZ = kad::blocks(N), z_pad = TZ * kTile, nwz = z_pad / 32, dp = depth_elems(d, dtype), pitch = dp * (int64_t)es;
+    const int64_t NL = n_perm + 1, W = kad::perm_words(NL);                            // labellings with the observed one; their words
+    FAD_TRY(ws.img[0].reserve((size_t)(z_pad * pitch)));
+    FAD_TRY(ws.h[0].reserve((size_t)z_pad * sizeof(float)));
+    FAD_TRY(ws.small.reserve(4096 * sizeof(double) + 2 * kHistBins * sizeof(unsigned long long)));
+    if (!on_device) FAD_TRY(ws.raw[0].reserve((size_t)(N * d) * es));
+    char* zimg = static_cast<char*>(ws.img[0].p);
+    float* zh = static_cast<float*>(ws.h[0].p);
+    for (int s = 0; s < 2; ++s) {
+        const void* src = s ? y : x;
+        int64_t rn = s ? m : n, ld = s ? ldy : ldx;
+        const int64_t r0 = s ? n : 0, r_pad = s ? z_pad - n : n;
+        if (!on_device) {
+            char* raw = static_cast<char*>(ws.raw[0].p) + (size_t)(r0 * d) * es;
+            FAD_HIP_TRY(hipMemcpy2DAsync(raw, (size_t)d * es, src, (size_t)ld * es, (size_t)d * es, (size_t)rn, hipMemcpyHostToDevice, st));
+            src = raw;
+            ld = d;
+        }
+        const dim3 grid((unsigned)cdiv(r_pad, 4));
+        char* img = zimg + r0 * pitch;
+        switch (dtype) {
+            case FAD_F16: kad_pack_kernel<_Float16><<<grid, 256, 0, st>>>(static_cast<const _Float16*>(src), rn, ld, d, reinterpret_cast<_Float16*>(img), dp, r_pad, zh + r0); break;
+            case FAD_BF16: kad_pack_kernel<__bf16><<<grid, 256, 0, st>>>(static_cast<const __bf16*>(src), rn, ld, d, reinterpret_cast<__bf16*>(img), dp, r_pad, zh + r0); break;
+            default: kad_pack_kernel<float><<<grid, 256, 0, st>>>(static_cast<const float*>(src), rn, ld, d, reinterpret_cast<float*>(img), dp, r_pad, zh + r0); break;
+        }
+        FAD_HIP_TRY(hipGetLastError());
+    }
+    double* info_d = static_cast<double*>(ws.small.p) + 1024;                          // norm sum, non-finite rows, bad labellings
+    unsigned long long* bad_d = reinterpret_cast<unsigned long long*>(info_d + 2);
+    kad_norm_info_kernel<<<1, 256, 0, st>>>(zh, N, info_d);
+    FAD_HIP_TRY(hipGetLastError());
+
+    // the labellings: the observed one (Z's first n rows), then the caller's, at a row pitch of nwz words (Z's padding rows are 0)
+    FAD_TRY(ws.perm_lab.reserve((size_t)(NL * nwz) * sizeof(uint32_t)));
+    uint32_t* lab = static_cast<uint32_t*>(ws.perm_lab.p);
+    std::vector<uint32_t> obs_row((size_t)nwz, 0u);
+    for (int64_t b = 0; b < n / 32; ++b) obs_row[(size_t)b] = 0xffffffffu;
+    if (n % 32) obs_row[(size_t)(n / 32)] = (1u << (n % 32)) - 1u;
+    FAD_HIP_TRY(hipMemsetAsync(lab, 0, (size_t)(NL * nwz) * sizeof(uint32_t), st));
+    FAD_HIP_TRY(hipMemcpyAsync(lab, obs_row.data(), (size_t)nwz * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    FAD_HIP_TRY(hipMemcpy2DAsync(lab + nwz, (size_t)nwz * sizeof(uint32_t), labels, (size_t)nwl * sizeof(uint32_t), (size_t)nwl * sizeof(uint32_t),
+                                 (size_t)n_perm, labels_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+    FAD_HIP_TRY(hipMemsetAsync(bad_d, 0, sizeof(unsigned long long), st));
+    kad_perm_check_kernel<<<(unsigned)n_perm, 256, 0, st>>>(lab, nwz, N, n, bad_d);
+    FAD_HIP_TRY(hipGetLastError());
+    double info[2];
+    unsigned long long bad = 0;
+    FAD_HIP_TRY(hipMemcpyAsync(info, info_d, sizeof(info), hipMemcpyDeviceToHost, st));
+    FAD_HIP_TRY(hipMemcpyAsync(&bad, bad_d, sizeof(bad), hipMemcpyDeviceToHost, st));
+    FAD_HIP_TRY(hipStreamSynchronize(st));
+    if (bad) return set_error(FAD_ERR_INVALID, "fad_kad_permutation_test: %llu labellings do not have exactly n = %lld ones below N = %lld", bad,
+                              (long long)n, (long long)N);
+    if (info[1] != 0.0)
+        return set_error(FAD_ERR_NOT_FINITE, "KAD: %lld of %lld rows of x and y have a NaN/Inf norm", (long long)info[1], (long long)N);
+
+    // the row and column words of every labelling word
+    FAD_TRY(ws.perm_rows.reserve((size_t)(W * z_pad) * sizeof(uint32_t)));
+    FAD_TRY(ws.perm_cols.reserve((size_t)(W * z_pad) * sizeof(uint32_t)));
+    uint32_t* rows_d = static_cast<uint32_t*>(ws.perm_rows.p);
+    uint32_t* cols_d = static_cast<uint32_t*>(ws.perm_cols.p);
+    kad_perm_rowbits_kernel<<<(unsigned)cdiv(W * z_pad, 256), 256, 0, st>>>(lab, NL, nwz, W, rows_d);
+    FAD_HIP_TRY(hipGetLastError());
+    kad_perm_colbits_kernel<<<(unsigned)cdiv(W * cdiv(nwz, 2), 4), 256, 0, st>>>(lab, NL, nwz, W, cols_d);
+    FAD_HIP_TRY(hipGetLastError());
+
+    // sigma: the given one, or the median pairwise distance of Z (fad_kad_median_distance on the pooled rows, bit for bit)
+    const Packed pz{zimg, zh, N, pitch, (int)(pitch / kChunk), info[0]};
+    double sigma;
+    float c;
+    FAD_TRY(resolve_sigma(pz, bandwidth, dtype, device, st, ws, "fad_kad_permutation_test", &sigma, &c));
+
+    // r = K'1 and T = 1'r: kad_unc_cols_kernel's walk over Z x Z (one set, kad_unc_tiles.h), float32 kernel values
+    const bool f32 = dtype == FAD_F32;
+    const std::vector<int64_t> blk = kad::unc_blocks(N, nullptr, 0);
+    const int64_t rr = kad::unc_rows_per_unit(kad::unc_tiles(blk), kad::tiles_per_launch_for(dp, f32, kad::kUncEpilogue));
+    std::vector<kad::Unit> units;
+    std::vector<int64_t> seg_start;
+    kad::unc_units(blk, rr, &units, &seg_start);
+    const int64_t U = (int64_t)units.size();
+    std::vector<int64_t> gslots;
+    const std::vector<kad::PermLaunch> pl = kad::perm_launches(TZ, NL, dp, f32, grid_cap(device), &gslots);
+    const int ng = (int)gslots.size();
+    std::vector<PermGroup> groups((size_t)ng);
+    int64_t nslot_doubles = 0;
+    for (int q = 0; q < ng; ++q) {
+        const int64_t w0 = kad::perm_group_start(q, ng, W), nw = kad::perm_group_start(q + 1, ng, W) - w0;
+        groups[(size_t)q] = PermGroup{w0, nw, nslot_doubles, gslots[(size_t)q]};
+        nslot_doubles += gslots[(size_t)q] * 32 * nw;
+    }
+
+    // units | seg_start | r [z_pad] | T | groups | t [NL] | observed sums [3] | permutation slots
+    size_t at[9];
+    at[0] = 0;
+    at[1] = at[0] + align256((size_t)U * sizeof(kad::Unit));
+    at[2] = at[1] + align256(seg_start.size() * sizeof(int64_t));
+    at[3] = at[2] + align256((size_t)z_pad * sizeof(double));
+    at[4] = at[3] + align256(sizeof(double));
+    at[5] = at[4] + align256((size_t)ng * sizeof(PermGroup));
+    at[6] = at[5] + align256((size_t)NL * sizeof(double));
+    at[7] = at[6] + align256(3 * sizeof(double));
+    at[8] = at[7] + align256((size_t)nslot_doubles * sizeof(double));
+    FAD_TRY(ws.perm.reserve(at[8]));
+    FAD_TRY(ws.unc_slots.reserve((size_t)(U * kTile) * sizeof(double)));
+    char* pb = static_cast<char*>(ws.perm.p);
+    kad::Unit* units_d = reinterpret_cast<kad::Unit*>(pb + at[0]);
+    int64_t* seg_d = reinterpret_cast<int64_t*>(pb + at[1]);
+    double* r_d = reinterpret_cast<double*>(pb + at[2]);
+    double* tot_d = reinterpret_cast<double*>(pb + at[3]);
+    PermGroup* groups_d = reinterpret_cast<PermGroup*>(pb + at[4]);
+    double* t_d = reinterpret_cast<double*>(pb + at[5]);
+    double* obs_d = reinterpret_cast<double*>(pb + at[6]);
+    double* pslots = reinterpret_cast<double*>(pb + at[7]);
+    FAD_HIP_TRY(hipMemcpyAsync(units_d, units.data(), (size_t)U * sizeof(kad::Unit), hipMemcpyHostToDevice, st));
+    FAD_HIP_TRY(hipMemcpyAsync(seg_d, seg_start.data(), seg_start.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    FAD_HIP_TRY(hipMemcpyAsync(groups_d, groups.data(), (size_t)ng * sizeof(PermGroup), hipMemcpyHostToDevice, st));
+
+    ColArgs ca{};
+    ca.a = ca.b = zimg; ca.ha = ca.hb = zh; ca.pitch = pitch; ca.nchunks = pz.nchunks; ca.c = c;
+    ca.units = units_d; ca.slots = static_cast<double*>(ws.unc_slots.p); ca.slot_pitch = kTile;
+    for (const kad::Launch& l : kad::launches(U, kad::unc_units_per_launch(rr, dp, f32), grid_cap(device))) {
+        ca.u0 = l.u0; ca.cnt = l.cnt;
+        FAD_TRY(with_dtype(dtype, [&](auto dt) { kad_unc_cols_kernel<dt><<<(unsigned)l.grid, kThreads, kLdsUnc, st>>>(ca); }));
+    }
+    kad_perm_rows_kernel<<<(unsigned)cdiv(z_pad, 256), 256, 0, st>>>(ca.slots, seg_d, N, z_pad, r_d);
+    FAD_HIP_TRY(hipGetLastError());
+    kad_perm_total_kernel<<<1, 256, 0, st>>>(r_d, N, tot_d);
+    FAD_HIP_TRY(hipGetLastError());
+    double T;
+    FAD_HIP_TRY(hipMemcpyAsync(&T, tot_d, sizeof(double), hipMemcpyDeviceToHost, st));
+    FAD_HIP_TRY(hipStreamSynchronize(st));
+
+    // the shift: the kernel value at the median distance (e^-1/2) under the default sigma; the mean off-diagonal kernel value of Z
+    // under a given one.  Any constant gives the same t; it sets how much of each kernel value f16 keeps.
+    const float c0 = bandwidth > 0 ? (float)(T / ((double)N * (double)(N - 1))) : 0.60653065971263342f;
+
+    FAD_HIP_TRY(hipMemsetAsync(pslots, 0, (size_t)nslot_doubles * sizeof(double), st));
+    PermArgs pa{};
+    pa.z = zimg; pa.h = zh; pa.pitch = pitch; pa.nchunks = pz.nchunks; pa.c = c; pa.c0 = c0; pa.TZ = TZ; pa.nwz = nwz; pa.z_pad = z_pad;
+    for (const kad::PermLaunch& l : pl) {
+        const PermGroup& gr = groups[(size_t)l.group];
+        pa.nw = (int)l.nw; pa.u0 = l.u0; pa.cnt = l.cnt;
+        pa.rowbits = rows_d + l.w0 * z_pad;
+        pa.colbits = cols_d + l.w0 * z_pad;
+        pa.slots = pslots + gr.slot_off;
+        FAD_TRY(with_dtype(dtype, [&](auto dt) { kad_perm_kernel<dt><<<(unsigned)l.grid, kThreads, kLdsPerm, st>>>(pa); }));
+    }
+    kad_perm_stats_kernel<<<(unsigned)NL, 256, 0, st>>>(pslots, groups_d, ng, lab, nwz, r_d, tot_d, (double)c0, n, m, t_d, obs_d);
+    FAD_HIP_TRY(hipGetLastError());
+    std::vector<double> t((size_t)NL);
+    double obs[3];
+    FAD_HIP_TRY(hipMemcpyAsync(t.data(), t_d, (size_t)NL * sizeof(double), hipMemcpyDeviceToHost, st));
+    FAD_HIP_TRY(hipMemcpyAsync(obs, obs_d, sizeof(obs), hipMemcpyDeviceToHost, st));
+    FAD_HIP_TRY(hipStreamSynchronize(st));
+
+    const double nd = (double)n, md = (double)m;
+    observed->mmd2 = t[0];
+    observed->kxx_mean = obs[0] / (nd * (nd - 1.0));
+    observed->kyy_mean = obs[1] / (md * (md - 1.0));
+    observed->kxy_mean = obs[2] / (nd * md);
+    observed->bandwidth = sigma;
+    observed->n = n;
+    observed->m = m;
+    int64_t ge = 0;
+    for (int64_t q = 0; q < n_perm; ++q) {
+        null_out[q] = t[(size_t)q + 1];
+        ge += t[(size_t)q + 1] >= t[0];
+    }
+    *p_value = (double)(1 + ge) / (double)(n_perm + 1);
     return FAD_OK;
 }
 

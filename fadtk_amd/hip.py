@@ -761,6 +761,102 @@ def kad_uncertainty(x, ys: Sequence, bandwidth: Optional[float] = None, device: 
     return out
 
 
+KAD_MAX_PERMUTATIONS = 65536
+
+
+def kad_label_words(n_rows: int) -> int:
+    """words of one packed labelling of N pooled rows: ceil(N / 32)"""
+    return (int(n_rows) + 31) // 32
+
+
+def _kad_labels(labels, N: int, device: int):
+    """-> (ptr, P, on_device, keepalive) of labellings as the C ABI takes them: [P x ceil(N / 32)] uint32 words (numpy uint32 / int32,
+    or a torch CUDA int32 tensor used in place), or a bool / uint8 [P x N] 0/1 matrix (numpy: packed on the host; torch: on the
+    device)."""
+    W = kad_label_words(N)
+    if K._is_torch(labels):
+        import torch
+        if labels.dim() != 2:
+            raise ValueError(f"KAD permutation test: labels must be 2-D, got shape {tuple(labels.shape)}")
+        if labels.dtype in (torch.bool, torch.uint8):
+            if labels.shape[1] != N:
+                raise ValueError(f"KAD permutation test: 0/1 labels must have N = {N} columns, got {labels.shape[1]}")
+            labels = pack_labels_torch(labels)
+        elif labels.dtype != torch.int32 and getattr(torch, "uint32", None) != labels.dtype:
+            raise ValueError(f"KAD permutation test: packed labels must be 32-bit words, got {labels.dtype}")
+        if labels.shape[1] != W:
+            raise ValueError(f"KAD permutation test: packed labels must have ceil(N / 32) = {W} words per row, got {labels.shape[1]}")
+        if not labels.is_cuda:
+            labels = labels.numpy().view(np.uint32)
+        else:
+            labels = labels.contiguous()
+            return labels.data_ptr(), labels.shape[0], 1, labels
+    a = np.asarray(labels)
+    if a.ndim != 2:
+        raise ValueError(f"KAD permutation test: labels must be 2-D, got shape {a.shape}")
+    if a.dtype in (np.bool_, np.uint8):
+        if a.shape[1] != N:
+            raise ValueError(f"KAD permutation test: 0/1 labels must have N = {N} columns, got {a.shape[1]}")
+        if a.dtype == np.uint8 and a.size and a.max() > 1:
+            raise ValueError("KAD permutation test: uint8 labels must be 0 or 1")
+        a = pack_labels(a)
+    elif a.dtype in (np.uint32, np.int32):
+        a = np.ascontiguousarray(a).view(np.uint32)
+    else:
+        raise ValueError(f"KAD permutation test: labels must be bool / uint8 [P, N] or 32-bit words [P, ceil(N / 32)], got {a.dtype}")
+    if a.shape[1] != W:
+        raise ValueError(f"KAD permutation test: packed labels must have ceil(N / 32) = {W} words per row, got {a.shape[1]}")
+    return a.ctypes.data, a.shape[0], 0, a
+
+
+def pack_labels(u) -> np.ndarray:
+    """0/1 labellings [P, N] (numpy) -> packed words [P, ceil(N / 32)] uint32: bit (i & 31) of word i >> 5 is row i."""
+    u = np.asarray(u).astype(bool)
+    P, N = u.shape
+    W = kad_label_words(N)
+    pad = np.zeros((P, 32 * W), dtype=bool)
+    pad[:, :N] = u
+    return np.ascontiguousarray(np.packbits(pad, axis=1, bitorder="little").view("<u4").astype(np.uint32))
+
+
+def pack_labels_torch(u):
+    """0/1 labellings [P, N] (torch, on their device) -> packed words [P, ceil(N / 32)] as int32 (the uint32 bits)."""
+    import torch
+    P, N = u.shape
+    W = kad_label_words(N)
+    bits = torch.zeros((P, 32 * W), dtype=torch.int64, device=u.device)
+    bits[:, :N] = u.to(torch.int64)
+    shifts = torch.arange(32, device=u.device, dtype=torch.int64)
+    words = (bits.view(P, W, 32) << shifts).sum(dim=2)
+    return torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32)
+
+
+def kad_permutation_test(x, y, labels, bandwidth: Optional[float] = None, device: int = 0) -> dict:
+    """``fad_kad_permutation_test``: the two-sample permutation test of KAD on the pooled rows Z = [x; y] -> dict of fad_kad_result
+    for the observed labelling (mmd2 = t_0, kxx_mean, kyy_mean, kxy_mean, bandwidth, n, m), ``null`` [P] (t of every labelling in
+    ``labels``) and ``p_value`` = (1 + #{null >= t_0}) / (P + 1).  ``labels``: the P random labellings (each with exactly n ones over
+    the N = n + m rows), packed words [P, ceil(N / 32)] (bit i & 31 of word i >> 5 is row i) or a 0/1 matrix [P, N]; the observed one
+    is added by the library.  ``bandwidth=None``: the median pairwise distance of Z (exact test); a given sigma is used as is."""
+    lib = K.load_library()
+    (px, n, d, ldx, cx, dev_x, kx), (py, m, dy, ldy, cy, dev_y, ky) = _kad_pair(x, y, "y", device)
+    if d != dy:
+        raise ValueError(f"KAD: x has D = {d}, y has D = {dy}")
+    if cx != cy:
+        raise ValueError("KAD: x and y must have the same dtype")
+    pl, P, dev_l, kl = _kad_labels(labels, n + m, device)
+    if not 1 <= P <= KAD_MAX_PERMUTATIONS:
+        raise ValueError(f"KAD permutation test takes 1 .. {KAD_MAX_PERMUTATIONS} labellings, got {P}")
+    bw = _kad_bandwidth(bandwidth)
+    res = K.FadKadResult()
+    null = np.zeros(P)
+    pv = C.c_double()
+    K.check(lib.fad_kad_permutation_test(px, n, ldx, py, m, ldy, d, cx, dev_x, bw, pl, P, dev_l, C.byref(res), null.ctypes.data,
+                                         C.byref(pv), int(device), K.current_stream_ptr(device)), "fad_kad_permutation_test")
+    out = res.as_dict()
+    out.update(null=null, p_value=float(pv.value))
+    return out
+
+
 # ------------------------------------------------------------------------ precision, recall, density, coverage (k-NN manifold metrics)
 PRDC_MAX_K = 16
 

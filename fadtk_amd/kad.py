@@ -18,6 +18,8 @@ one batched GPU call (``fad_kad_individual``); ``path,score`` lines sorted by |s
 
 Several evaluation sets against one baseline, with standard errors and paired comparisons (``fad_kad_uncertainty``, a first-order
 estimate): ``calc_kernel_audio_distance_uncertainty`` / ``KernelAudioDistance.score_many``, and ``python -m fadtk_amd.kad_compare``.
+Whether a set is distinguishable from the baseline at all (a two-sample permutation test, ``fad_kad_permutation_test``):
+``calc_kernel_audio_distance_permutation_test`` / ``KernelAudioDistance.permutation_test``, and ``python -m fadtk_amd.kad_permutation``.
 """
 from __future__ import annotations
 
@@ -169,6 +171,66 @@ def calc_kernel_audio_distance_uncertainty(x, ys: Sequence, bandwidth: Optional[
                           bandwidth=res["bandwidth"], scale=scale, details=res)
 
 
+def random_labellings(n: int, m: int, permutations: int, seed: int = 0, device: int = 0, chunk: int = 64):
+    """``permutations`` random labellings of N = n + m pooled rows, each with exactly n ones, packed to words [P, ceil(N / 32)] (int32
+    holding the uint32 bits) on cuda:``device``: a seeded torch generator there, a stable argsort of uniform keys per labelling, packed
+    on the device ``chunk`` labellings at a time.  The same (n, m, permutations, seed) gives the same words on every run."""
+    import torch
+    from .hip import pack_labels_torch
+    N = n + m
+    dev = torch.device("cuda", device)
+    gen = torch.Generator(device=dev).manual_seed(int(seed))
+    out = []
+    for p0 in range(0, permutations, chunk):
+        b = min(chunk, permutations - p0)
+        keys = torch.rand((b, N), generator=gen, device=dev)
+        idx = torch.argsort(keys, dim=1, stable=True)[:, :n]
+        u = torch.zeros((b, N), dtype=torch.bool, device=dev)
+        u.scatter_(1, idx, True)
+        out.append(pack_labels_torch(u))
+    return torch.cat(out)
+
+
+def calc_kernel_audio_distance_permutation_test(x, y, permutations: int = 1000, seed: int = 0, bandwidth: Optional[float] = None,
+                                                scale: float = 1.0, labels=None, return_labels: bool = False, device: int = 0) -> dict:
+    """Is y distinguishable from the baseline x at all?  The two-sample permutation test of KAD (``fad_kad_permutation_test``): the
+    rows are pooled, relabelled at random ``permutations`` times with the sizes held at n and m, and MMD^2 is recomputed for every
+    labelling in one fused GPU pass; p = (1 + #{null >= observed}) / (P + 1).  ``bandwidth=None``: the median pairwise distance of the
+    POOLED rows, which keeps the test exact (KAD's default, the baseline's median, would make it approximate); a given sigma is used as
+    is.  Labellings come from a seeded generator on the device unless ``labels`` gives them (bool / uint8 [P, N] or packed words
+    [P, ceil(N / 32)]).  numpy arrays or torch CUDA tensors of float16 / bfloat16 / float32.  -> dict: ``kad`` (scale * MMD^2),
+    ``mmd2``, ``p_value``, ``null`` [P] (MMD^2 of every random labelling), ``bandwidth``, ``kxx_mean``, ``kyy_mean``, ``kxy_mean``,
+    ``n``, ``m``, ``permutations``, ``seed`` (None when labels are given) and, with ``return_labels``, ``labels`` (packed words)."""
+    from . import hip
+    sx, sy = _shape_of(x), _shape_of(y)
+    if len(sx) != 2 or len(sy) != 2:
+        raise ValueError(f"KAD needs two 2-D row matrices, got shapes {sx} and {sy}")
+    if sx[1] != sy[1]:
+        raise ValueError(f"KAD: the sets have different dimensions ({sx[1]} and {sy[1]})")
+    if sx[0] < 2 or sy[0] < 2:
+        raise ValueError(f"KAD needs at least 2 rows per set, got {sx[0]} and {sy[0]}")
+    if labels is None:
+        if not 1 <= int(permutations) <= hip.KAD_MAX_PERMUTATIONS:
+            raise ValueError(f"KAD permutation test takes 1 .. {hip.KAD_MAX_PERMUTATIONS} permutations, got {permutations}")
+        labels = random_labellings(sx[0], sy[0], int(permutations), seed=seed, device=device)
+    else:
+        seed = None
+    if hip.K._is_torch(x) and hip.K._is_torch(y):
+        if x.dtype != y.dtype:                     # one dtype, as calc_kernel_audio_distance_uncertainty casts mixed sets
+            x, y = x.float(), y.float()
+    elif not hip.K._is_torch(x) and not hip.K._is_torch(y):
+        x, y = np.asarray(x), np.asarray(y)
+        if x.dtype != y.dtype:
+            x, y = x.astype(np.float32), y.astype(np.float32)
+    res = hip.kad_permutation_test(x, y, labels, bandwidth=bandwidth, device=device)
+    out = {"kad": float(scale) * res["mmd2"], "mmd2": res["mmd2"], "p_value": res["p_value"], "null": res["null"],
+           "bandwidth": res["bandwidth"], "kxx_mean": res["kxx_mean"], "kyy_mean": res["kyy_mean"], "kxy_mean": res["kxy_mean"],
+           "n": int(res["n"]), "m": int(res["m"]), "permutations": int(len(res["null"])), "seed": seed}
+    if return_labels:
+        out["labels"] = labels
+    return out
+
+
 class KernelAudioDistance:
     """KAD between two directories of audio, over the embedding caches FrechetAudioDistance writes and reads."""
 
@@ -207,6 +269,17 @@ class KernelAudioDistance:
         if len({x.dtype, *(y.dtype for y in ys)}) > 1 or x.dtype == np.float64:      # one dtype; float64 caches are narrowed
             x, ys = x.astype(np.float32), [y.astype(np.float32) for y in ys]
         return calc_kernel_audio_distance_uncertainty(x, ys, bandwidth=bandwidth, scale=scale, device=self.device_index)
+
+    def permutation_test(self, baseline: PathLike, eval_dir: PathLike, permutations: int = 1000, seed: int = 0,
+                         bandwidth: Optional[float] = None, scale: float = 1.0) -> dict:
+        """The KAD permutation test of ``eval_dir`` against ``baseline`` (calc_kernel_audio_distance_permutation_test), sigma from the
+        pooled rows by default."""
+        x = self.load_rows(baseline)
+        y = self.load_rows(eval_dir)
+        if x.dtype != y.dtype or x.dtype == np.float64:
+            x, y = x.astype(np.float32), y.astype(np.float32)
+        return calc_kernel_audio_distance_permutation_test(x, y, permutations=permutations, seed=seed, bandwidth=bandwidth, scale=scale,
+                                                           device=self.device_index)
 
     def score_individual(self, baseline: PathLike, eval_dir: PathLike, csv_name: Union[Path, str], bandwidth: Optional[float] = None,
                          scale: float = 1.0) -> Path:

@@ -373,6 +373,30 @@ int fad_kad_uncertainty(const void* x, int64_t n, int64_t ldx, const void* const
                         double* cov /* [n_sets * n_sets] */, double* proj_x /* [n_sets * n] or NULL */,
                         double* proj_y /* [sum m_s] or NULL */, int device, void* stream);
 
+/* ------------------------------------------------------------------ KAD two-sample permutation test
+ * Is y distinguishable from x at all?  Z = [x; y] pooled (N = n + m rows), K' = the Gaussian kernel matrix of Z with a zero diagonal,
+ * r = K'1, T = 1'r.  A labelling is a 0/1 vector u over Z's rows with exactly n ones (the "baseline" group):
+ *   q(u) = u'K'u,  R(u) = u'r,  Sxx = q,  Sxy = R - q,  Syy = T - 2R + q
+ *   t(u) = Sxx / (n (n - 1)) + Syy / (m (m - 1)) - 2 Sxy / (n m)        (fad_kad's MMD^2 when u is x's own labelling)
+ * Labelling 0 is the observed one (Z's first n rows), added by the library; `labels` holds the n_perm random ones as packed bits,
+ * [n_perm x ceil(N / 32)] uint32 row-major, bit (i & 31) of word i >> 5 is row i of Z; every labelling has exactly n ones and no bit at
+ * or past N.  null[p] = t(u_{p+1}) (host, n_perm entries); p_value = (1 + #{p : null[p] >= t_0}) / (n_perm + 1), compared in float64.
+ * observed: mmd2 = t_0, its kxx / kyy / kxy means, sigma, n and m.
+ * Bandwidth <= 0: sigma = the median pairwise distance of Z, bit for bit fad_kad_median_distance on the concatenated rows -- a function of
+ * the pooled rows alone, so the test is exact.  A given sigma is used as is; KAD's baseline median (fad_kad's default) depends on the
+ * labelling and makes the test approximate.  Every labelling goes through the same kernels, so the p-value is exact under
+ * exchangeability whatever the rounding: q is summed on the matrix cores from f16(k - c0) (c0 = e^-1/2 under the default sigma, the
+ * mean off-diagonal kernel value of Z under a given one), R and T from float32 kernel values, all in float64 past one tile.
+ * Rows host or device per on_device, labels per labels_on_device.  Argument errors come before any device call: dtype, d outside
+ * 1 .. 2048, ld < d, n or m < 2 -> FAD_ERR_TOO_FEW_ROWS, n_perm outside 1 .. 65536, N >= 2^31 - 128, a non-finite bandwidth, host
+ * labels with a wrong count -> FAD_ERR_INVALID.  Device labels with a wrong count -> FAD_ERR_INVALID (checked on the device); a NaN/Inf
+ * row norm -> FAD_ERR_NOT_FINITE.  Workspace (kept per thread and device): Z's image, about 3 (n_perm + 33) N / 8 bytes of label words,
+ * the row-sum pass's slots (128 float64 per unit, about 16 384 units), and at most 512 x 1024 float64 slots per group of 1024 labellings.  No float atomics: the
+ * same bits on every run.  Synchronises `stream`. */
+int fad_kad_permutation_test(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype,
+                             int on_device, double bandwidth, const uint32_t* labels, int64_t n_perm, int labels_on_device,
+                             fad_kad_result_t* observed, double* null /* [n_perm] host */, double* p_value, int device, void* stream);
+
 /* ------------------------------------------------------------------ precision, recall, density, coverage (k-NN manifold metrics)
  * Not in the reference: Kynkaanniemi et al. 2019 (precision, recall) and Naeem et al. 2020 (density, coverage) between the baseline
  * ("real") rows x [n x d] and the evaluation ("fake") rows y [m x d], with k neighbours, Euclidean distances compared squared:
