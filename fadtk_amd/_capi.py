@@ -239,8 +239,11 @@ def current_stream_ptr(device: Optional[int] = None) -> int:
     return 0
 
 
-def rows_view(x) -> Tuple[int, int, int, int, int, int, object]:
-    """-> (ptr, n, d, ld, dtype_code, on_device, keepalive) for a 2-D frame matrix."""
+def rows_view(x, host_bf16: bool = False) -> Tuple[int, int, int, int, int, int, object]:
+    """-> (ptr, n, d, ld, dtype_code, on_device, keepalive) for a 2-D frame matrix.
+
+    A host torch.bfloat16 matrix is widened to float32 unless ``host_bf16``: then it goes in as FAD_BF16, like the same tensor on the
+    device (for entry points that stage host rows by element size, such as fad_frechet_batched_vs_baseline)."""
     if _is_torch(x):
         import torch
         if x.dim() != 2:
@@ -253,6 +256,8 @@ def rows_view(x) -> Tuple[int, int, int, int, int, int, object]:
         if x.is_cuda:
             return x.data_ptr(), x.shape[0], x.shape[1], max(x.stride(0), x.shape[1]), codes[x.dtype], 1, x
         if x.dtype == torch.bfloat16:
+            if host_bf16:
+                return x.data_ptr(), x.shape[0], x.shape[1], max(x.stride(0), x.shape[1]), FAD_BF16, 0, x
             x = x.to(torch.float32)
         x = x.numpy()
     a = np.asarray(x)

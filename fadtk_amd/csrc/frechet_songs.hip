@@ -526,7 +526,8 @@ __global__ __launch_bounds__(256) void gram_eig(const double* __restrict__ xc, c
         }
     }
     double t = 0.0;
-    for (int i = tid; i < m; i += 256) { const double lam = G[i][i]; t += lam > 0.0 ? sqrt(lam) : 0.0; }
+    // (a NaN eigenvalue -- a non-finite Sigma_b reaches G through W even when the song is finite -- stays NaN: the host reads it as FAD_ERR_NOT_FINITE)
+    for (int i = tid; i < m; i += 256) { const double lam = G[i][i]; t += lam > 0.0 ? sqrt(lam) : (lam == lam ? 0.0 : lam); }
     t = block_sum(t, red);
     if (tid == 0) tr_sqrt_out[song] = t;
 }
@@ -1041,6 +1042,16 @@ static int batched_core(int d, const double* dmu_b, const double* dcov_b, const 
     return FAD_OK;
 }
 
+// Every route's last word on a song: a score that is not finite -- a NaN or infinite frame makes the song's mean and tr Sigma_s NaN, whatever
+// its route did with the matrix root -- is FAD_ERR_NOT_FINITE with a NaN score, never a NaN or an infinity with status 0 or -8 (the
+// reference's eig raises on such a song and score_individual drops it, fad.py:380-383).
+static void mark_non_finite(int64_t n_songs, double* out_scores, int32_t* out_status) {
+    for (int64_t s = 0; s < n_songs; ++s)
+        if ((out_status[s] == FAD_OK || out_status[s] == FAD_ERR_NOT_CONVERGED) && !std::isfinite(out_scores[s])) {
+            out_status[s] = FAD_ERR_NOT_FINITE; out_scores[s] = __builtin_nan("");
+        }
+}
+
 // Songs of many frames with the reference's own means (mean_mode = 1, 16-bit / float32 frames): the walk of numpy's running sums is a second
 // pass over all frames (0.4 ms for 2000 x [2250 x 128]) that nothing but the MEAN TERM of a score waits for -- and a score is linear in it.
 // So the walk and the mean terms run on the library's side stream beside the covariances and the square roots (MFMA work, the HBM idle), the
@@ -1054,7 +1065,11 @@ static int batched_impl(int d, const double* dmu_b, const double* dcov_b, const 
     hipStream_t side = moments_side_stream(device);
     const bool defer = mean_mode == 1 && !std::is_same<TIn, double>::value && long_songs > 0 && side != nullptr &&
                        (h_off[n_songs] - h_off[0]) / n_songs >= 64;
-    if (!defer) return batched_core<TIn>(d, dmu_b, dcov_b, drows, ld, h_off, d_off, n_songs, mean_mode, device, st, ws, knobs, out_scores, out_status, false);
+    if (!defer) {
+        const int rc = batched_core<TIn>(d, dmu_b, dcov_b, drows, ld, h_off, d_off, n_songs, mean_mode, device, st, ws, knobs, out_scores, out_status, false);
+        if (rc == FAD_OK) mark_non_finite(n_songs, out_scores, out_status);
+        return rc;
+    }
     FAD_TRY(ws.songrun.reserve((size_t)n_songs * d * sizeof(float) + (size_t)n_songs * sizeof(double) + 64));
     float* runs = static_cast<float*>(ws.songrun.p);
     double* mt_ref = reinterpret_cast<double*>(static_cast<char*>(ws.songrun.p) + (((size_t)n_songs * d * sizeof(float) + 63) & ~(size_t)63));
@@ -1082,6 +1097,7 @@ static int batched_impl(int d, const double* dmu_b, const double* dcov_b, const 
             if (!(out_scores[s] == out_scores[s])) continue;             // (not scored)
             out_scores[s] += h_ref[s] - h_scal[2 * s];
         }
+        mark_non_finite(n_songs, out_scores, out_status);
     } while (false);
     if (rc != FAD_OK) (void)hipStreamSynchronize(side);                  // (nothing of this call may still be reading the frames when it returns an error)
     (void)hipEventDestroy(fork); (void)hipEventDestroy(join);

@@ -508,7 +508,7 @@ def frechet_batched(mu_b, cov_b, rows, offsets: Sequence[int], mean_mode: int = 
         mu_b = K.f64_host(mu_b)
         d = mu_b.shape[0]
         cov_b = K.f64_host(cov_b, (d, d))
-    ptr, n, dd, ld, code, on_dev, keep = K.rows_view(rows)
+    ptr, n, dd, ld, code, on_dev, keep = K.rows_view(rows, host_bf16=True)      # (host bfloat16 rows: their means rounded as on the device)
     if n > 0 and dd != d:
         raise AssertionError(f"songs have {dd} features, baseline has {d}")
     if base_on_dev and not on_dev:

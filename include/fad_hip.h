@@ -252,7 +252,10 @@ int fad_frechet_multi_end(fad_frechet_job_t* job, int count, double* out_fad, fa
  * Replaces the loop of score_individual (fadtk/fad.py:373-387): for every song s (rows
  * [offsets[s], offsets[s+1]) of `rows`), FAD between the baseline (mu_b, cov_b) and that song's
  * own (mu_s, cov_s).  Songs with fewer than 2 frames get status FAD_ERR_TOO_FEW_ROWS and a NaN
- * score (the reference drops them, fad.py:380-391).
+ * score (the reference drops them, fad.py:380-391).  A song with a NaN or infinite frame, and every song of two or more frames when
+ * cov_b holds a non-finite entry, gets status FAD_ERR_NOT_FINITE and a NaN score, in every route; the other songs of the call keep
+ * the bits they have without it (the reference's eig raises on such a song and score_individual drops it).  No song comes back with
+ * a non-finite score and status FAD_OK or FAD_ERR_NOT_CONVERGED.
  * mean_mode: 0 = song mean in float64; 1 = round the song mean to the input dtype first, as
  * np.mean does for float16 (model_loader.py:47-48 + fad.py:48).
  * on_device = 1: rows, mu_b and cov_b are DEVICE pointers (a caller scoring many batches against one baseline uploads it
