@@ -26,6 +26,9 @@ def __getattr__(name):
     if name in ("PrecisionRecall", "calc_precision_recall_density_coverage"):      # lazy, as KAD's
         from . import prdc
         return getattr(prdc, name)
+    if name in ("NearestNeighbours", "calc_nearest_neighbours", "calc_authenticity"):      # lazy, as KAD's
+        from . import nearest
+        return getattr(nearest, name)
     if name == "cache_embedding_files":
         from .fad_batch import cache_embedding_files
         return cache_embedding_files

@@ -66,6 +66,13 @@ class FadPrdcDetail(C.Structure):
     _fields_ = [("radius2_x", C.c_void_p), ("radius2_y", C.c_void_p), ("balls_y", C.c_void_p), ("flags_x", C.c_void_p)]
 
 
+class FadNearestResult(C.Structure):
+    _fields_ = [("authenticity", C.c_double), ("n", C.c_int64), ("m", C.c_int64), ("k", C.c_int64), ("copied", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 _P = C.c_void_p
 _I64 = C.c_int64
 # name -> (restype, argtypes)     -- one entry per declaration in include/fad_hip.h
@@ -129,6 +136,8 @@ SIGNATURES = {
                                            C.POINTER(FadKadResult), _P, C.POINTER(C.c_double), C.c_int, _P]),
     "fad_prdc": (C.c_int, [_P, _I64, _I64, _P, _I64, _I64, _I64, C.c_int, C.c_int, C.c_int, C.POINTER(FadPrdcResult),
                            C.POINTER(FadPrdcDetail), C.c_int, _P]),
+    "fad_nearest": (C.c_int, [_P, _I64, _I64, _P, _I64, _I64, _I64, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P,
+                              C.POINTER(FadNearestResult), C.c_int, _P]),
 }
 
 _lib = None

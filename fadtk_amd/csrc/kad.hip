@@ -1,6 +1,7 @@
 // Kernel Audio Distance: the unbiased Gaussian-kernel MMD^2 between two sets of embedding rows, and the median pairwise distance
-// of one set (the default bandwidth).  DESIGN.md 4.6.  Per-song KAD (4.7), the k-NN precision / recall / density / coverage (4.8) and
-// KAD's standard errors (4.9) run on the same main loop.
+// of one set (the default bandwidth).  DESIGN.md 4.6.  Per-song KAD (4.7), the k-NN precision / recall / density / coverage (4.8),
+// KAD's standard errors (4.9), its permutation test (4.10) and the nearest baseline rows with authenticity (4.11) run on the same main
+// loop.
 //
 // Every pass is one GEMM-shaped walk over 128 x 128 tiles of a pair space (kad_tiles.h) whose n x m matrix is never stored:
 //   - pack:   each set is copied once into a zero-padded [n_pad x dp] image of its own dtype (dp: D rounded up to 128 bytes, n_pad:
@@ -1133,6 +1134,135 @@ __global__ void __launch_bounds__(1024) prdc_stats_kernel(const int* __restrict_
     if (threadIdx.x < 4) out[threadIdx.x] = red[threadIdx.x][0];
 }
 
+// ------------------------------------------------------------------------------------ nearest baseline rows, authenticity
+// fad_nearest's cross pass: X rows x Y columns on PRDC's cross map, tile_mfma with a per-column top-k of 64-bit keys
+// (bits(d^2) << 32) | i, d^2 = max(-2 S', 0) with the sign bit cleared (the clamp may give -0.0), so that a key orders as (d^2, i) and
+// the result is fully determined.  After each tile one v_permlane32_swap per pair of accumulator elements hands lane half h both row
+// halves of column bj = h: a lane keeps ONE list (PRDC's two float lists' registers), and the row of every element is wave-uniform.
+// The list (KB entries, KB >= k, a template bucket: 1, 4, 8, 16) is descending, t[0] the k-th smallest key, entries q >= k held at 0;
+// a key enters by t[q] = max(t[q + 1], min(t[q], v)) (topk_insert's med3 on u64) behind topk_tile's wave-uniform skip, and KB = 1 is a
+// plain u64 min.
+// Padding rows give d^2 = +inf: their keys sort after every real row's and never reach an output (n >= k).  At a unit's end the wm = 1
+// waves' lists merge into the wm = 0 waves' through LDS, one list of k keys per (row range R, column) slot; nearest_reduce_kernel
+// merges a column's NR slots.  Integers and float32 bits only: the same result on every run.
+template <int KB>
+__device__ __forceinline__ void key_insert(uint64_t (&t)[KB], uint64_t v) {
+#pragma unroll
+    for (int q = 0; q < KB - 1; ++q) {
+        const uint64_t lo = t[q] < v ? t[q] : v;
+        t[q] = t[q + 1] > lo ? t[q + 1] : lo;
+    }
+    t[KB - 1] = t[KB - 1] < v ? t[KB - 1] : v;
+}
+
+template <int KB>
+__device__ __forceinline__ void key_init(uint64_t (&t)[KB], int k) {
+#pragma unroll
+    for (int q = 0; q < KB; ++q) t[q] = q < k ? ~0ull : 0ull;
+}
+
+__device__ __forceinline__ uint64_t d2_key(float acc, uint32_t i) {
+    const uint32_t b = __float_as_uint(fmaxf(-2.f * acc, 0.f)) & 0x7fffffffu;
+    return (uint64_t)b << 32 | i;
+}
+
+template <int DT, int KB>
+__global__ void __launch_bounds__(kThreads, 2) nearest_cross_kernel(PrdcArgs p, uint64_t* __restrict__ lists) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    uint64_t* lx = reinterpret_cast<uint64_t*>(lds + 2 * kOpBytes + 2 * kTile * 4);     // the wm = 1 waves' lists of a unit [128][KB]
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
+    const int rbase = wm * 64, c = wn * 64 + (lane >> 5) * 32 + (lane & 31);          // the lane's column of the tile (after the swap)
+    const int64_t G = gridDim.x, nslots = kad::launch_slots(p.cnt);
+
+    for (int64_t L = blockIdx.x; L < nslots; L += G) {
+        bool live;
+        const int64_t v = kad::slot_tile(L, p.cnt, &live);
+        if (!live) continue;                                                          // uniform over the workgroup
+        const int64_t u = p.u0 + v;
+        const kad::Unit un = kad::cross_unit(u, p.TI, p.TJ, p.rr);
+        uint64_t t[KB];
+        key_init(t, p.k);
+
+        for (int64_t I = un.I0; I < un.I1; ++I) {
+            f32x16 acc[2][2];
+            tile_mfma<DT>(p.a, p.b, p.ha, p.hb, p.pitch, p.nchunks, I, un.J, lds, [](int) {}, acc);
+            const uint32_t i0 = (uint32_t)(I * kTile + rbase);
+#pragma unroll
+            for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+                for (int g = 0; g < 16; ++g) {
+                    // lanes 32..63 of column block 0 swap with lanes 0..31 of column block 1: lane half h then holds column bj = h at
+                    // rows r (first) and r + 4 (second)
+                    const auto s = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[bi][0][g]), __float_as_uint(acc[bi][1][g]), false,
+                                                                    false);
+                    const uint32_t r = i0 + bi * 32 + (g & 3) + 8 * (g >> 2);
+                    const uint64_t k0 = d2_key(__uint_as_float(s[0]), r), k1 = d2_key(__uint_as_float(s[1]), r + 4);
+                    if constexpr (KB == 1) {
+                        t[0] = k0 < t[0] ? k0 : t[0];
+                        t[0] = k1 < t[0] ? k1 : t[0];
+                    } else {
+                        if (__ballot(k0 < t[0])) key_insert(t, k0);                  // wave-uniform skip
+                        if (__ballot(k1 < t[0])) key_insert(t, k1);
+                    }
+                }
+        }
+
+        if (wm == 1) {
+#pragma unroll
+            for (int q = 0; q < KB; ++q) lx[c * KB + q] = t[q];
+        }
+        __syncthreads();
+        if (wm == 0) {
+#pragma unroll
+            for (int q = 0; q < KB; ++q) key_insert(t, q < p.k ? lx[c * KB + q] : ~0ull);
+            uint64_t* out = lists + ((u / p.TJ) * p.list_pitch + un.J * kTile + c) * p.k;
+#pragma unroll
+            for (int q = 0; q < KB; ++q)
+                if (q < p.k) out[q] = t[q];
+        }
+    }
+}
+
+template <int KB>
+constexpr size_t lds_nearest() { return 2 * kOpBytes + 2 * kTile * 4 + kTile * KB * sizeof(uint64_t); }
+
+// column j < m: the k smallest keys of its NR slots -> index[j * k + q], dist2[j * k + q] in ascending (d^2, i)
+__global__ void __launch_bounds__(256) nearest_reduce_kernel(const uint64_t* __restrict__ lists, int64_t nr, int64_t pitch, int k, int64_t m,
+                                                             int32_t* __restrict__ index, float* __restrict__ dist2) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= m) return;
+    uint64_t t[kMaxK];
+    key_init(t, k);
+    for (int64_t R = 0; R < nr; ++R) {
+        const uint64_t* l = lists + (R * pitch + j) * k;
+#pragma unroll
+        for (int q = 0; q < kMaxK; ++q) key_insert(t, q < k ? l[q] : ~0ull);
+    }
+#pragma unroll
+    for (int q = 0; q < kMaxK; ++q)
+        if (q < k) {
+            index[j * k + (k - 1 - q)] = (int32_t)(uint32_t)t[q];
+            dist2[j * k + (k - 1 - q)] = __uint_as_float((uint32_t)(t[q] >> 32));
+        }
+}
+
+// authenticity: nn_r2[j] = r1^2 of y_j's nearest row, and the count of copied rows (d^2 <= r1^2, non-strict) added to *copied
+__global__ void __launch_bounds__(256) nearest_copied_kernel(const int32_t* __restrict__ index, const float* __restrict__ dist2, int k,
+                                                             int64_t m, const float* __restrict__ r2x, int64_t n,
+                                                             float* __restrict__ nn_r2, unsigned long long* __restrict__ copied) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    int hit = 0;
+    if (j < m) {
+        const int32_t i = index[j * k];
+        const float r = i >= 0 && i < n ? r2x[i] : NAN;                              // always a row of x when n >= k
+        nn_r2[j] = r;
+        hit = dist2[j * k] <= r;
+    }
+    const int n_hit = __syncthreads_count(hit);
+    if (threadIdx.x == 0 && n_hit) atomicAdd(copied, (unsigned long long)n_hit);     // integer counts: order does not matter
+}
+
 // ------------------------------------------------------------------------------------------------------------------ host side
 struct KadWorkspace {
     DevBuf raw[2], img[2], h[2], slots, small;       // small: info, pass offsets, pass sums, histograms
@@ -1140,10 +1270,12 @@ struct KadWorkspace {
     DevBuf lists, prdc;                              // fad_prdc: the radius passes' top-k slots; radii, counts, flags and totals
     DevBuf unc_slots, unc;                           // fad_kad_uncertainty: column slots of the pass; unit tables and per-row outputs
     DevBuf perm_lab, perm_rows, perm_cols, perm;     // fad_kad_permutation_test: labellings, row and column words; slots and tables
+    DevBuf near;                                     // fad_nearest: index, dist2, radii, nn radii, copied count
     void release_all() {
         for (int i = 0; i < 2; ++i) { raw[i].release(); img[i].release(); h[i].release(); }
         slots.release(); small.release(); cross.release(); band.release(); songs.release(); lists.release(); prdc.release();
         unc_slots.release(); unc.release(); perm_lab.release(); perm_rows.release(); perm_cols.release(); perm.release();
+        near.release();
     }
 };
 
@@ -1350,6 +1482,27 @@ static int radius_pass(const Packed& x, int k, int dtype, int device, hipStream_
         FAD_TRY(with_dtype(dtype, [&](auto dt) { prdc_radius_kernel<dt><<<(unsigned)l.grid, kThreads, kLdsRadius, st>>>(p); }));
     }
     prdc_radius_reduce_kernel<<<(unsigned)cdiv(p.list_pitch, 256), 256, 0, st>>>(lists, q.NR, p.list_pitch, k, x.n, r2);
+    FAD_HIP_TRY(hipGetLastError());
+    return FAD_OK;
+}
+
+// index / dist2 [m x k] (device) = the k nearest rows of x to every row of y, ascending in (d^2, i); `lists` holds NR * TJ * 128 * k keys
+static int nearest_pass(const Packed& x, const Packed& y, int k, int dtype, int device, hipStream_t st, uint64_t* lists, int32_t* index,
+                        float* dist2) {
+    const PrdcPlan q = prdc_plan(x, y, dtype, kad::kNearestEpilogue);
+    PrdcArgs p{};
+    p.a = x.img; p.ha = x.h; p.b = y.img; p.hb = y.h; p.pitch = x.pitch; p.nchunks = x.nchunks; p.k = k;
+    p.TI = q.TI; p.TJ = q.TJ; p.rr = q.rr; p.list_pitch = q.TJ * kTile;
+    for (const kad::Launch& l : kad::launches(q.NR * q.TJ, q.per_launch, grid_cap(device))) {
+        p.u0 = l.u0; p.cnt = l.cnt;
+        FAD_TRY(with_dtype(dtype, [&](auto dt) {
+            if (k == 1) nearest_cross_kernel<dt, 1><<<(unsigned)l.grid, kThreads, lds_nearest<1>(), st>>>(p, lists);
+            else if (k <= 4) nearest_cross_kernel<dt, 4><<<(unsigned)l.grid, kThreads, lds_nearest<4>(), st>>>(p, lists);
+            else if (k <= 8) nearest_cross_kernel<dt, 8><<<(unsigned)l.grid, kThreads, lds_nearest<8>(), st>>>(p, lists);
+            else nearest_cross_kernel<dt, kMaxK><<<(unsigned)l.grid, kThreads, lds_nearest<kMaxK>(), st>>>(p, lists);
+        }));
+    }
+    nearest_reduce_kernel<<<(unsigned)cdiv(y.n, 256), 256, 0, st>>>(lists, q.NR, p.list_pitch, k, y.n, index, dist2);
     FAD_HIP_TRY(hipGetLastError());
     return FAD_OK;
 }
@@ -1762,6 +1915,73 @@ int fad_prdc(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, in
     out->density = (double)tot[1] / ((double)k * (double)m);
     out->recall = (double)tot[2] / (double)n;
     out->coverage = (double)tot[3] / (double)n;
+    out->n = n;
+    out->m = m;
+    out->k = k;
+    return FAD_OK;
+}
+
+int fad_nearest(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype, int on_device, int k,
+                int authenticity, int32_t* index, float* dist2, float* nn_radius2, fad_nearest_result_t* out, int device, void* stream) {
+    using namespace fad;
+    if (!out || !index || !dist2) return set_error(FAD_ERR_INVALID, "fad_nearest: NULL output");
+    if (k < 1 || k > kMaxK) return set_error(FAD_ERR_INVALID, "fad_nearest: k = %d is outside 1 .. %d", k, kMaxK);
+    if (!x || !y) return set_error(FAD_ERR_INVALID, "fad_nearest: NULL rows");
+    // dtype, d and ld as fad_kad checks them; the row counts are checked below
+    FAD_TRY(check_rows(x, std::max<int64_t>(n, 2), ldx, d, dtype, "fad_nearest (x)"));
+    FAD_TRY(check_rows(y, std::max<int64_t>(m, 2), ldy, d, dtype, "fad_nearest (y)"));
+    if (n < k || m < 1 || (authenticity && n < 2))
+        return set_error(FAD_ERR_TOO_FEW_ROWS, "fad_nearest: k = %d%s needs n >= %d and m >= 1, got n = %lld, m = %lld", k,
+                         authenticity ? " with authenticity" : "", authenticity ? std::max(k, 2) : k, (long long)n, (long long)m);
+    if (n > INT32_MAX - kTile || m > INT32_MAX - kTile)
+        return set_error(FAD_ERR_INVALID, "fad_nearest: %lld and %lld rows (at most %d per set)", (long long)n, (long long)m, INT32_MAX - kTile);
+    FAD_TRY(check_device(device));
+    DeviceGuard g(device);
+    if (!g.ok) return set_error(FAD_ERR_HIP, "hipSetDevice(%d) failed", device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    KadWorkspace& ws = workspace(device);
+
+    Packed px, py;
+    FAD_TRY(pack_set(0, x, n, ldx, d, dtype, on_device, st, ws, &px));
+    FAD_TRY(pack_set(1, y, m, ldy, d, dtype, on_device, st, ws, &py));
+    const PrdcPlan qc = prdc_plan(px, py, dtype, kad::kNearestEpilogue), qx = prdc_plan(px, px, dtype, kad::kTopkEpilogue);
+    const int64_t n_pad = qx.TJ * kTile, m_pad = qc.TJ * kTile;
+
+    // index | dist2 | radii x | nn radii | copied
+    size_t at[6];
+    at[0] = 0;
+    at[1] = at[0] + align256((size_t)(m * k) * sizeof(int32_t));
+    at[2] = at[1] + align256((size_t)(m * k) * sizeof(float));
+    at[3] = at[2] + align256((size_t)n_pad * sizeof(float));
+    at[4] = at[3] + align256((size_t)m * sizeof(float));
+    at[5] = at[4] + align256(sizeof(unsigned long long));
+    FAD_TRY(ws.near.reserve(at[5]));
+    // the radius pass's float lists, then (stream-ordered) the cross pass's keys in the same buffer
+    FAD_TRY(ws.lists.reserve(std::max((size_t)(qc.NR * m_pad * k) * sizeof(uint64_t),
+                                      authenticity ? (size_t)(qx.NR * n_pad) * sizeof(float) : (size_t)0)));
+    char* nb = static_cast<char*>(ws.near.p);
+    int32_t* index_d = reinterpret_cast<int32_t*>(nb + at[0]);
+    float* dist2_d = reinterpret_cast<float*>(nb + at[1]);
+    float* r2x = reinterpret_cast<float*>(nb + at[2]);
+    float* nn_r2 = reinterpret_cast<float*>(nb + at[3]);
+    unsigned long long* copied_d = reinterpret_cast<unsigned long long*>(nb + at[4]);
+
+    if (authenticity) FAD_TRY(radius_pass(px, 1, dtype, device, st, static_cast<float*>(ws.lists.p), r2x));
+    FAD_TRY(nearest_pass(px, py, k, dtype, device, st, static_cast<uint64_t*>(ws.lists.p), index_d, dist2_d));
+    unsigned long long copied = 0;
+    if (authenticity) {
+        FAD_HIP_TRY(hipMemsetAsync(copied_d, 0, sizeof(unsigned long long), st));
+        nearest_copied_kernel<<<(unsigned)cdiv(m, 256), 256, 0, st>>>(index_d, dist2_d, k, m, r2x, n, nn_r2, copied_d);
+        FAD_HIP_TRY(hipGetLastError());
+        FAD_HIP_TRY(hipMemcpyAsync(&copied, copied_d, sizeof(copied), hipMemcpyDeviceToHost, st));
+        if (nn_radius2) FAD_HIP_TRY(hipMemcpyAsync(nn_radius2, nn_r2, (size_t)m * sizeof(float), hipMemcpyDeviceToHost, st));
+    }
+    FAD_HIP_TRY(hipMemcpyAsync(index, index_d, (size_t)(m * k) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    FAD_HIP_TRY(hipMemcpyAsync(dist2, dist2_d, (size_t)(m * k) * sizeof(float), hipMemcpyDeviceToHost, st));
+    FAD_HIP_TRY(hipStreamSynchronize(st));
+
+    out->authenticity = authenticity ? 1.0 - (double)copied / (double)m : NAN;
+    out->copied = authenticity ? (int64_t)copied : -1;
     out->n = n;
     out->m = m;
     out->k = k;

@@ -82,8 +82,9 @@ inline std::vector<Launch> launches(int64_t total, int64_t per_launch, int64_t c
 // count in one bin, 28 ms (histogram) -- no launch holds the GPU anywhere near 100 ms, n = 10^6 cuts into tens of launches per pass.
 // PRDC's passes weigh their own epilogues: kTopkEpilogue for the radius pass's per-column top-k (a compare and a
 // wave-uniform skip per pair, a 16-step insertion where a value enters), kFlagEpilogue for the cross pass's two threshold tests, counts
-// and ballots per pair.
-constexpr int64_t kSumEpilogue = 128, kHistEpilogue = 2048, kTopkEpilogue = 1024, kFlagEpilogue = 512;
+// and ballots per pair.  fad_nearest's cross pass weighs kNearestEpilogue: the top-k of 64-bit keys, a permlane swap
+// per two pairs and a u64 compare per pair, six VALU ops per list entry where a key enters.
+constexpr int64_t kSumEpilogue = 128, kHistEpilogue = 2048, kTopkEpilogue = 1024, kFlagEpilogue = 512, kNearestEpilogue = 1536;
 KAD_HD inline int64_t tiles_per_launch_for(int64_t depth, bool f32, int64_t epilogue) {
     const int64_t cost = (f32 ? 16 * depth : depth) + epilogue;
     const int64_t t = ((int64_t)1 << 30) / cost;

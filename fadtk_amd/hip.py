@@ -888,3 +888,33 @@ def prdc(x, y, k: int = 5, device: int = 0, details: bool = False) -> dict:
     out = res.as_dict()
     out.update(arrays)
     return out
+
+
+# ------------------------------------------------------------------------ nearest baseline rows and authenticity (k-NN search)
+def nearest(x, y, k: int = 1, authenticity: bool = True, device: int = 0) -> dict:
+    """``fad_nearest``: the k nearest rows of x (baseline) to every row of y, ascending in (float32 d^2, index) -> dict of ``index``
+    [m, k] (int32), ``dist2`` [m, k] (float32 squared distances), ``nn_radius2`` [m] (float32 r1^2 of each row's nearest baseline row,
+    None without authenticity), ``authenticity`` (NaN without it), ``copied`` (-1 without it), ``n``, ``m`` and ``k``.  Both sets are
+    numpy arrays or both torch CUDA tensors of one dtype (float16 / bfloat16 / float32)."""
+    k = int(k)
+    if not 1 <= k <= PRDC_MAX_K:
+        raise ValueError(f"nearest: k must be in 1 .. {PRDC_MAX_K}, got {k}")
+    lib = K.load_library()
+    (px, n, d, ldx, cx, dev_x, kx), (py, m, dy, ldy, cy, dev_y, ky) = _kad_pair(x, y, "y", device)
+    if d != dy:
+        raise ValueError(f"nearest: x has D = {d}, y has D = {dy}")
+    if cx != cy:
+        raise ValueError("nearest: x and y must have the same dtype")
+    if n < k or m < 1 or (authenticity and n < 2):
+        raise ValueError(f"nearest with k = {k}{' and authenticity' if authenticity else ''} needs at least "
+                         f"{max(k, 2) if authenticity else k} baseline rows and 1 evaluation row, got {n} and {m}")
+    index = np.zeros((m, k), np.int32)
+    dist2 = np.zeros((m, k), np.float32)
+    nn_r2 = np.zeros(m, np.float32) if authenticity else None
+    res = K.FadNearestResult()
+    K.check(lib.fad_nearest(px, n, ldx, py, m, ldy, d, cx, dev_x, k, int(bool(authenticity)), index.ctypes.data, dist2.ctypes.data,
+                            nn_r2.ctypes.data if nn_r2 is not None else None, C.byref(res), int(device), K.current_stream_ptr(device)),
+            "fad_nearest")
+    out = res.as_dict()
+    out.update(index=index, dist2=dist2, nn_radius2=nn_r2)
+    return out

@@ -427,6 +427,28 @@ typedef struct fad_prdc_detail {
 int fad_prdc(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype,
              int on_device, int k, fad_prdc_result_t* out, fad_prdc_detail_t* detail /* may be NULL */, int device, void* stream);
 
+/* ------------------------------------------------------------------ nearest baseline rows and authenticity (k-NN search)
+ * Not in the reference.  For every evaluation row y_j (y [m x d]) its k nearest rows of the baseline x [n x d], 1 <= k <= 16, in
+ * ascending order of the key (d^2, i): d^2 is the float32 max(-2 S', 0) that fad_prdc's passes form (|x_i|^2 + |y_j|^2 - 2 x_i.y_j,
+ * products on the matrix cores), and equal d^2 are ordered by the smaller index i.  The result is fully determined: the same bits on
+ * every run.  index [m x k] (int32) and dist2 [m x k] (float32) are host arrays, row j holding y_j's list.
+ * Authenticity (Alaa et al. 2022, "How Faithful is your Synthetic Data?"), when `authenticity` is nonzero: nn(j) is index[j * k],
+ * r1^2(i) the squared distance from x_i to its nearest OTHER row of x (fad_prdc's radius with k = 1: self excluded by index, so a
+ * duplicate row gives 0); y_j is COPIED when dist2[j * k] <= r1^2(nn(j)).  The test is NON-strict, unlike fad_prdc's strict tests, so
+ * an exact copy of a baseline row always counts.  out->copied = the number of copied rows, out->authenticity = 1 - copied / m, and
+ * nn_radius2 [m] (host, may be NULL) = r1^2(nn(j)).  Without it the radius pass is skipped, authenticity is NaN, copied is -1 and
+ * nn_radius2 is not written.  Rows are float16, bfloat16 or float32, host or device per on_device, 1 <= d <= 2048, ld >= d,
+ * n, m < 2^31 - 128.  Argument errors come before any device call: k outside 1 .. 16, a NULL output or an unknown dtype ->
+ * FAD_ERR_INVALID; n < k, m < 1, or n < 2 with authenticity -> FAD_ERR_TOO_FEW_ROWS.  A NaN/Inf row norm -> FAD_ERR_NOT_FINITE.
+ * Work goes on `stream`; the call synchronises it. */
+typedef struct fad_nearest_result {
+    double authenticity;
+    int64_t n, m, k, copied;
+} fad_nearest_result_t;
+int fad_nearest(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype, int on_device,
+                int k, int authenticity, int32_t* index, float* dist2, float* nn_radius2 /* may be NULL */, fad_nearest_result_t* out,
+                int device, void* stream);
+
 /* ------------------------------------------------------------------ diagnostics (NOT part of the drop-in surface)
  * Nothing in fadtk corresponds to these two calls and no binding of the reference needs them: they exist for bench.py's
  * roofline object (HIP events around the tile kernel on the stream it is launched on) and for the GPU tests that check

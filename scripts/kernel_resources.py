@@ -23,6 +23,6 @@ for s in src:
             cur[k.split(" ")[0]] = v
         if k.startswith("LDS"):
             name = subprocess.run(["c++filt", cur["name"]], capture_output=True, text=True).stdout.strip()
-            name = re.sub(r"\(.*\)$", "", name)
+            name = re.sub(r"\(.*\)$", "", name.replace("(anonymous namespace)::", ""))
             if "anchor" in name or (want and not any(w in name for w in want)): continue
             print(f"{name} | {cur.get('VGPRs')} | {cur.get('AGPRs')} | {cur.get('ScratchSize')} | {cur.get('LDS')} | {cur.get('Occupancy')} | {s.name}")
