@@ -28,6 +28,7 @@ FAD_ERR_NOT_FINITE = -7
 FAD_ERR_NOT_CONVERGED = -8
 
 FAD_F16, FAD_BF16, FAD_F32, FAD_F64 = 0, 1, 2, 3
+FAD_KAD_GAUSSIAN, FAD_KAD_IQ, FAD_KAD_IMQ = 0, 1, 2      # fad_kad_kernel: the kernel argument of the fad_kad*_k entry points
 FAD_MEAN_SECOND_ONLY = 16     # | dtype: fad_frechet_from_moments' mean term with only the second mean rounded (include/fad_hip.h)
 
 LIB_PATH = Path(__file__).resolve().parent / "lib" / "libfad_hip.so"
@@ -134,6 +135,14 @@ SIGNATURES = {
                                       C.c_double, C.POINTER(FadKadResult), _P, _P, _P, C.c_int, _P]),
     "fad_kad_permutation_test": (C.c_int, [_P, _I64, _I64, _P, _I64, _I64, _I64, C.c_int, C.c_int, C.c_double, _P, _I64, C.c_int,
                                            C.POINTER(FadKadResult), _P, C.POINTER(C.c_double), C.c_int, _P]),
+    "fad_kad_k": (C.c_int, [_P, _I64, _I64, _P, _I64, _I64, _I64, C.c_int, C.c_int, C.c_double, C.c_int, C.POINTER(FadKadResult),
+                            C.c_int, _P]),
+    "fad_kad_individual_k": (C.c_int, [_P, _I64, _I64, _P, _I64, _I64, C.POINTER(_I64), _I64, _I64, C.c_int, C.c_int, C.c_double, C.c_int,
+                                       C.POINTER(FadKadResult), _P, _P, _P, _P, C.c_int, _P]),
+    "fad_kad_uncertainty_k": (C.c_int, [_P, _I64, _I64, C.POINTER(_P), C.POINTER(_I64), C.POINTER(_I64), C.c_int, _I64, C.c_int, C.c_int,
+                                        C.c_double, C.c_int, C.POINTER(FadKadResult), _P, _P, _P, C.c_int, _P]),
+    "fad_kad_permutation_test_k": (C.c_int, [_P, _I64, _I64, _P, _I64, _I64, _I64, C.c_int, C.c_int, C.c_double, C.c_int, _P, _I64,
+                                             C.c_int, C.POINTER(FadKadResult), _P, C.POINTER(C.c_double), C.c_int, _P]),
     "fad_prdc": (C.c_int, [_P, _I64, _I64, _P, _I64, _I64, _I64, C.c_int, C.c_int, C.c_int, C.POINTER(FadPrdcResult),
                            C.POINTER(FadPrdcDetail), C.c_int, _P]),
     "fad_nearest": (C.c_int, [_P, _I64, _I64, _P, _I64, _I64, _I64, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P,

@@ -13,6 +13,8 @@
 //             bitwise the same result on every run (no float atomics);
 //   - median: the same walk over the baseline's triangle with a histogram epilogue -- an exact radix select on the bit patterns
 //             of the clamped float32 d^2 (11 / 11 / 10 bits, LDS histograms, integer global counts).
+// The _k entry points take the kernel: FAD_KAD_GAUSSIAN as above, or the heavy-tailed FAD_KAD_IQ k = 1 / (1 + t) and FAD_KAD_IMQ
+// k = 1 / sqrt(1 + t), t = d^2 / (2 sigma^2) = -c S' with c = 1 / sigma^2 -- a compile-time parameter of the epilogues (kernel_value).
 // The cross pass always runs with the larger set (by rows, then by sum of row norms) as the row operand, so that swapping the
 // arguments adds exactly the same tile sums.  KAD's code object is loaded at its first call, not by check_device's warm-up.
 #include "fad_common.h"
@@ -50,7 +52,7 @@ struct PassArgs {
     int64_t pitch, n_a, n_b;                   // n_b == n_a for a triangle
     int64_t u0, cnt, tiles_j;                  // launch's tiles [u0, u0 + cnt); triangle: T, rectangle: TJ
     int tri, nchunks;
-    float c;                                   // log2(e) / sigma^2 (MODE_SUM)
+    float c;                                   // log2(e) / sigma^2, 1 / sigma^2 for iq and imq (MODE_SUM)
     double* slots;                             // MODE_SUM: one per workgroup of the launch
     unsigned long long* hist;                  // MODE_HIST: [2][kHistBins] integer counts
     unsigned int pref0, pref1; int two, hi_shift, lo_shift, bits;
@@ -101,8 +103,29 @@ __device__ __forceinline__ void chunk_mfma(const char* la, const char* lb, int l
     }
 }
 
+// k(S') of one accumulator element, KF one of FAD_KAD_*.  Three instructions either way: mul / min / exp2, or fma / max / rcp (rsq).
+template <int KF>
+__device__ __forceinline__ float kernel_value(float acc, float c) {
+    if constexpr (KF == FAD_KAD_GAUSSIAN) {
+        // c > 0, so min(S', 0) * c == min(S' * c, 0).  The multiply is an ordinary VALU op that reads the MFMA result, so the
+        // compiler places the MFMA -> VALU wait states before it; the clamp then reads only that VALU result.  (An inline-asm read
+        // of the accumulator itself would get no wait states: the hazard recognizer does not look inside asm.)  The clamp is asm so
+        // that no canonicalising v_max comes with it.
+        float v = acc * c, w;
+        asm("v_min_f32 %0, 0, %1" : "=v"(w) : "v"(v));
+        return __builtin_amdgcn_exp2f(w);
+    } else {
+        // u = 1 + t, t = -c S' >= 0 up to rounding; the same two properties: the fma is the ordinary op that reads the MFMA result, the
+        // clamp to u >= 1 is asm on the fma's result.  A padding row's -inf gives u = +inf and k = 0; a NaN clamps to 1, so k = 1 (as
+        // the Gaussian's min does).
+        float u = fmaf(acc, -c, 1.0f), w;
+        asm("v_max_f32 %0, 1.0, %1" : "=v"(w) : "v"(u));
+        return KF == FAD_KAD_IQ ? __builtin_amdgcn_rcpf(w) : __builtin_amdgcn_rsqf(w);
+    }
+}
+
 // k(S') summed over the wave's 64 x 64 pairs of a tile; MASK: a diagonal tile of a triangle counts only column > row
-template <bool MASK>
+template <bool MASK, int KF>
 __device__ __forceinline__ float tile_sum(const f32x16 (&acc)[2][2], float c, int rbase, int cbase, int lane) {
     // The row offset of the lane, opaque to the compiler: the 64 mask comparisons are made here, per diagonal tile, instead of being
     // hoisted out of the tile loop as 64 lane masks (128 SGPRs, spilled to VGPR lanes around the whole loop).
@@ -115,13 +138,7 @@ __device__ __forceinline__ float tile_sum(const f32x16 (&acc)[2][2], float c, in
         for (int bj = 0; bj < 2; ++bj)
 #pragma unroll
             for (int g = 0; g < 16; ++g) {
-                // c > 0, so min(S', 0) * c == min(S' * c, 0).  The multiply is an ordinary VALU op that reads the MFMA result, so the
-                // compiler places the MFMA -> VALU wait states before it; the clamp then reads only that VALU result.  (An inline-asm read
-                // of the accumulator itself would get no wait states: the hazard recognizer does not look inside asm.)  The clamp is asm so
-                // that no canonicalising v_max comes with it.
-                float v = acc[bi][bj][g] * c, w;
-                asm("v_min_f32 %0, 0, %1" : "=v"(w) : "v"(v));
-                float e = __builtin_amdgcn_exp2f(w);
+                float e = kernel_value<KF>(acc[bi][bj][g], c);
                 if (MASK) e = (bj * 32 - bi * 32 - (g & 3) - 8 * (g >> 2)) > lrow ? e : 0.f;     // column > row
                 s += e;
             }
@@ -187,7 +204,7 @@ __device__ __forceinline__ void tile_mfma(const char* a, const char* b, const fl
     }
 }
 
-template <int DT, int MODE>
+template <int DT, int MODE, int KF = FAD_KAD_GAUSSIAN>
 __global__ void __launch_bounds__(kThreads, 2) kad_pass_kernel(PassArgs p) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     unsigned int* lhist = reinterpret_cast<unsigned int*>(lds + 2 * kOpBytes + 2 * kTile * 4);   // MODE_HIST: [2][kHistBins]
@@ -210,7 +227,7 @@ __global__ void __launch_bounds__(kThreads, 2) kad_pass_kernel(PassArgs p) {
 
         const int rbase = wm * 64, cbase = wn * 64;
         if (MODE == MODE_SUM) {
-            const float s = (p.tri && t.I == t.J) ? tile_sum<true>(acc, p.c, rbase, cbase, lane) : tile_sum<false>(acc, p.c, rbase, cbase, lane);
+            const float s = (p.tri && t.I == t.J) ? tile_sum<true, KF>(acc, p.c, rbase, cbase, lane) : tile_sum<false, KF>(acc, p.c, rbase, cbase, lane);
             dsum += (double)s;
         } else {
             const uint64_t mask = (1ull << p.bits) - 1;
@@ -314,7 +331,7 @@ struct ColArgs {
     const float* ha; const float* hb;
     int64_t pitch;
     int nchunks;
-    float c;                                   // log2(e) / sigma^2
+    float c;                                   // log2(e) / sigma^2, 1 / sigma^2 for iq and imq
     int64_t u0, cnt;                           // the launch's units [u0, u0 + cnt)
     int64_t TI, TJ, rr;                        // cross: the unit map
     const kad::Unit* units;                    // band: (J, I0, I1) per unit
@@ -326,7 +343,7 @@ struct ColArgs {
 // diagonal tile (column > row), 2: a band tile holding more than one song (column < end of the row's song, and on a diagonal tile
 // column > row), 3: a diagonal tile of a full square (column != row).  Masks are selects: a NaN row that the clamp turned into k = 1
 // still adds nothing where it is masked.
-template <int MASK>
+template <int MASK, int KF>
 __device__ __forceinline__ void col_sums(const f32x16 (&acc)[2][2], float c, int rbase, int cbase, int lane, const int* lend, bool diag,
                                          double (&dcol)[2]) {
     int lrow = rbase + 4 * (lane >> 5), lcol = cbase + (lane & 31);
@@ -345,9 +362,7 @@ __device__ __forceinline__ void col_sums(const f32x16 (&acc)[2][2], float c, int
         for (int bi = 0; bi < 2; ++bi)
 #pragma unroll
             for (int g = 0; g < 16; ++g) {
-                float v = acc[bi][bj][g] * c, w;                  // as tile_sum: the MFMA result read by ordinary code, the clamp in asm
-                asm("v_min_f32 %0, 0, %1" : "=v"(w) : "v"(v));
-                float e = __builtin_amdgcn_exp2f(w);
+                float e = kernel_value<KF>(acc[bi][bj][g], c);    // as tile_sum
                 const int r = lrow + bi * 32 + (g & 3) + 8 * (g >> 2), col = lcol + bj * 32;
                 if (MASK == 1) e = col > r ? e : 0.f;
                 if (MASK == 2) e = (col < le[bi][g >> 2][g & 3] && (!diag || col > r)) ? e : 0.f;
@@ -358,7 +373,7 @@ __device__ __forceinline__ void col_sums(const f32x16 (&acc)[2][2], float c, int
     }
 }
 
-template <int DT, bool BAND>
+template <int DT, bool BAND, int KF>
 __global__ void __launch_bounds__(kThreads, 2) kad_cols_kernel(ColArgs p) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     int* lend = reinterpret_cast<int*>(lds + 2 * kOpBytes + 2 * kTile * 4);           // BAND: end of each row's song - J * 128, in [0, 128]
@@ -388,13 +403,13 @@ __global__ void __launch_bounds__(kThreads, 2) kad_cols_kernel(ColArgs p) {
             if (BAND) {
                 const bool diag = I == un.J;
                 if (lend[0] >= kTile) {                                               // the tile lies inside one song (uniform)
-                    if (diag) col_sums<1>(acc, p.c, rbase, cbase, lane, lend, true, dcol);
-                    else col_sums<0>(acc, p.c, rbase, cbase, lane, lend, false, dcol);
+                    if (diag) col_sums<1, KF>(acc, p.c, rbase, cbase, lane, lend, true, dcol);
+                    else col_sums<0, KF>(acc, p.c, rbase, cbase, lane, lend, false, dcol);
                 } else {
-                    col_sums<2>(acc, p.c, rbase, cbase, lane, lend, diag, dcol);
+                    col_sums<2, KF>(acc, p.c, rbase, cbase, lane, lend, diag, dcol);
                 }
             } else {
-                col_sums<0>(acc, p.c, rbase, cbase, lane, lend, false, dcol);
+                col_sums<0, KF>(acc, p.c, rbase, cbase, lane, lend, false, dcol);
             }
         }
 
@@ -474,7 +489,7 @@ __global__ void __launch_bounds__(256) kad_song_reduce_kernel(const double* __re
 // column != row on a diagonal one -- one float64 slot per (unit, column).  Then four small float64 kernels, each in a fixed order:
 // the row sums and projections a, b per row of Z; per-set means and the spread of b; the centred cross products of a in partial sums
 // over fixed row ranges; those partials summed.
-template <int DT>
+template <int DT, int KF>
 __global__ void __launch_bounds__(kThreads, 2) kad_unc_cols_kernel(ColArgs p) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     double* lx = reinterpret_cast<double*>(lds + 2 * kOpBytes + 2 * kTile * 4);       // the wm = 1 waves' column sums of a unit
@@ -494,8 +509,8 @@ __global__ void __launch_bounds__(kThreads, 2) kad_unc_cols_kernel(ColArgs p) {
         for (int64_t I = un.I0; I < un.I1; ++I) {
             f32x16 acc[2][2];
             tile_mfma<DT>(p.a, p.b, p.ha, p.hb, p.pitch, p.nchunks, I, un.J, lds, [](int) {}, acc);
-            if (I == un.J) col_sums<3>(acc, p.c, rbase, cbase, lane, nullptr, true, dcol);
-            else col_sums<0>(acc, p.c, rbase, cbase, lane, nullptr, false, dcol);
+            if (I == un.J) col_sums<3, KF>(acc, p.c, rbase, cbase, lane, nullptr, true, dcol);
+            else col_sums<0, KF>(acc, p.c, rbase, cbase, lane, nullptr, false, dcol);
         }
 
         // a column: the two lane halves, then the wm = 0 and wm = 1 waves, in this order (kad_cols_kernel)
@@ -669,7 +684,7 @@ struct PermArgs {
     const char* z; const float* h;             // Z's image and -|row|^2 / 2 (-inf on the padding rows)
     int64_t pitch;
     int nchunks, nw;                           // nw: words of the launch's group
-    float c, c0;                               // log2(e) / sigma^2, the shift
+    float c, c0;                               // log2(e) / sigma^2 (1 / sigma^2 for iq and imq), the shift
     int64_t TZ, u0, cnt;                       // the triangle and the launch's tiles [u0, u0 + cnt)
     const uint32_t* rowbits;                   // the group's row words: [nw][NWZ][32] (kad_perm_rowbits_kernel)
     const uint32_t* colbits;                   // the group's column words: [nw][z_pad] (kad_perm_colbits_kernel)
@@ -677,7 +692,7 @@ struct PermArgs {
     double* slots;                             // the group's slots: [group slots][32 nw], added into
 };
 
-template <int DT>
+template <int DT, int KF>
 __global__ void __launch_bounds__(kThreads, 2) kad_perm_kernel(PermArgs p) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -707,9 +722,7 @@ __global__ void __launch_bounds__(kThreads, 2) kad_perm_kernel(PermArgs p) {
             for (int bj = 0; bj < 2; ++bj)
 #pragma unroll
                 for (int g = 0; g < 16; ++g) {
-                    float x = acc[bi][bj][g] * p.c, w;                                // as tile_sum: the clamp in asm
-                    asm("v_min_f32 %0, 0, %1" : "=v"(w) : "v"(x));
-                    float e = __builtin_amdgcn_exp2f(w) - p.c0;
+                    float e = kernel_value<KF>(acc[bi][bj][g], p.c) - p.c0;           // as tile_sum
                     if (diag) e = (bj * 32 - bi * 32 - (g & 3) - 8 * (g >> 2)) > lrow ? e : 0.f;
                     af[bi][bj][g >> 3][g & 7] = (_Float16)e;
                 }
@@ -1360,6 +1373,22 @@ static int with_dtype(int dtype, F&& f) {
     return FAD_OK;
 }
 
+// f(dt, std::integral_constant<int, KF>{}) for the rows' dtype and the kernel (one of FAD_KAD_*, checked by check_kernel)
+template <typename F>
+static int with_dtype_kernel(int dtype, int kernel, F&& f) {
+    switch (kernel) {
+        case FAD_KAD_IQ: return with_dtype(dtype, [&](auto dt) { f(dt, std::integral_constant<int, FAD_KAD_IQ>{}); });
+        case FAD_KAD_IMQ: return with_dtype(dtype, [&](auto dt) { f(dt, std::integral_constant<int, FAD_KAD_IMQ>{}); });
+        default: return with_dtype(dtype, [&](auto dt) { f(dt, std::integral_constant<int, FAD_KAD_GAUSSIAN>{}); });
+    }
+}
+
+static int check_kernel(int kernel, const char* who) {
+    if (kernel != FAD_KAD_GAUSSIAN && kernel != FAD_KAD_IQ && kernel != FAD_KAD_IMQ)
+        return set_error(FAD_ERR_INVALID, "%s: unknown kernel %d (FAD_KAD_GAUSSIAN = 0, FAD_KAD_IQ = 1, FAD_KAD_IMQ = 2)", who, kernel);
+    return FAD_OK;
+}
+
 // the rows of `a` against those of `b`, over the triangle (tri: b is a) or the rectangle; each launch sets u0 and cnt
 static PassArgs pass_args(const Packed& a, const Packed& b, bool tri, float c) {
     PassArgs p{};
@@ -1417,7 +1446,7 @@ static int median_of_packed(const Packed& x, int dtype, int device, hipStream_t 
 // N sum passes into consecutive slot ranges, then sums_d[q] = pass q's slots summed in a fixed order (enqueued, not read back).
 // fad_kad runs XX, YY and XY; fad_kad_individual XX alone, so its Kxx comes from the same launches, slots and sum as fad_kad's.
 template <int N>
-static int sum_passes(const PassArgs (&passes)[N], int dtype, int device, hipStream_t st, KadWorkspace& ws, double* sums_d) {
+static int sum_passes(const PassArgs (&passes)[N], int dtype, int kernel, int device, hipStream_t st, KadWorkspace& ws, double* sums_d) {
     std::vector<kad::Launch> launches[N];
     int64_t off[N + 1] = {0};
     for (int q = 0; q < N; ++q) {
@@ -1433,7 +1462,9 @@ static int sum_passes(const PassArgs (&passes)[N], int dtype, int device, hipStr
         p.slots = static_cast<double*>(ws.slots.p) + off[q];
         for (const kad::Launch& l : launches[q]) {
             p.u0 = l.u0; p.cnt = l.cnt;
-            FAD_TRY(with_dtype(dtype, [&](auto dt) { kad_pass_kernel<dt, MODE_SUM><<<(unsigned)l.grid, kThreads, kLdsSum, st>>>(p); }));
+            FAD_TRY(with_dtype_kernel(dtype, kernel, [&](auto dt, auto kf) {
+                kad_pass_kernel<dt, MODE_SUM, kf><<<(unsigned)l.grid, kThreads, kLdsSum, st>>>(p);
+            }));
             p.slots += l.grid;
         }
     }
@@ -1442,15 +1473,16 @@ static int sum_passes(const PassArgs (&passes)[N], int dtype, int device, hipStr
     return FAD_OK;
 }
 
-// sigma = `bandwidth`, or the median pairwise distance of x when it is 0, and c = log2(e) / sigma^2 as the kernels' float32
-static int resolve_sigma(const Packed& x, double bandwidth, int dtype, int device, hipStream_t st, KadWorkspace& ws, const char* who,
+// sigma = `bandwidth`, or the median pairwise distance of x when it is 0, and c = log2(e) / sigma^2 (1 / sigma^2 for iq and imq, whose
+// epilogue takes t = c d^2 / 2 itself) as the kernels' float32
+static int resolve_sigma(const Packed& x, double bandwidth, int kernel, int dtype, int device, hipStream_t st, KadWorkspace& ws, const char* who,
                          double* sigma, float* c) {
     *sigma = bandwidth;
     if (!(*sigma > 0)) FAD_TRY(median_of_packed(x, dtype, device, st, ws, sigma));
     if (!(*sigma > 0) || !std::isfinite(*sigma))
         return set_error(FAD_ERR_INVALID, "%s: bandwidth %g (the median pairwise distance of the baseline when none is given) must be > 0"
                          " -- are all baseline rows identical?", who, *sigma);
-    const double cd = 1.4426950408889634 / (*sigma * *sigma);
+    const double cd = (kernel == FAD_KAD_GAUSSIAN ? 1.4426950408889634 : 1.0) / (*sigma * *sigma);
     if (!(cd > 0) || !std::isfinite(cd) || !std::isfinite((float)cd) || (float)cd == 0.f)
         return set_error(FAD_ERR_INVALID, "%s: bandwidth %g is outside the float32 range of the kernel", who, *sigma);
     *c = (float)cd;
@@ -1530,8 +1562,14 @@ int fad_kad_median_distance(const void* x, int64_t n, int64_t ld, int64_t d, int
 
 int fad_kad(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype, int on_device,
             double bandwidth, fad_kad_result_t* out, int device, void* stream) {
+    return fad_kad_k(x, n, ldx, y, m, ldy, d, dtype, on_device, bandwidth, FAD_KAD_GAUSSIAN, out, device, stream);
+}
+
+int fad_kad_k(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype, int on_device,
+              double bandwidth, int kernel, fad_kad_result_t* out, int device, void* stream) {
     using namespace fad;
     if (!out) return set_error(FAD_ERR_INVALID, "fad_kad: NULL output");
+    FAD_TRY(check_kernel(kernel, "fad_kad"));
     FAD_TRY(check_rows(x, n, ldx, d, dtype, "fad_kad (x)"));
     FAD_TRY(check_rows(y, m, ldy, d, dtype, "fad_kad (y)"));
     if (std::isnan(bandwidth) || std::isinf(bandwidth))
@@ -1547,14 +1585,14 @@ int fad_kad(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int
     FAD_TRY(pack_set(1, y, m, ldy, d, dtype, on_device, st, ws, &py));
     double sigma;
     float c;
-    FAD_TRY(resolve_sigma(px, bandwidth, dtype, device, st, ws, "fad_kad", &sigma, &c));
+    FAD_TRY(resolve_sigma(px, bandwidth, kernel, dtype, device, st, ws, "fad_kad", &sigma, &c));
 
     // passes: XX and YY over their triangles, XY over the rectangle with the larger set as the row operand
     const bool x_rows = n != m ? n > m : px.norm_sum >= py.norm_sum;
     const PassArgs passes[3] = {pass_args(px, px, true, c), pass_args(py, py, true, c),
                                 pass_args(x_rows ? px : py, x_rows ? py : px, false, c)};
     double* sums_d = static_cast<double*>(ws.small.p) + 16;
-    FAD_TRY(sum_passes(passes, dtype, device, st, ws, sums_d));
+    FAD_TRY(sum_passes(passes, dtype, kernel, device, st, ws, sums_d));
     double sums[3];
     FAD_HIP_TRY(hipMemcpyAsync(sums, sums_d, sizeof(sums), hipMemcpyDeviceToHost, st));
     FAD_HIP_TRY(hipStreamSynchronize(st));
@@ -1573,8 +1611,16 @@ int fad_kad(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int
 int fad_kad_individual(const void* x, int64_t n, int64_t ldx, const void* rows, int64_t n_rows, int64_t ldy, const int64_t* offsets,
                        int64_t n_songs, int64_t d, int dtype, int on_device, double bandwidth, fad_kad_result_t* base, double* out_mmd2,
                        double* out_kyy_mean, double* out_kxy_mean, int32_t* out_status, int device, void* stream) {
+    return fad_kad_individual_k(x, n, ldx, rows, n_rows, ldy, offsets, n_songs, d, dtype, on_device, bandwidth, FAD_KAD_GAUSSIAN, base,
+                                out_mmd2, out_kyy_mean, out_kxy_mean, out_status, device, stream);
+}
+
+int fad_kad_individual_k(const void* x, int64_t n, int64_t ldx, const void* rows, int64_t n_rows, int64_t ldy, const int64_t* offsets,
+                         int64_t n_songs, int64_t d, int dtype, int on_device, double bandwidth, int kernel, fad_kad_result_t* base,
+                         double* out_mmd2, double* out_kyy_mean, double* out_kxy_mean, int32_t* out_status, int device, void* stream) {
     using namespace fad;
     if (!base) return set_error(FAD_ERR_INVALID, "fad_kad_individual: NULL output");
+    FAD_TRY(check_kernel(kernel, "fad_kad_individual"));
     FAD_TRY(check_rows(x, n, ldx, d, dtype, "fad_kad_individual (x)"));
     if (n_songs < 0 || n_songs > INT32_MAX) return set_error(FAD_ERR_INVALID, "fad_kad_individual: %lld songs", (long long)n_songs);
     if (!offsets || (n_songs > 0 && (!out_mmd2 || !out_kyy_mean || !out_kxy_mean || !out_status)))
@@ -1601,10 +1647,10 @@ int fad_kad_individual(const void* x, int64_t n, int64_t ldx, const void* rows, 
     FAD_TRY(pack_set(0, x, n, ldx, d, dtype, on_device, st, ws, &px));
     double sigma;
     float c;
-    FAD_TRY(resolve_sigma(px, bandwidth, dtype, device, st, ws, "fad_kad_individual", &sigma, &c));
+    FAD_TRY(resolve_sigma(px, bandwidth, kernel, dtype, device, st, ws, "fad_kad_individual", &sigma, &c));
     const PassArgs xx[1] = {pass_args(px, px, true, c)};
     double* sxx_d = static_cast<double*>(ws.small.p) + 16;
-    FAD_TRY(sum_passes(xx, dtype, device, st, ws, sxx_d));
+    FAD_TRY(sum_passes(xx, dtype, kernel, device, st, ws, sxx_d));
 
     // the songs: cross pass (X x Y) and band pass (pairs inside each song), per-column slots, one reduction per song
     if (n_rows > 0 && n_songs > 0) {
@@ -1651,13 +1697,17 @@ int fad_kad_individual(const void* x, int64_t n, int64_t ldx, const void* rows, 
         p.slots = static_cast<double*>(ws.cross.p); p.slot_pitch = m_pad;
         for (const kad::Launch& l : kad::launches(NR * TJ, kad::units_per_launch(rr, depth, f32), grid_cap(device))) {
             p.u0 = l.u0; p.cnt = l.cnt;
-            FAD_TRY(with_dtype(dtype, [&](auto dt) { kad_cols_kernel<dt, false><<<(unsigned)l.grid, kThreads, kLdsCols, st>>>(p); }));
+            FAD_TRY(with_dtype_kernel(dtype, kernel, [&](auto dt, auto kf) {
+                kad_cols_kernel<dt, false, kf><<<(unsigned)l.grid, kThreads, kLdsCols, st>>>(p);
+            }));
         }
         p.a = py.img; p.ha = py.h; p.units = bunits_d; p.row_end = row_end_d;
         p.slots = static_cast<double*>(ws.band.p); p.slot_pitch = kTile;
         for (const kad::Launch& l : kad::launches(U, kad::units_per_launch(kad::kBandPiece, depth, f32), grid_cap(device))) {
             p.u0 = l.u0; p.cnt = l.cnt;
-            FAD_TRY(with_dtype(dtype, [&](auto dt) { kad_cols_kernel<dt, true><<<(unsigned)l.grid, kThreads, kLdsCols, st>>>(p); }));
+            FAD_TRY(with_dtype_kernel(dtype, kernel, [&](auto dt, auto kf) {
+                kad_cols_kernel<dt, true, kf><<<(unsigned)l.grid, kThreads, kLdsCols, st>>>(p);
+            }));
         }
         kad_song_reduce_kernel<<<(unsigned)n_songs, 256, 0, st>>>(static_cast<const double*>(ws.cross.p), NR, m_pad,
                                                                   static_cast<const double*>(ws.band.p), bstart_d, py.h, off_d, (double)n,
@@ -1689,8 +1739,16 @@ int fad_kad_individual(const void* x, int64_t n, int64_t ldx, const void* rows, 
 int fad_kad_uncertainty(const void* x, int64_t n, int64_t ldx, const void* const* ys, const int64_t* ms, const int64_t* ldys, int n_sets,
                         int64_t d, int dtype, int on_device, double bandwidth, fad_kad_result_t* out, double* cov, double* proj_x,
                         double* proj_y, int device, void* stream) {
+    return fad_kad_uncertainty_k(x, n, ldx, ys, ms, ldys, n_sets, d, dtype, on_device, bandwidth, FAD_KAD_GAUSSIAN, out, cov, proj_x, proj_y,
+                                 device, stream);
+}
+
+int fad_kad_uncertainty_k(const void* x, int64_t n, int64_t ldx, const void* const* ys, const int64_t* ms, const int64_t* ldys, int n_sets,
+                          int64_t d, int dtype, int on_device, double bandwidth, int kernel, fad_kad_result_t* out, double* cov,
+                          double* proj_x, double* proj_y, int device, void* stream) {
     using namespace fad;
     if (!out || !cov) return set_error(FAD_ERR_INVALID, "fad_kad_uncertainty: NULL output");
+    FAD_TRY(check_kernel(kernel, "fad_kad_uncertainty"));
     if (n_sets < 1 || n_sets > kad::kUncMaxSets)
         return set_error(FAD_ERR_INVALID, "fad_kad_uncertainty: %d evaluation sets (1 .. %d)", n_sets, kad::kUncMaxSets);
     if (!ys || !ms || !ldys) return set_error(FAD_ERR_INVALID, "fad_kad_uncertainty: NULL set table");
@@ -1757,7 +1815,7 @@ int fad_kad_uncertainty(const void* x, int64_t n, int64_t ldx, const void* const
     const Packed px{zimg, zh, n, pitch, (int)(pitch / kChunk), info[0]};
     double sigma;
     float c;
-    FAD_TRY(resolve_sigma(px, bandwidth, dtype, device, st, ws, "fad_kad_uncertainty", &sigma, &c));
+    FAD_TRY(resolve_sigma(px, bandwidth, kernel, dtype, device, st, ws, "fad_kad_uncertainty", &sigma, &c));
 
     // the pass: units, slots and per-row tables
     const bool f32 = dtype == FAD_F32;
@@ -1803,7 +1861,9 @@ int fad_kad_uncertainty(const void* x, int64_t n, int64_t ldx, const void* const
     p.units = units_d; p.slots = slots; p.slot_pitch = kTile;
     for (const kad::Launch& l : kad::launches(U, kad::unc_units_per_launch(rr, dp, f32), grid_cap(device))) {
         p.u0 = l.u0; p.cnt = l.cnt;
-        FAD_TRY(with_dtype(dtype, [&](auto dt) { kad_unc_cols_kernel<dt><<<(unsigned)l.grid, kThreads, kLdsUnc, st>>>(p); }));
+        FAD_TRY(with_dtype_kernel(dtype, kernel, [&](auto dt, auto kf) {
+            kad_unc_cols_kernel<dt, kf><<<(unsigned)l.grid, kThreads, kLdsUnc, st>>>(p);
+        }));
     }
     kad_unc_rows_kernel<<<(unsigned)cdiv(z_pad, 256), 256, 0, st>>>(slots, seg_d, q, a_d, b_d, rxx_d, ryy_d, ryx_d);
     FAD_HIP_TRY(hipGetLastError());
@@ -1991,8 +2051,16 @@ int fad_nearest(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m,
 int fad_kad_permutation_test(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype,
                              int on_device, double bandwidth, const uint32_t* labels, int64_t n_perm, int labels_on_device,
                              fad_kad_result_t* observed, double* null_out, double* p_value, int device, void* stream) {
+    return fad_kad_permutation_test_k(x, n, ldx, y, m, ldy, d, dtype, on_device, bandwidth, FAD_KAD_GAUSSIAN, labels, n_perm,
+                                      labels_on_device, observed, null_out, p_value, device, stream);
+}
+
+int fad_kad_permutation_test_k(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype,
+                               int on_device, double bandwidth, int kernel, const uint32_t* labels, int64_t n_perm, int labels_on_device,
+                               fad_kad_result_t* observed, double* null_out, double* p_value, int device, void* stream) {
     using namespace fad;
     if (!observed || !null_out || !p_value) return set_error(FAD_ERR_INVALID, "fad_kad_permutation_test: NULL output");
+    FAD_TRY(check_kernel(kernel, "fad_kad_permutation_test"));
     FAD_TRY(check_rows(x, n, ldx, d, dtype, "fad_kad_permutation_test (x)"));
     FAD_TRY(check_rows(y, m, ldy, d, dtype, "fad_kad_permutation_test (y)"));
     if (n_perm < 1 || n_perm > kad::kPermMax)
@@ -2092,7 +2160,7 @@ int fad_kad_permutation_test(const void* x, int64_t n, int64_t ldx, const void* 
     const Packed pz{zimg, zh, N, pitch, (int)(pitch / kChunk), info[0]};
     double sigma;
     float c;
-    FAD_TRY(resolve_sigma(pz, bandwidth, dtype, device, st, ws, "fad_kad_permutation_test", &sigma, &c));
+    FAD_TRY(resolve_sigma(pz, bandwidth, kernel, dtype, device, st, ws, "fad_kad_permutation_test", &sigma, &c));
 
     // r = K'1 and T = 1'r: kad_unc_cols_kernel's walk over Z x Z (one set, kad_unc_tiles.h), float32 kernel values
     const bool f32 = dtype == FAD_F32;
@@ -2144,7 +2212,9 @@ int fad_kad_permutation_test(const void* x, int64_t n, int64_t ldx, const void* 
     ca.units = units_d; ca.slots = static_cast<double*>(ws.unc_slots.p); ca.slot_pitch = kTile;
     for (const kad::Launch& l : kad::launches(U, kad::unc_units_per_launch(rr, dp, f32), grid_cap(device))) {
         ca.u0 = l.u0; ca.cnt = l.cnt;
-        FAD_TRY(with_dtype(dtype, [&](auto dt) { kad_unc_cols_kernel<dt><<<(unsigned)l.grid, kThreads, kLdsUnc, st>>>(ca); }));
+        FAD_TRY(with_dtype_kernel(dtype, kernel, [&](auto dt, auto kf) {
+            kad_unc_cols_kernel<dt, kf><<<(unsigned)l.grid, kThreads, kLdsUnc, st>>>(ca);
+        }));
     }
     kad_perm_rows_kernel<<<(unsigned)cdiv(z_pad, 256), 256, 0, st>>>(ca.slots, seg_d, N, z_pad, r_d);
     FAD_HIP_TRY(hipGetLastError());
@@ -2154,9 +2224,11 @@ int fad_kad_permutation_test(const void* x, int64_t n, int64_t ldx, const void* 
     FAD_HIP_TRY(hipMemcpyAsync(&T, tot_d, sizeof(double), hipMemcpyDeviceToHost, st));
     FAD_HIP_TRY(hipStreamSynchronize(st));
 
-    // the shift: the kernel value at the median distance (e^-1/2) under the default sigma; the mean off-diagonal kernel value of Z
-    // under a given one.  Any constant gives the same t; it sets how much of each kernel value f16 keeps.
-    const float c0 = bandwidth > 0 ? (float)(T / ((double)N * (double)(N - 1))) : 0.60653065971263342f;
+    // the shift: the kernel value at the median distance (t = 1/2: e^-1/2, 2/3 for iq, 1 / sqrt(1.5) for imq) under the default sigma;
+    // the mean off-diagonal kernel value of Z under a given one.  Any constant gives the same t; it sets how much of each kernel value
+    // f16 keeps.
+    const float at_median = kernel == FAD_KAD_IQ ? 0.66666666666666663f : kernel == FAD_KAD_IMQ ? 0.81649658092772603f : 0.60653065971263342f;
+    const float c0 = bandwidth > 0 ? (float)(T / ((double)N * (double)(N - 1))) : at_median;
 
     FAD_HIP_TRY(hipMemsetAsync(pslots, 0, (size_t)nslot_doubles * sizeof(double), st));
     PermArgs pa{};
@@ -2167,7 +2239,9 @@ int fad_kad_permutation_test(const void* x, int64_t n, int64_t ldx, const void* 
         pa.rowbits = rows_d + l.w0 * z_pad;
         pa.colbits = cols_d + l.w0 * z_pad;
         pa.slots = pslots + gr.slot_off;
-        FAD_TRY(with_dtype(dtype, [&](auto dt) { kad_perm_kernel<dt><<<(unsigned)l.grid, kThreads, kLdsPerm, st>>>(pa); }));
+        FAD_TRY(with_dtype_kernel(dtype, kernel, [&](auto dt, auto kf) {
+            kad_perm_kernel<dt, kf><<<(unsigned)l.grid, kThreads, kLdsPerm, st>>>(pa);
+        }));
     }
     kad_perm_stats_kernel<<<(unsigned)NL, 256, 0, st>>>(pslots, groups_d, ng, lab, nwz, r_d, tot_d, (double)c0, n, m, t_d, obs_d);
     FAD_HIP_TRY(hipGetLastError());

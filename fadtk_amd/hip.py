@@ -661,6 +661,17 @@ def _kad_bandwidth(bandwidth: Optional[float]) -> float:
     return bw
 
 
+KAD_KERNELS = {"gaussian": K.FAD_KAD_GAUSSIAN, "iq": K.FAD_KAD_IQ, "imq": K.FAD_KAD_IMQ}
+
+
+def kad_kernel_code(kernel: str) -> int:
+    """-> the C ABI's kernel argument (FAD_KAD_*) of a kernel name: "gaussian" exp(-t), "iq" 1 / (1 + t) or "imq" 1 / sqrt(1 + t),
+    t = |a - b|^2 / (2 sigma^2).  Any other name is a ValueError, raised before the native library is touched."""
+    if not isinstance(kernel, str) or kernel not in KAD_KERNELS:
+        raise ValueError(f"KAD: kernel must be one of {', '.join(map(repr, KAD_KERNELS))}, got {kernel!r}")
+    return KAD_KERNELS[kernel]
+
+
 def kad_median_distance(x, device: int = 0) -> float:
     """``fad_kad_median_distance``: np.median(scipy.spatial.distance.pdist(x)) of one set of rows (numpy on the host, or a torch CUDA
     tensor used in place on torch's current stream)."""
@@ -672,10 +683,12 @@ def kad_median_distance(x, device: int = 0) -> float:
     return float(out.value)
 
 
-def kad(x, y, bandwidth: Optional[float] = None, device: int = 0) -> dict:
-    """``fad_kad``: the unbiased Gaussian-kernel MMD^2 between the rows of x (baseline) and y -> dict of fad_kad_result
-    (mmd2, kxx_mean, kyy_mean, kxy_mean, bandwidth, n, m).  ``bandwidth=None``: the median pairwise distance of x.
+def kad(x, y, bandwidth: Optional[float] = None, device: int = 0, kernel: str = "gaussian") -> dict:
+    """``fad_kad_k``: the unbiased kernel MMD^2 between the rows of x (baseline) and y -> dict of fad_kad_result
+    (mmd2, kxx_mean, kyy_mean, kxy_mean, bandwidth, n, m).  ``bandwidth=None``: the median pairwise distance of x.  ``kernel``:
+    "gaussian" (the default), "iq" or "imq" (kad_kernel_code).
     Both sets are numpy arrays or both torch CUDA tensors of one dtype (float16 / bfloat16 / float32)."""
+    kf = kad_kernel_code(kernel)
     lib = K.load_library()
     (px, n, d, ldx, cx, dev_x, kx), (py, m, dy, ldy, cy, dev_y, ky) = _kad_pair(x, y, "y", device)
     if d != dy:
@@ -684,15 +697,18 @@ def kad(x, y, bandwidth: Optional[float] = None, device: int = 0) -> dict:
         raise ValueError("KAD: x and y must have the same dtype")
     res = K.FadKadResult()
     bw = _kad_bandwidth(bandwidth)
-    K.check(lib.fad_kad(px, n, ldx, py, m, ldy, d, cx, dev_x, bw, C.byref(res), int(device), K.current_stream_ptr(device)), "fad_kad")
+    K.check(lib.fad_kad_k(px, n, ldx, py, m, ldy, d, cx, dev_x, bw, kf, C.byref(res), int(device), K.current_stream_ptr(device)), "fad_kad")
     return res.as_dict()
 
 
-def kad_individual(x, rows, offsets: Sequence[int], bandwidth: Optional[float] = None, device: int = 0) -> dict:
-    """``fad_kad_individual``: KAD between the baseline rows x and every song s = rows[offsets[s]:offsets[s + 1]], one sigma for all
+def kad_individual(x, rows, offsets: Sequence[int], bandwidth: Optional[float] = None, device: int = 0,
+                   kernel: str = "gaussian") -> dict:
+    """``fad_kad_individual_k``: KAD between the baseline rows x and every song s = rows[offsets[s]:offsets[s + 1]], one sigma for all
     (``bandwidth=None``: the median pairwise distance of x) -> dict of float64 arrays ``mmd2``, ``kyy_mean``, ``kxy_mean`` and int32
     ``status`` [S] (NaN where status is FAD_ERR_TOO_FEW_ROWS or FAD_ERR_NOT_FINITE), plus ``kxx_mean``, ``bandwidth`` and ``n``.
-    x and rows are both numpy arrays or both torch CUDA tensors of one dtype (float16 / bfloat16 / float32)."""
+    ``kernel``: "gaussian", "iq" or "imq".  x and rows are both numpy arrays or both torch CUDA tensors of one dtype (float16 /
+    bfloat16 / float32)."""
+    kf = kad_kernel_code(kernel)
     lib = K.load_library()
     (px, n, d, ldx, cx, dev_x, kx), (py, m, dy, ldy, cy, dev_y, ky) = _kad_pair(x, rows, "rows", device)
     if m > 0 and d != dy:
@@ -707,9 +723,9 @@ def kad_individual(x, rows, offsets: Sequence[int], bandwidth: Optional[float] =
     out = {k: np.full(S, np.nan) for k in ("mmd2", "kyy_mean", "kxy_mean")}
     out["status"] = np.zeros(S, dtype=np.int32)
     res = K.FadKadResult()
-    K.check(lib.fad_kad_individual(px, n, ldx, py if m > 0 else None, m, max(ldy, d), off.ctypes.data_as(C.POINTER(C.c_int64)), S, d,
-                                   cx, dev_x, bw, C.byref(res), out["mmd2"].ctypes.data, out["kyy_mean"].ctypes.data,
-                                   out["kxy_mean"].ctypes.data, out["status"].ctypes.data, int(device), K.current_stream_ptr(device)),
+    K.check(lib.fad_kad_individual_k(px, n, ldx, py if m > 0 else None, m, max(ldy, d), off.ctypes.data_as(C.POINTER(C.c_int64)), S, d,
+                                     cx, dev_x, bw, kf, C.byref(res), out["mmd2"].ctypes.data, out["kyy_mean"].ctypes.data,
+                                     out["kxy_mean"].ctypes.data, out["status"].ctypes.data, int(device), K.current_stream_ptr(device)),
             "fad_kad_individual")
     out.update(kxx_mean=res.kxx_mean, bandwidth=res.bandwidth, n=res.n)
     return out
@@ -718,14 +734,16 @@ def kad_individual(x, rows, offsets: Sequence[int], bandwidth: Optional[float] =
 KAD_MAX_SETS = 64
 
 
-def kad_uncertainty(x, ys: Sequence, bandwidth: Optional[float] = None, device: int = 0, rows: bool = False) -> dict:
-    """``fad_kad_uncertainty``: KAD between the baseline rows x and each evaluation set ys[s] (1 <= S <= 64), one sigma for all
+def kad_uncertainty(x, ys: Sequence, bandwidth: Optional[float] = None, device: int = 0, rows: bool = False,
+                    kernel: str = "gaussian") -> dict:
+    """``fad_kad_uncertainty_k``: KAD between the baseline rows x and each evaluation set ys[s] (1 <= S <= 64), one sigma for all
     (``bandwidth=None``: the median pairwise distance of x), with the first-order covariance of the S estimates -> dict of float64
     arrays ``mmd2``, ``kyy_mean``, ``kxy_mean``, ``stderr`` [S] and ``cov`` [S, S], plus ``kxx_mean``, ``bandwidth``, ``n`` and ``m``
     [S] (int64).  ``rows=True`` adds the per-row projections ``proj_x`` [S, n] (a^s_i) and ``proj_y`` (a list of [m_s] arrays, b^s_l).
     A first-order (Hoeffding-projection) estimate: meaningful for sets that differ from the baseline; for a set with the baseline's own
-    distribution it understates the spread (include/fad_hip.h).  x and every set are numpy arrays, or all torch CUDA tensors, of one
-    dtype (float16 / bfloat16 / float32)."""
+    distribution it understates the spread (include/fad_hip.h).  ``kernel``: "gaussian", "iq" or "imq".  x and every set are numpy
+    arrays, or all torch CUDA tensors, of one dtype (float16 / bfloat16 / float32)."""
+    kf = kad_kernel_code(kernel)
     ys = list(ys)
     if not 1 <= len(ys) <= KAD_MAX_SETS:
         raise ValueError(f"KAD uncertainty takes 1 .. {KAD_MAX_SETS} evaluation sets, got {len(ys)}")
@@ -749,9 +767,9 @@ def kad_uncertainty(x, ys: Sequence, bandwidth: Optional[float] = None, device: 
     cov = np.zeros((S, S))
     proj_x = np.zeros((S, n)) if rows else None
     proj_y = np.zeros(int(ms.sum())) if rows else None
-    K.check(lib.fad_kad_uncertainty(px, n, ldx, ptrs, ms.ctypes.data_as(C.POINTER(C.c_int64)), lds.ctypes.data_as(C.POINTER(C.c_int64)),
-                                    S, d, cx, dev_x, bw, res, cov.ctypes.data, proj_x.ctypes.data if rows else None,
-                                    proj_y.ctypes.data if rows else None, int(device), K.current_stream_ptr(device)), "fad_kad_uncertainty")
+    K.check(lib.fad_kad_uncertainty_k(px, n, ldx, ptrs, ms.ctypes.data_as(C.POINTER(C.c_int64)), lds.ctypes.data_as(C.POINTER(C.c_int64)),
+                                      S, d, cx, dev_x, bw, kf, res, cov.ctypes.data, proj_x.ctypes.data if rows else None,
+                                      proj_y.ctypes.data if rows else None, int(device), K.current_stream_ptr(device)), "fad_kad_uncertainty")
     out = {k: np.array([getattr(r, k) for r in res]) for k in ("mmd2", "kyy_mean", "kxy_mean")}
     out.update(stderr=np.sqrt(np.diag(cov)), cov=cov, kxx_mean=res[0].kxx_mean, bandwidth=res[0].bandwidth, n=int(res[0].n),
                m=np.array([r.m for r in res], dtype=np.int64))
@@ -831,12 +849,14 @@ def pack_labels_torch(u):
     return torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32)
 
 
-def kad_permutation_test(x, y, labels, bandwidth: Optional[float] = None, device: int = 0) -> dict:
-    """``fad_kad_permutation_test``: the two-sample permutation test of KAD on the pooled rows Z = [x; y] -> dict of fad_kad_result
+def kad_permutation_test(x, y, labels, bandwidth: Optional[float] = None, device: int = 0, kernel: str = "gaussian") -> dict:
+    """``fad_kad_permutation_test_k``: the two-sample permutation test of KAD on the pooled rows Z = [x; y] -> dict of fad_kad_result
     for the observed labelling (mmd2 = t_0, kxx_mean, kyy_mean, kxy_mean, bandwidth, n, m), ``null`` [P] (t of every labelling in
     ``labels``) and ``p_value`` = (1 + #{null >= t_0}) / (P + 1).  ``labels``: the P random labellings (each with exactly n ones over
     the N = n + m rows), packed words [P, ceil(N / 32)] (bit i & 31 of word i >> 5 is row i) or a 0/1 matrix [P, N]; the observed one
-    is added by the library.  ``bandwidth=None``: the median pairwise distance of Z (exact test); a given sigma is used as is."""
+    is added by the library.  ``bandwidth=None``: the median pairwise distance of Z (exact test); a given sigma is used as is.
+    ``kernel``: "gaussian", "iq" or "imq"."""
+    kf = kad_kernel_code(kernel)
     lib = K.load_library()
     (px, n, d, ldx, cx, dev_x, kx), (py, m, dy, ldy, cy, dev_y, ky) = _kad_pair(x, y, "y", device)
     if d != dy:
@@ -850,8 +870,8 @@ def kad_permutation_test(x, y, labels, bandwidth: Optional[float] = None, device
     res = K.FadKadResult()
     null = np.zeros(P)
     pv = C.c_double()
-    K.check(lib.fad_kad_permutation_test(px, n, ldx, py, m, ldy, d, cx, dev_x, bw, pl, P, dev_l, C.byref(res), null.ctypes.data,
-                                         C.byref(pv), int(device), K.current_stream_ptr(device)), "fad_kad_permutation_test")
+    K.check(lib.fad_kad_permutation_test_k(px, n, ldx, py, m, ldy, d, cx, dev_x, bw, kf, pl, P, dev_l, C.byref(res), null.ctypes.data,
+                                           C.byref(pv), int(device), K.current_stream_ptr(device)), "fad_kad_permutation_test")
     out = res.as_dict()
     out.update(null=null, p_value=float(pv.value))
     return out

@@ -1,10 +1,13 @@
-"""Kernel Audio Distance (KAD): the unbiased Gaussian-kernel MMD^2 between two sets of embedding rows.
+"""Kernel Audio Distance (KAD): the unbiased kernel MMD^2 (Gaussian by default) between two sets of embedding rows.
 
 An addition beyond fadtk's FAD (Chung et al. 2025, "KAD: No More FAD! An Effective and Efficient Evaluation Metric for Audio
 Generation"), computed by the same library on the same embedding caches:
 
     k(a, b) = exp(-|a - b|^2 / (2 sigma^2))
     MMD^2   = mean_{i != j} k(x_i, x_j) + mean_{i != j} k(y_i, y_j) - 2 mean_{i, j} k(x_i, y_j)
+
+``kernel`` / ``--kernel`` picks the KAD toolkit's other kernels with the same bandwidth convention, t = |a - b|^2 / (2 sigma^2):
+``"iq"`` k = 1 / (1 + t) and ``"imq"`` k = 1 / sqrt(1 + t), the heavy-tailed choices for sets far apart, where the Gaussian saturates.
 
 x is the baseline, y the evaluation set: all frames of all cached ``.npy`` files of a directory, concatenated (the rows FAD feeds
 to ``calc_embd_statistics``).  sigma defaults to the median pairwise distance within the baseline
@@ -14,7 +17,7 @@ negative: the estimator is unbiased.
 Per song (``--indiv``): KAD between the baseline and each file of the evaluation directory alone, one sigma for all, every song in
 one batched GPU call (``fad_kad_individual``); ``path,score`` lines sorted by |score|, like fadtk's per-song FAD.
 
-    python -m fadtk_amd.kad <model> <baseline_dir> <eval_dir> [csv] [--bandwidth S] [--scale F] [-w N] [--indiv]
+    python -m fadtk_amd.kad <model> <baseline_dir> <eval_dir> [csv] [--bandwidth S] [--kernel K] [--scale F] [-w N] [--indiv]
 
 Several evaluation sets against one baseline, with standard errors and paired comparisons (``fad_kad_uncertainty``, a first-order
 estimate): ``calc_kernel_audio_distance_uncertainty`` / ``KernelAudioDistance.score_many``, and ``python -m fadtk_amd.kad_compare``.
@@ -38,6 +41,7 @@ from .utils import PathLike, tmap, write
 
 log = logging.getLogger("fadtk_amd")
 CSV_HEADER = "model,baseline,eval,kad,bandwidth,scale,time\n"
+KAD_KERNELS = ("gaussian", "iq", "imq")
 INDIV_BYTES = 4 << 30          # song rows per fad_kad_individual call at most (a larger set is split; sigma comes from the first call)
 
 
@@ -45,9 +49,51 @@ def _shape_of(x):
     return tuple(x.shape) if hasattr(x, "shape") else np.asarray(x).shape
 
 
-def calc_kernel_audio_distance(x, y, bandwidth: Optional[float] = None, scale: float = 1.0, device: int = 0, details: bool = False):
-    """scale * MMD^2 between the rows of x (baseline) and y, on the GPU (``fad_kad``).  numpy arrays or torch CUDA tensors of
-    float16 / bfloat16 / float32.  ``details=True`` returns (value, dict of the fad_kad_result fields)."""
+def _check_kernel(kernel) -> str:
+    """the kernel name, or a ValueError -- before any file is read or the native library is loaded"""
+    from .hip import kad_kernel_code
+    kad_kernel_code(kernel)
+    return kernel
+
+
+def _csv_forms(header: str, kernel: str):
+    """-> (the header this kernel's rows go under, the other form, what a row gains): the Gaussian kernel writes header and rows as
+    they are; another kernel adds one trailing column ``kernel`` to both."""
+    plain, extended = header, header.rstrip("\n") + ",kernel\n"
+    return (plain, extended, "") if kernel == "gaussian" else (extended, plain, f",{kernel}")
+
+
+def check_csv(target: PathLike, header: str, kernel: str = "gaussian") -> None:
+    """Refuse (ValueError) a CSV that begins with the header of the other form: no CSV mixes rows with and without the kernel column."""
+    mine, other, _ = _csv_forms(header, kernel)
+    if Path(target).is_file():
+        with open(target) as fh:
+            first = fh.readline()
+        if first.rstrip("\r\n") == other.rstrip("\n"):
+            raise ValueError(f"{target} has the header {other.strip()!r}; a row for kernel {kernel!r} goes under {mine.strip()!r}: "
+                             "write it to another file")
+
+
+def append_csv(target: PathLike, header: str, rows: Sequence[str], kernel: str = "gaussian") -> None:
+    """Append ``rows`` (no line ends) to the CSV ``target`` under ``header`` (written when the file is new), in the form of ``kernel``
+    (_csv_forms); a file of the other form is refused, untouched (check_csv)."""
+    mine, _, tail = _csv_forms(header, kernel)
+    check_csv(target, header, kernel)
+    target = Path(target)
+    target.parent.mkdir(parents=True, exist_ok=True)
+    if not target.is_file():
+        target.write_text(mine)
+    with open(target, "a") as fh:
+        for row in rows:
+            fh.write(row + tail + "\n")
+
+
+def calc_kernel_audio_distance(x, y, bandwidth: Optional[float] = None, scale: float = 1.0, device: int = 0, details: bool = False,
+                               kernel: str = "gaussian"):
+    """scale * MMD^2 between the rows of x (baseline) and y, on the GPU (``fad_kad_k``).  numpy arrays or torch CUDA tensors of
+    float16 / bfloat16 / float32.  ``kernel``: "gaussian", "iq" or "imq".  ``details=True`` returns (value, dict of the fad_kad_result
+    fields)."""
+    _check_kernel(kernel)
     sx, sy = _shape_of(x), _shape_of(y)
     if len(sx) != 2 or len(sy) != 2:
         raise ValueError(f"KAD needs two 2-D row matrices, got shapes {sx} and {sy}")
@@ -56,18 +102,19 @@ def calc_kernel_audio_distance(x, y, bandwidth: Optional[float] = None, scale: f
     if sx[0] < 2 or sy[0] < 2:
         raise ValueError(f"KAD needs at least 2 rows per set, got {sx[0]} and {sy[0]}")
     from . import hip
-    res = hip.kad(x, y, bandwidth=bandwidth, device=device)
+    res = hip.kad(x, y, bandwidth=bandwidth, device=device, kernel=kernel)
     value = float(scale) * res["mmd2"]
     return (value, res) if details else value
 
 
 def calc_kernel_audio_distance_individual(x, songs: Sequence, bandwidth: Optional[float] = None, scale: float = 1.0, device: int = 0,
-                                          details: bool = False, max_bytes: int = INDIV_BYTES):
+                                          details: bool = False, max_bytes: int = INDIV_BYTES, kernel: str = "gaussian"):
     """scale * MMD^2 between the rows of x (baseline) and each song [m_s x D] alone, one sigma for all (``bandwidth=None``: the median
     pairwise distance of x), on the GPU (``fad_kad_individual``) -> float64 array [S], NaN for songs with fewer than 2 frames or a
     non-finite row.  numpy arrays or torch CUDA tensors; mixed dtypes are cast to float32.  Songs whose rows together exceed
-    ``max_bytes`` go in several calls, the later ones with the first call's sigma.  ``details=True`` returns (values, dict of
-    hip.kad_individual's arrays and kxx_mean / bandwidth / n)."""
+    ``max_bytes`` go in several calls, the later ones with the first call's sigma (and every call with ``kernel``: "gaussian", "iq"
+    or "imq").  ``details=True`` returns (values, dict of hip.kad_individual's arrays and kxx_mean / bandwidth / n)."""
+    _check_kernel(kernel)
     from . import hip
     sx = _shape_of(x)
     if len(sx) != 2 or sx[0] < 2:
@@ -101,7 +148,7 @@ def calc_kernel_audio_distance_individual(x, songs: Sequence, bandwidth: Optiona
             s1 += 1
         part = [y.reshape(-1, sx[1]) if shapes[s0 + i][0] == 0 else y for i, y in enumerate(songs[s0:s1])]
         off = np.concatenate([[0], np.cumsum([shapes[s][0] for s in range(s0, s1)], dtype=np.int64)])
-        r = hip.kad_individual(x, cat(part), off, bandwidth=bw, device=device)
+        r = hip.kad_individual(x, cat(part), off, bandwidth=bw, device=device, kernel=kernel)
         for k in ("mmd2", "kyy_mean", "kxy_mean", "status"):
             res[k][s0:s1] = r[k]
         res.update(kxx_mean=r["kxx_mean"], bandwidth=r["bandwidth"], n=r["n"])
@@ -141,13 +188,14 @@ class KadUncertainty:
 
 
 def calc_kernel_audio_distance_uncertainty(x, ys: Sequence, bandwidth: Optional[float] = None, scale: float = 1.0, device: int = 0,
-                                           rows: bool = False) -> KadUncertainty:
+                                           rows: bool = False, kernel: str = "gaussian") -> KadUncertainty:
     """KAD between the rows of x (baseline) and each evaluation set in ``ys`` (1 .. 64 of them), one sigma for all (``bandwidth=None``:
     the median pairwise distance of x), with standard errors and the covariance of the S estimates, in one GPU call
     (``fad_kad_uncertainty``).  ``scale`` multiplies values and stderr by |scale| (the values by scale) and cov by scale^2;
     ``compare()`` of the result gives the paired z and p matrices.  numpy arrays or torch CUDA tensors of float16 / bfloat16 /
-    float32; mixed dtypes are cast to float32.  ``rows=True`` keeps the per-row projections in ``details``.  The estimate is
-    first-order: see KadUncertainty."""
+    float32; mixed dtypes are cast to float32.  ``rows=True`` keeps the per-row projections in ``details``.  ``kernel``: "gaussian",
+    "iq" or "imq".  The estimate is first-order: see KadUncertainty."""
+    _check_kernel(kernel)
     from . import hip
     sx = _shape_of(x)
     if len(sx) != 2 or sx[0] < 2:
@@ -165,7 +213,7 @@ def calc_kernel_audio_distance_uncertainty(x, ys: Sequence, bandwidth: Optional[
         x, ys = np.asarray(x), [np.asarray(y) for y in ys]
         if len({x.dtype, *(y.dtype for y in ys)}) > 1:
             x, ys = x.astype(np.float32), [y.astype(np.float32) for y in ys]
-    res = hip.kad_uncertainty(x, ys, bandwidth=bandwidth, device=device, rows=rows)
+    res = hip.kad_uncertainty(x, ys, bandwidth=bandwidth, device=device, rows=rows, kernel=kernel)
     scale = float(scale)
     return KadUncertainty(values=scale * res["mmd2"], stderr=abs(scale) * res["stderr"], cov=scale * scale * res["cov"],
                           bandwidth=res["bandwidth"], scale=scale, details=res)
@@ -192,7 +240,8 @@ def random_labellings(n: int, m: int, permutations: int, seed: int = 0, device: 
 
 
 def calc_kernel_audio_distance_permutation_test(x, y, permutations: int = 1000, seed: int = 0, bandwidth: Optional[float] = None,
-                                                scale: float = 1.0, labels=None, return_labels: bool = False, device: int = 0) -> dict:
+                                                scale: float = 1.0, labels=None, return_labels: bool = False, device: int = 0,
+                                                kernel: str = "gaussian") -> dict:
     """Is y distinguishable from the baseline x at all?  The two-sample permutation test of KAD (``fad_kad_permutation_test``): the
     rows are pooled, relabelled at random ``permutations`` times with the sizes held at n and m, and MMD^2 is recomputed for every
     labelling in one fused GPU pass; p = (1 + #{null >= observed}) / (P + 1).  ``bandwidth=None``: the median pairwise distance of the
@@ -200,7 +249,9 @@ def calc_kernel_audio_distance_permutation_test(x, y, permutations: int = 1000, 
     is.  Labellings come from a seeded generator on the device unless ``labels`` gives them (bool / uint8 [P, N] or packed words
     [P, ceil(N / 32)]).  numpy arrays or torch CUDA tensors of float16 / bfloat16 / float32.  -> dict: ``kad`` (scale * MMD^2),
     ``mmd2``, ``p_value``, ``null`` [P] (MMD^2 of every random labelling), ``bandwidth``, ``kxx_mean``, ``kyy_mean``, ``kxy_mean``,
-    ``n``, ``m``, ``permutations``, ``seed`` (None when labels are given) and, with ``return_labels``, ``labels`` (packed words)."""
+    ``n``, ``m``, ``permutations``, ``seed`` (None when labels are given) and, with ``return_labels``, ``labels`` (packed words).
+    ``kernel``: "gaussian", "iq" or "imq"."""
+    _check_kernel(kernel)
     from . import hip
     sx, sy = _shape_of(x), _shape_of(y)
     if len(sx) != 2 or len(sy) != 2:
@@ -222,7 +273,7 @@ def calc_kernel_audio_distance_permutation_test(x, y, permutations: int = 1000, 
         x, y = np.asarray(x), np.asarray(y)
         if x.dtype != y.dtype:
             x, y = x.astype(np.float32), y.astype(np.float32)
-    res = hip.kad_permutation_test(x, y, labels, bandwidth=bandwidth, device=device)
+    res = hip.kad_permutation_test(x, y, labels, bandwidth=bandwidth, device=device, kernel=kernel)
     out = {"kad": float(scale) * res["mmd2"], "mmd2": res["mmd2"], "p_value": res["p_value"], "null": res["null"],
            "bandwidth": res["bandwidth"], "kxx_mean": res["kxx_mean"], "kyy_mean": res["kyy_mean"], "kxy_mean": res["kxy_mean"],
            "n": int(res["n"]), "m": int(res["m"]), "permutations": int(len(res["null"])), "seed": seed}
@@ -249,7 +300,9 @@ class KernelAudioDistance:
             raise ValueError(f"KAD: {path} is not a directory")
         return self.fad.load_embeddings(p)
 
-    def score(self, baseline: PathLike, eval: PathLike, bandwidth: Optional[float] = None, scale: float = 1.0, details: bool = False):
+    def score(self, baseline: PathLike, eval: PathLike, bandwidth: Optional[float] = None, scale: float = 1.0, details: bool = False,
+              kernel: str = "gaussian"):
+        _check_kernel(kernel)
         x = self.load_rows(baseline)
         y = self.load_rows(eval)
         if x.dtype == np.float64:             # embedding caches are float32 / float16; a float64 cache is narrowed explicitly
@@ -258,35 +311,39 @@ class KernelAudioDistance:
             y = y.astype(np.float32)
         if x.dtype != y.dtype:
             x, y = x.astype(np.float32), y.astype(np.float32)
-        return calc_kernel_audio_distance(x, y, bandwidth=bandwidth, scale=scale, device=self.device_index, details=details)
+        return calc_kernel_audio_distance(x, y, bandwidth=bandwidth, scale=scale, device=self.device_index, details=details,
+                                          kernel=kernel)
 
     def score_many(self, baseline: PathLike, eval_dirs: Sequence[PathLike], bandwidth: Optional[float] = None,
-                   scale: float = 1.0) -> KadUncertainty:
+                   scale: float = 1.0, kernel: str = "gaussian") -> KadUncertainty:
         """KAD of every directory in ``eval_dirs`` against one baseline, with standard errors and their covariance, in one GPU call
         (calc_kernel_audio_distance_uncertainty); ``compare()`` of the result gives the paired z / p matrices."""
+        _check_kernel(kernel)
         x = self.load_rows(baseline)
         ys = [self.load_rows(e) for e in eval_dirs]
         if len({x.dtype, *(y.dtype for y in ys)}) > 1 or x.dtype == np.float64:      # one dtype; float64 caches are narrowed
             x, ys = x.astype(np.float32), [y.astype(np.float32) for y in ys]
-        return calc_kernel_audio_distance_uncertainty(x, ys, bandwidth=bandwidth, scale=scale, device=self.device_index)
+        return calc_kernel_audio_distance_uncertainty(x, ys, bandwidth=bandwidth, scale=scale, device=self.device_index, kernel=kernel)
 
     def permutation_test(self, baseline: PathLike, eval_dir: PathLike, permutations: int = 1000, seed: int = 0,
-                         bandwidth: Optional[float] = None, scale: float = 1.0) -> dict:
+                         bandwidth: Optional[float] = None, scale: float = 1.0, kernel: str = "gaussian") -> dict:
         """The KAD permutation test of ``eval_dir`` against ``baseline`` (calc_kernel_audio_distance_permutation_test), sigma from the
         pooled rows by default."""
+        _check_kernel(kernel)
         x = self.load_rows(baseline)
         y = self.load_rows(eval_dir)
         if x.dtype != y.dtype or x.dtype == np.float64:
             x, y = x.astype(np.float32), y.astype(np.float32)
         return calc_kernel_audio_distance_permutation_test(x, y, permutations=permutations, seed=seed, bandwidth=bandwidth, scale=scale,
-                                                           device=self.device_index)
+                                                           device=self.device_index, kernel=kernel)
 
     def score_individual(self, baseline: PathLike, eval_dir: PathLike, csv_name: Union[Path, str], bandwidth: Optional[float] = None,
-                         scale: float = 1.0) -> Path:
+                         scale: float = 1.0, kernel: str = "gaussian") -> Path:
         """Per-file KAD against the baseline, written as ``path,score`` lines sorted by |score| (FrechetAudioDistance.score_individual's
         format).  All songs go in one batched GPU call with one sigma; files whose embedding is missing, unreadable, of another D or
         shorter than two frames are logged and dropped.  A ``str`` name goes under data/kad-individual/<model>/; an existing CSV is
         left as it is."""
+        _check_kernel(kernel)
         csv = Path(csv_name)
         if isinstance(csv_name, str):
             csv = Path("data") / "kad-individual" / self.ml.name / csv_name
@@ -322,7 +379,7 @@ class KernelAudioDistance:
         pairs = []
         if keep:
             values, res = calc_kernel_audio_distance_individual(x, [e for _, e in keep], bandwidth=bandwidth, scale=scale,
-                                                                device=self.device_index, details=True)
+                                                                device=self.device_index, details=True, kernel=kernel)
             for (f, _), v, st in zip(keep, values, res["status"]):
                 if st == 0:
                     pairs.append((f, np.float64(v)))
@@ -338,7 +395,7 @@ def main(argv=None):
     from .cli import _registry, _setup_logging
     _setup_logging()
     models = _registry()
-    p = ArgumentParser(prog="python -m fadtk_amd.kad", description="Kernel Audio Distance (unbiased Gaussian-kernel MMD^2) "
+    p = ArgumentParser(prog="python -m fadtk_amd.kad", description="Kernel Audio Distance (unbiased kernel MMD^2, Gaussian by default) "
                        "between two directories of audio, on one GPU")
     p.add_argument("model", type=str, choices=list(models), help="embedding model")
     p.add_argument("baseline", type=str, help="baseline dataset directory")
@@ -346,11 +403,16 @@ def main(argv=None):
     p.add_argument("csv", type=str, nargs="?", help="append the result to this CSV; with --indiv: where per-song scores go "
                                                     "(default kad-individual-results.csv)")
     p.add_argument("--bandwidth", type=float, default=None, help="kernel sigma (default: median pairwise distance of the baseline)")
+    p.add_argument("--kernel", type=str, choices=list(KAD_KERNELS), default="gaussian",
+                   help="gaussian exp(-t), iq 1 / (1 + t) or imq 1 / sqrt(1 + t), t = d^2 / (2 sigma^2) (default gaussian); a CSV written "
+                        "for iq or imq has one more column, kernel")
     p.add_argument("--scale", type=float, default=1.0, help="factor applied to the reported MMD^2 (default 1)")
     p.add_argument("-w", "--workers", type=int, default=8, help="number of workers")
     p.add_argument("--indiv", action="store_true", help="one score per song of the eval directory")
     a = p.parse_args(argv)
     model = models[a.model]
+    if a.csv and not a.indiv:
+        check_csv(a.csv, CSV_HEADER, a.kernel)             # before any work: a CSV of the other form is refused
 
     from .fad_batch import cache_embedding_files
     for dataset in (a.baseline, a.eval):
@@ -360,17 +422,13 @@ def main(argv=None):
     if a.indiv:
         assert Path(a.eval).is_dir(), "Individual KAD requires a directory as the evaluation dataset"
         out = Path(a.csv or "kad-individual-results.csv")
-        kad.score_individual(a.baseline, a.eval, out, bandwidth=a.bandwidth, scale=a.scale)
+        kad.score_individual(a.baseline, a.eval, out, bandwidth=a.bandwidth, scale=a.scale, kernel=a.kernel)
         log.info(f"Individual KAD scores saved to {out}")
         return
-    value, res = kad.score(a.baseline, a.eval, bandwidth=a.bandwidth, scale=a.scale, details=True)
+    value, res = kad.score(a.baseline, a.eval, bandwidth=a.bandwidth, scale=a.scale, details=True, kernel=a.kernel)
     if a.csv:
-        target = Path(a.csv)
-        target.parent.mkdir(parents=True, exist_ok=True)
-        if not target.is_file():
-            target.write_text(CSV_HEADER)
-        with open(target, "a") as fh:
-            fh.write(f"{model.name},{a.baseline},{a.eval},{value!r},{res['bandwidth']!r},{a.scale!r},{time.time()}\n")
+        append_csv(a.csv, CSV_HEADER, [f"{model.name},{a.baseline},{a.eval},{value!r},{res['bandwidth']!r},{a.scale!r},{time.time()}"],
+                   a.kernel)
         log.info(f"KAD score appended to {a.csv}")
     log.info(f"The KAD {model.name} score between {a.baseline} and {a.eval} is: {value} (bandwidth {res['bandwidth']})")
     print(value)

@@ -4,10 +4,11 @@ One GPU call (``fad_kad_uncertainty``) gives every set's KAD with one sigma, the
 the paired z / p of every two sets: "model A scores 0.0121 and model B 0.0134 against the same baseline -- is that a difference?".
 The estimate is first-order (meaningful for sets that differ from the baseline).
 
-    python -m fadtk_amd.kad_compare <model> <baseline_dir> <eval_dir> [<eval_dir> ...] [--csv F] [--bandwidth S] [--scale F] [-w N]
+    python -m fadtk_amd.kad_compare <model> <baseline_dir> <eval_dir> [<eval_dir> ...] [--csv F] [--bandwidth S] [--kernel K] [--scale F] [-w N]
 
 Embeddings are cached as ``python -m fadtk_amd.kad`` caches them.  ``--csv`` appends one row per evaluation set
-(model, baseline, eval, kad, stderr, bandwidth, scale); the pairwise z / p table is logged.
+(model, baseline, eval, kad, stderr, bandwidth, scale; with ``--kernel iq`` or ``imq`` one more column, kernel); the pairwise z / p
+table is logged.
 """
 from __future__ import annotations
 
@@ -15,7 +16,7 @@ import logging
 from argparse import ArgumentParser
 from pathlib import Path
 
-from .kad import KernelAudioDistance
+from .kad import KAD_KERNELS, KernelAudioDistance, append_csv, check_csv
 
 log = logging.getLogger("fadtk_amd")
 CSV_HEADER = "model,baseline,eval,kad,stderr,bandwidth,scale\n"
@@ -33,27 +34,27 @@ def main(argv=None):
     p.add_argument("eval", type=str, nargs="+", help=f"directories to evaluate (1 .. {KAD_MAX_SETS})")
     p.add_argument("--csv", type=str, default=None, help="append one row per evaluation directory to this CSV")
     p.add_argument("--bandwidth", type=float, default=None, help="kernel sigma (default: median pairwise distance of the baseline)")
+    p.add_argument("--kernel", type=str, choices=list(KAD_KERNELS), default="gaussian",
+                   help="gaussian exp(-t), iq 1 / (1 + t) or imq 1 / sqrt(1 + t), t = d^2 / (2 sigma^2) (default gaussian); a CSV written "
+                        "for iq or imq has one more column, kernel")
     p.add_argument("--scale", type=float, default=1.0, help="factor applied to the reported MMD^2 and its standard error (default 1)")
     p.add_argument("-w", "--workers", type=int, default=8, help="number of workers")
     a = p.parse_args(argv)
     if len(a.eval) > KAD_MAX_SETS:
         p.error(f"at most {KAD_MAX_SETS} evaluation directories, got {len(a.eval)}")
     model = models[a.model]
+    if a.csv:
+        check_csv(a.csv, CSV_HEADER, a.kernel)             # before any work: a CSV of the other form is refused
 
     from .fad_batch import cache_embedding_files
     for dataset in (a.baseline, *a.eval):
         if Path(dataset).is_dir():
             cache_embedding_files(dataset, model, workers=a.workers)
     kad = KernelAudioDistance(model, audio_load_worker=a.workers, load_model=False)
-    res = kad.score_many(a.baseline, a.eval, bandwidth=a.bandwidth, scale=a.scale)
+    res = kad.score_many(a.baseline, a.eval, bandwidth=a.bandwidth, scale=a.scale, kernel=a.kernel)
     if a.csv:
-        target = Path(a.csv)
-        target.parent.mkdir(parents=True, exist_ok=True)
-        if not target.is_file():
-            target.write_text(CSV_HEADER)
-        with open(target, "a") as fh:
-            for e, v, se in zip(a.eval, res.values, res.stderr):
-                fh.write(f"{model.name},{a.baseline},{e},{float(v)!r},{float(se)!r},{res.bandwidth!r},{a.scale!r}\n")
+        append_csv(a.csv, CSV_HEADER, [f"{model.name},{a.baseline},{e},{float(v)!r},{float(se)!r},{res.bandwidth!r},{a.scale!r}"
+                                       for e, v, se in zip(a.eval, res.values, res.stderr)], a.kernel)
         log.info(f"KAD scores appended to {a.csv}")
     for e, v, se in zip(a.eval, res.values, res.stderr):
         log.info(f"The KAD {model.name} score between {a.baseline} and {e} is: {v} +- {se} (bandwidth {res.bandwidth})")

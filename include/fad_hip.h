@@ -336,6 +336,31 @@ int fad_kad_median_distance(const void* x, int64_t n, int64_t ld, int64_t d, int
  * otherwise a rounding residue may leave a tiny positive median, which is used as the bandwidth. */
 int fad_kad(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype,
             int on_device, double bandwidth, fad_kad_result_t* out, int device, void* stream);
+/* ------------------------------------------------------------------ KAD kernels
+ * The _k entry points below take the kernel as the KAD toolkit does, one bandwidth convention for all, gamma = 1 / (2 sigma^2):
+ *   FAD_KAD_GAUSSIAN   k(a, b) = exp(-gamma |a - b|^2)
+ *   FAD_KAD_IQ         k(a, b) = 1 / (1 + gamma |a - b|^2)          (inverse quadratic)
+ *   FAD_KAD_IMQ        k(a, b) = 1 / sqrt(1 + gamma |a - b|^2)      (inverse multiquadric)
+ * The toolkit forms gamma = 1 / (2 sigma^2 + eps) with eps = 1e-8; this library adds no eps, for any kernel (a median of 0 is an error
+ * instead).  That is the only difference.  Each _k function is its parent with `kernel` after `bandwidth`: the same arguments, results,
+ * errors and default bandwidth (a median distance, whatever the kernel); the parent is the _k function with FAD_KAD_GAUSSIAN, bit for
+ * bit.  Any other value of `kernel` -> FAD_ERR_INVALID.  The heavy-tailed kernels are evaluated in float32 as 1 / max(1 + t, 1) (its
+ * square root for imq), t = gamma |a - b|^2; the permutation test's c0 under the default sigma is k at t = 1/2: 2/3 and 1 / sqrt(1.5). */
+typedef enum fad_kad_kernel { FAD_KAD_GAUSSIAN = 0, FAD_KAD_IQ = 1, FAD_KAD_IMQ = 2 } fad_kad_kernel;
+int fad_kad_k(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype,
+              int on_device, double bandwidth, int kernel, fad_kad_result_t* out, int device, void* stream);
+int fad_kad_individual_k(const void* x, int64_t n, int64_t ldx, const void* rows, int64_t n_rows, int64_t ldy,
+                         const int64_t* offsets, int64_t n_songs, int64_t d, int dtype, int on_device, double bandwidth, int kernel,
+                         fad_kad_result_t* base, double* out_mmd2, double* out_kyy_mean, double* out_kxy_mean,
+                         int32_t* out_status, int device, void* stream);
+int fad_kad_uncertainty_k(const void* x, int64_t n, int64_t ldx, const void* const* ys, const int64_t* ms, const int64_t* ldys,
+                          int n_sets, int64_t d, int dtype, int on_device, double bandwidth, int kernel,
+                          fad_kad_result_t* out /* [n_sets] */, double* cov /* [n_sets * n_sets] */,
+                          double* proj_x /* [n_sets * n] or NULL */, double* proj_y /* [sum m_s] or NULL */, int device, void* stream);
+int fad_kad_permutation_test_k(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype,
+                               int on_device, double bandwidth, int kernel, const uint32_t* labels, int64_t n_perm,
+                               int labels_on_device, fad_kad_result_t* observed, double* null /* [n_perm] host */, double* p_value,
+                               int device, void* stream);
 /* ------------------------------------------------------------------ per-song KAD (--indiv)
  * For every song s (rows [offsets[s], offsets[s+1]) of `rows` [n_rows x d]), KAD between the baseline x [n x d] and that song alone,
  * with one sigma for all songs: what fad_kad(x, song_s, bandwidth = sigma) gives, in one call that packs the baseline, finds sigma
