@@ -20,7 +20,8 @@ def __getattr__(name):
         return getattr(model_loader, name)
     if name in ("KernelAudioDistance", "calc_kernel_audio_distance", "calc_kernel_audio_distance_individual",
                 "calc_kernel_audio_distance_uncertainty", "KadUncertainty",
-                "calc_kernel_audio_distance_permutation_test", "KAD_KERNELS"):      # lazy: `python -m fadtk_amd.kad` runs the module itself
+                "calc_kernel_audio_distance_permutation_test", "calc_kernel_audio_distance_sweep", "KadSweep",
+                "KAD_KERNELS"):      # lazy: `python -m fadtk_amd.kad` runs the module itself
         from . import kad
         return getattr(kad, name)
     if name in ("PrecisionRecall", "calc_precision_recall_density_coverage"):      # lazy, as KAD's

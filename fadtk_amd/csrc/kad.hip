@@ -1,7 +1,7 @@
 // Kernel Audio Distance: the unbiased Gaussian-kernel MMD^2 between two sets of embedding rows, and the median pairwise distance
 // of one set (the default bandwidth).  DESIGN.md 4.6.  Per-song KAD (4.7), the k-NN precision / recall / density / coverage (4.8),
-// KAD's standard errors (4.9), its permutation test (4.10) and the nearest baseline rows with authenticity (4.11) run on the same main
-// loop.
+// KAD's standard errors (4.9), its permutation test (4.10), the nearest baseline rows with authenticity (4.11) and KAD at several
+// bandwidths in one pass (4.12) run on the same main loop.
 //
 // Every pass is one GEMM-shaped walk over 128 x 128 tiles of a pair space (kad_tiles.h) whose n x m matrix is never stored:
 //   - pack:   each set is copied once into a zero-padded [n_pad x dp] image of its own dtype (dp: D rounded up to 128 bytes, n_pad:
@@ -319,6 +319,89 @@ __global__ void __launch_bounds__(256) kad_slots_sum_kernel(const double* __rest
     }
     if (threadIdx.x == 0) out[blockIdx.x] = red[0];
 }
+
+// ------------------------------------------------------------------------------------------------- bandwidth sweep
+// fad_kad_sweep's sum pass: kad_pass_kernel<DT, MODE_SUM, KF> with NB constants c[b] instead of one.  The pair GEMM does not depend on
+// sigma, so a tile's accumulators are formed once and read NB times: element by element in tile_sum's order (bi, bj, g), bandwidth b's
+// kernel value into b's own per-lane float partial, per tile into b's own double, and at the end b's own butterfly and
+// ((l0 + l1) + l2) + l3 into b's own slot of the workgroup, slots[b * stride + workgroup].  Bandwidth b therefore adds exactly what
+// kad_pass_kernel adds with c = c[b], in the same order: the same bits wherever the two make the same launch cut.
+template <int NB>
+struct SweepArgs {
+    PassArgs p;                                // p.c is not read; p.slots: the pass's slots of bandwidth 0 from this launch on
+    int64_t stride;                            // slots of the whole pass per bandwidth
+    float c[NB];
+};
+
+template <bool MASK, int KF, int NB>
+__device__ __forceinline__ void tile_sum_sweep(const f32x16 (&acc)[2][2], const float (&c)[NB], int rbase, int cbase, int lane,
+                                               float (&s)[NB]) {
+    int lrow = rbase + 4 * (lane >> 5) - (cbase + (lane & 31));
+    if (MASK) asm volatile("" : "+v"(lrow));                                          // as tile_sum
+#pragma unroll
+    for (int b = 0; b < NB; ++b) s[b] = 0.f;
+#pragma unroll
+    for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+        for (int bj = 0; bj < 2; ++bj)
+#pragma unroll
+            for (int g = 0; g < 16; ++g) {
+                const bool keep = !MASK || (bj * 32 - bi * 32 - (g & 3) - 8 * (g >> 2)) > lrow;       // column > row
+#pragma unroll
+                for (int b = 0; b < NB; ++b) {
+                    float e = kernel_value<KF>(acc[bi][bj][g], c[b]);     // every read of the accumulator is kernel_value's mul / fma
+                    if (MASK) e = keep ? e : 0.f;
+                    s[b] += e;
+                }
+            }
+}
+
+template <int DT, int KF, int NB>
+__global__ void __launch_bounds__(kThreads, 2) kad_sweep_kernel(SweepArgs<NB> q) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    double* lred = reinterpret_cast<double*>(lds + 2 * kOpBytes + 2 * kTile * 4);     // [NB][4]
+    const PassArgs& p = q.p;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
+    const int64_t G = gridDim.x, nslots = kad::launch_slots(p.cnt);
+    double dsum[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) dsum[b] = 0.0;
+    // Thread b < NB writes bandwidth b's slot at the end.  Its address is formed here and made opaque, so it waits in two VGPRs, of which
+    // there are enough; left to the end, the slots pointer and the stride wait in SGPRs, two of which were spilled around the tile loop.
+    double* dst = p.slots + (tid * q.stride + blockIdx.x);
+    asm volatile("" : "+v"(dst));
+
+    for (int64_t L = blockIdx.x; L < nslots; L += G) {
+        bool live;
+        const int64_t v = kad::slot_tile(L, p.cnt, &live);
+        if (!live) continue;                                                          // uniform over the workgroup
+        const kad::Tile t = p.tri ? kad::tri_tile(p.u0 + v, p.tiles_j) : kad::rect_tile(p.u0 + v, p.tiles_j);
+        f32x16 acc[2][2];
+        tile_mfma<DT>(p.a, p.b, p.ha, p.hb, p.pitch, p.nchunks, t.I, t.J, lds, [](int) {}, acc);
+
+        const int rbase = wm * 64, cbase = wn * 64;
+        float s[NB];
+        if (p.tri && t.I == t.J) tile_sum_sweep<true, KF, NB>(acc, q.c, rbase, cbase, lane, s);
+        else tile_sum_sweep<false, KF, NB>(acc, q.c, rbase, cbase, lane, s);
+#pragma unroll
+        for (int b = 0; b < NB; ++b) dsum[b] += (double)s[b];
+    }
+
+    __syncthreads();
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) dsum[b] += __shfl_xor(dsum[b], off, 64);
+        if (lane == 0) lred[4 * b + wave] = dsum[b];
+    }
+    __syncthreads();
+    if (tid < NB) *dst = ((lred[4 * tid] + lred[4 * tid + 1]) + lred[4 * tid + 2]) + lred[4 * tid + 3];
+}
+
+constexpr int kSweepGroup = 8;                 // bandwidths per pass at most: the largest NB instantiated (4 and 8)
+template <int NB>
+constexpr size_t lds_sweep() { return 2 * kOpBytes + 2 * kTile * 4 + NB * 4 * sizeof(double); }
 
 // ------------------------------------------------------------------------------------------------- per-song passes
 // fad_kad_individual's cross (X x Y) and band (Y x Y inside each song) passes: tile_mfma, with an epilogue that keeps per-column
@@ -1473,19 +1556,81 @@ static int sum_passes(const PassArgs (&passes)[N], int dtype, int kernel, int de
     return FAD_OK;
 }
 
-// sigma = `bandwidth`, or the median pairwise distance of x when it is 0, and c = log2(e) / sigma^2 (1 / sigma^2 for iq and imq, whose
-// epilogue takes t = c d^2 / 2 itself) as the kernels' float32
+// c = log2(e) / sigma^2 (1 / sigma^2 for iq and imq, whose epilogue takes t = c d^2 / 2 itself) as the kernels' float32: the one place a
+// bandwidth becomes a kernel constant, for resolve_sigma and fad_kad_sweep alike
+enum SigmaCheck { SIGMA_OK = 0, SIGMA_NOT_POSITIVE = 1, SIGMA_OUTSIDE_F32 = 2 };
+static SigmaCheck sigma_constant(double sigma, int kernel, float* c) {
+    if (!(sigma > 0) || !std::isfinite(sigma)) return SIGMA_NOT_POSITIVE;
+    const double cd = (kernel == FAD_KAD_GAUSSIAN ? 1.4426950408889634 : 1.0) / (sigma * sigma);
+    if (!(cd > 0) || !std::isfinite(cd) || !std::isfinite((float)cd) || (float)cd == 0.f) return SIGMA_OUTSIDE_F32;
+    *c = (float)cd;
+    return SIGMA_OK;
+}
+
+// sigma = `bandwidth`, or the median pairwise distance of x when it is 0, and its c (sigma_constant)
 static int resolve_sigma(const Packed& x, double bandwidth, int kernel, int dtype, int device, hipStream_t st, KadWorkspace& ws, const char* who,
                          double* sigma, float* c) {
     *sigma = bandwidth;
     if (!(*sigma > 0)) FAD_TRY(median_of_packed(x, dtype, device, st, ws, sigma));
-    if (!(*sigma > 0) || !std::isfinite(*sigma))
-        return set_error(FAD_ERR_INVALID, "%s: bandwidth %g (the median pairwise distance of the baseline when none is given) must be > 0"
-                         " -- are all baseline rows identical?", who, *sigma);
-    const double cd = (kernel == FAD_KAD_GAUSSIAN ? 1.4426950408889634 : 1.0) / (*sigma * *sigma);
-    if (!(cd > 0) || !std::isfinite(cd) || !std::isfinite((float)cd) || (float)cd == 0.f)
-        return set_error(FAD_ERR_INVALID, "%s: bandwidth %g is outside the float32 range of the kernel", who, *sigma);
-    *c = (float)cd;
+    switch (sigma_constant(*sigma, kernel, c)) {
+        case SIGMA_NOT_POSITIVE:
+            return set_error(FAD_ERR_INVALID, "%s: bandwidth %g (the median pairwise distance of the baseline when none is given) must be > 0"
+                             " -- are all baseline rows identical?", who, *sigma);
+        case SIGMA_OUTSIDE_F32:
+            return set_error(FAD_ERR_INVALID, "%s: bandwidth %g is outside the float32 range of the kernel", who, *sigma);
+        default: return FAD_OK;
+    }
+}
+
+// The three sum passes for a group of g <= NB bandwidths (c[0 .. g), padded with c[g - 1]; the padded sums are dropped):
+// sums[3 * b + q] = pass q's sum under c[b], read back.  Slots: pass q takes NB * G_q of them, G_q its launches' grids together,
+// bandwidth b's at [NB * (G_0 + .. + G_{q-1}) + b * G_q, + G_q) -- within that range in fad_kad_k's order, launch after launch.  A
+// launch's epilogue weighs NB single ones (kad_tiles.h), so a launch of 8 bandwidths is no longer than one of fad_kad_k.
+template <int NB>
+static int sweep_passes(const PassArgs (&passes)[3], const float* c, int g, int dtype, int kernel, int device, hipStream_t st,
+                        KadWorkspace& ws, double* sums) {
+    std::vector<kad::Launch> launches[3];
+    int64_t G[3], off[3 * NB + 1];
+    int64_t base = 0;
+    for (int q = 0; q < 3; ++q) {
+        const PassArgs& p = passes[q];
+        const int64_t total = p.tri ? kad::tri_tiles(p.tiles_j) : kad::blocks(p.n_a) * p.tiles_j;
+        const int64_t per = kad::tiles_per_launch_for(p.pitch / (int64_t)dtype_size(dtype), dtype == FAD_F32, kad::kSumEpilogue * NB);
+        launches[q] = kad::launches(total, per, grid_cap(device));
+        G[q] = 0;
+        for (const kad::Launch& l : launches[q]) G[q] += l.grid;
+        for (int b = 0; b < NB; ++b) off[q * NB + b] = base + b * G[q];
+        base += NB * G[q];
+    }
+    off[3 * NB] = base;
+    FAD_TRY(ws.slots.reserve((size_t)base * sizeof(double)));
+    // ws.small: the sweep's offset table [3 * 8 + 1] at double 32 and its sums [3 * 8] at double 64, clear of the single passes' places
+    // (info 0 .. 3, offsets 8 .. 11, sums 16 .. 18), of the per-set info at 1024 and of the histograms at 4096
+    int64_t* off_d = reinterpret_cast<int64_t*>(static_cast<double*>(ws.small.p) + 32);
+    double* sums_d = static_cast<double*>(ws.small.p) + 64;
+    static_assert(3 * kSweepGroup + 1 <= 32 && NB <= kSweepGroup, "the sweep's tables in ws.small");
+    FAD_HIP_TRY(hipMemcpyAsync(off_d, off, sizeof(off), hipMemcpyHostToDevice, st));
+    for (int q = 0; q < 3; ++q) {
+        SweepArgs<NB> a;
+        a.p = passes[q];
+        a.stride = G[q];
+        for (int b = 0; b < NB; ++b) a.c[b] = c[b < g ? b : g - 1];
+        a.p.slots = static_cast<double*>(ws.slots.p) + off[q * NB];
+        for (const kad::Launch& l : launches[q]) {
+            a.p.u0 = l.u0; a.p.cnt = l.cnt;
+            FAD_TRY(with_dtype_kernel(dtype, kernel, [&](auto dt, auto kf) {
+                kad_sweep_kernel<dt, kf, NB><<<(unsigned)l.grid, kThreads, lds_sweep<NB>(), st>>>(a);
+            }));
+            a.p.slots += l.grid;
+        }
+    }
+    kad_slots_sum_kernel<<<3 * NB, 256, 0, st>>>(static_cast<const double*>(ws.slots.p), off_d, sums_d);
+    FAD_HIP_TRY(hipGetLastError());
+    double host[3 * NB];
+    FAD_HIP_TRY(hipMemcpyAsync(host, sums_d, sizeof(host), hipMemcpyDeviceToHost, st));
+    FAD_HIP_TRY(hipStreamSynchronize(st));
+    for (int b = 0; b < g; ++b)
+        for (int q = 0; q < 3; ++q) sums[3 * b + q] = host[q * NB + b];
     return FAD_OK;
 }
 
@@ -1604,6 +1749,77 @@ int fad_kad_k(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, i
     out->bandwidth = sigma;
     out->n = n;
     out->m = m;
+    return FAD_OK;
+}
+
+
+int fad_kad_sweep(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype, int on_device,
+                  const double* bandwidths, int n_bw, int relative, int kernel, fad_kad_result_t* out, int device, void* stream) {
+    using namespace fad;
+    if (!out) return set_error(FAD_ERR_INVALID, "fad_kad_sweep: NULL output");
+    if (!bandwidths) return set_error(FAD_ERR_INVALID, "fad_kad_sweep: NULL bandwidths");
+    if (n_bw < 1 || n_bw > FAD_KAD_MAX_BANDWIDTHS)
+        return set_error(FAD_ERR_INVALID, "fad_kad_sweep: %d bandwidths, outside 1 .. %d", n_bw, FAD_KAD_MAX_BANDWIDTHS);
+    FAD_TRY(check_kernel(kernel, "fad_kad_sweep"));
+    FAD_TRY(check_rows(x, n, ldx, d, dtype, "fad_kad_sweep (x)"));
+    FAD_TRY(check_rows(y, m, ldy, d, dtype, "fad_kad_sweep (y)"));
+    for (int b = 0; b < n_bw; ++b)
+        if (!(bandwidths[b] > 0) || !std::isfinite(bandwidths[b]))
+            return set_error(FAD_ERR_INVALID, "fad_kad_sweep: %s %d is %g; every one must be finite and > 0 (the median is the factor 1)",
+                             relative ? "factor" : "bandwidth", b, bandwidths[b]);
+    FAD_TRY(check_device(device));
+    DeviceGuard g(device);
+    if (!g.ok) return set_error(FAD_ERR_HIP, "hipSetDevice(%d) failed", device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    KadWorkspace& ws = workspace(device);
+
+    Packed px, py;
+    FAD_TRY(pack_set(0, x, n, ldx, d, dtype, on_device, st, ws, &px));
+    FAD_TRY(pack_set(1, y, m, ldy, d, dtype, on_device, st, ws, &py));
+    double median = 1.0;
+    if (relative) {
+        FAD_TRY(median_of_packed(px, dtype, device, st, ws, &median));
+        if (!(median > 0) || !std::isfinite(median))
+            return set_error(FAD_ERR_INVALID, "fad_kad_sweep: the median pairwise distance of the baseline is %g; it must be > 0"
+                             " -- are all baseline rows identical?", median);
+    }
+    double sigma[FAD_KAD_MAX_BANDWIDTHS];
+    float c[FAD_KAD_MAX_BANDWIDTHS];
+    for (int b = 0; b < n_bw; ++b) {
+        sigma[b] = relative ? bandwidths[b] * median : bandwidths[b];
+        if (sigma_constant(sigma[b], kernel, &c[b]) != SIGMA_OK)
+            return set_error(FAD_ERR_INVALID, "fad_kad_sweep: bandwidth %d (%g) is outside the float32 range of the kernel", b, sigma[b]);
+    }
+
+    // passes as fad_kad_k's: XX and YY over their triangles, XY over the rectangle with the larger set as the row operand
+    const bool x_rows = n != m ? n > m : px.norm_sum >= py.norm_sum;
+    double sums[3 * FAD_KAD_MAX_BANDWIDTHS];
+    for (int b0 = 0; b0 < n_bw; b0 += kSweepGroup) {
+        const int gb = std::min(kSweepGroup, n_bw - b0);
+        const PassArgs passes[3] = {pass_args(px, px, true, c[b0]), pass_args(py, py, true, c[b0]),
+                                    pass_args(x_rows ? px : py, x_rows ? py : px, false, c[b0])};
+        if (gb == 1) {                         // fad_kad_k's own kernel, places and order
+            double* sums_d = static_cast<double*>(ws.small.p) + 16;
+            FAD_TRY(sum_passes(passes, dtype, kernel, device, st, ws, sums_d));
+            FAD_HIP_TRY(hipMemcpyAsync(sums + 3 * b0, sums_d, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+            FAD_HIP_TRY(hipStreamSynchronize(st));
+        } else if (gb <= 4) {
+            FAD_TRY(sweep_passes<4>(passes, c + b0, gb, dtype, kernel, device, st, ws, sums + 3 * b0));
+        } else {
+            FAD_TRY(sweep_passes<8>(passes, c + b0, gb, dtype, kernel, device, st, ws, sums + 3 * b0));
+        }
+    }
+
+    for (int b = 0; b < n_bw; ++b) {           // only now: a refusal above leaves `out` as it was
+        fad_kad_result_t& r = out[b];
+        r.kxx_mean = 2.0 * sums[3 * b] / ((double)n * (double)(n - 1));
+        r.kyy_mean = 2.0 * sums[3 * b + 1] / ((double)m * (double)(m - 1));
+        r.kxy_mean = sums[3 * b + 2] / ((double)n * (double)m);
+        r.mmd2 = r.kxx_mean + r.kyy_mean - 2.0 * r.kxy_mean;
+        r.bandwidth = sigma[b];
+        r.n = n;
+        r.m = m;
+    }
     return FAD_OK;
 }
 

@@ -701,6 +701,50 @@ def kad(x, y, bandwidth: Optional[float] = None, device: int = 0, kernel: str = 
     return res.as_dict()
 
 
+KAD_MAX_BANDWIDTHS = 32
+
+
+def kad_sweep_bandwidths(bandwidths=None, factors=None):
+    """-> (float64 array [B], relative): the C ABI's bandwidth list of ``fad_kad_sweep`` and whether it holds factors of the baseline's
+    median distance.  Exactly one of the two is given, 1 .. 32 finite values > 0; anything else is a ValueError, raised before the
+    native library is touched."""
+    if (bandwidths is None) == (factors is None):
+        raise ValueError("KAD sweep: give exactly one of bandwidths (sigma values) and factors (of the baseline's median distance)")
+    what, given = ("factors", factors) if bandwidths is None else ("bandwidths", bandwidths)
+    try:
+        v = np.array(list(given) if not isinstance(given, np.ndarray) else given, dtype=np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        raise ValueError(f"KAD sweep: {what} must be a sequence of numbers, got {given!r}") from None
+    if not 1 <= v.size <= KAD_MAX_BANDWIDTHS:
+        raise ValueError(f"KAD sweep takes 1 .. {KAD_MAX_BANDWIDTHS} {what}, got {v.size}")
+    if not (np.isfinite(v) & (v > 0)).all():
+        raise ValueError(f"KAD sweep: every one of {what} must be finite and > 0, got {v.tolist()}")
+    return np.ascontiguousarray(v), int(bandwidths is None)
+
+
+def kad_sweep(x, y, bandwidths=None, factors=None, device: int = 0, kernel: str = "gaussian") -> dict:
+    """``fad_kad_sweep``: ``kad`` at B bandwidths in one call -- both sets packed once, a tile's dot products formed once for up to 8
+    bandwidths -> dict of float64 arrays ``mmd2``, ``kxx_mean``, ``kyy_mean``, ``kxy_mean``, ``bandwidth`` [B] in the order given, plus
+    ``n`` and ``m``.  ``bandwidths``: the sigma values themselves; ``factors``: multiples of the median pairwise distance of x (found
+    once; the factor 1 is ``kad``'s default).  Exactly one of the two, 1 .. 32 finite values > 0.  Entry b carries the bits of
+    ``kad(x, y, bandwidth=sigma_b)``.  x, y and ``kernel`` as ``kad`` takes them."""
+    kf = kad_kernel_code(kernel)
+    bw, relative = kad_sweep_bandwidths(bandwidths, factors)
+    lib = K.load_library()
+    (px, n, d, ldx, cx, dev_x, kx), (py, m, dy, ldy, cy, dev_y, ky) = _kad_pair(x, y, "y", device)
+    if d != dy:
+        raise ValueError(f"KAD: x has D = {d}, y has D = {dy}")
+    if cx != cy:
+        raise ValueError("KAD: x and y must have the same dtype")
+    B = int(bw.size)
+    res = (K.FadKadResult * B)()
+    K.check(lib.fad_kad_sweep(px, n, ldx, py, m, ldy, d, cx, dev_x, bw.ctypes.data_as(C.POINTER(C.c_double)), B, relative, kf, res,
+                              int(device), K.current_stream_ptr(device)), "fad_kad_sweep")
+    out = {k: np.array([getattr(r, k) for r in res], dtype=np.float64) for k in ("mmd2", "kxx_mean", "kyy_mean", "kxy_mean", "bandwidth")}
+    out.update(n=int(res[0].n), m=int(res[0].m))
+    return out
+
+
 def kad_individual(x, rows, offsets: Sequence[int], bandwidth: Optional[float] = None, device: int = 0,
                    kernel: str = "gaussian") -> dict:
     """``fad_kad_individual_k``: KAD between the baseline rows x and every song s = rows[offsets[s]:offsets[s + 1]], one sigma for all

@@ -18,9 +18,13 @@ Per song (``--indiv``): KAD between the baseline and each file of the evaluation
 one batched GPU call (``fad_kad_individual``); ``path,score`` lines sorted by |score|, like fadtk's per-song FAD.
 
     python -m fadtk_amd.kad <model> <baseline_dir> <eval_dir> [csv] [--bandwidth S] [--kernel K] [--scale F] [-w N] [--indiv]
+    python -m fadtk_amd.kad <model> <baseline_dir> <eval_dir> [csv] --bandwidths S1,S2,... | --bandwidth-factors F1,F2,...
 
 Several evaluation sets against one baseline, with standard errors and paired comparisons (``fad_kad_uncertainty``, a first-order
 estimate): ``calc_kernel_audio_distance_uncertainty`` / ``KernelAudioDistance.score_many``, and ``python -m fadtk_amd.kad_compare``.
+Several bandwidths in one fused GPU call (``fad_kad_sweep``), a ladder around the median by default, and their mixture kernel:
+``calc_kernel_audio_distance_sweep`` / ``KernelAudioDistance.score_sweep``, and ``--bandwidths S1,S2,...`` or
+``--bandwidth-factors F1,F2,...`` on the command line (one CSV row per bandwidth).
 Whether a set is distinguishable from the baseline at all (a two-sample permutation test, ``fad_kad_permutation_test``):
 ``calc_kernel_audio_distance_permutation_test`` / ``KernelAudioDistance.permutation_test``, and ``python -m fadtk_amd.kad_permutation``.
 """
@@ -105,6 +109,56 @@ def calc_kernel_audio_distance(x, y, bandwidth: Optional[float] = None, scale: f
     res = hip.kad(x, y, bandwidth=bandwidth, device=device, kernel=kernel)
     value = float(scale) * res["mmd2"]
     return (value, res) if details else value
+
+
+SWEEP_FACTORS = (0.25, 0.5, 1, 2, 4)         # the default ladder: the baseline's median distance halved and doubled twice
+
+
+@dataclass
+class KadSweep:
+    """KAD at B bandwidths (``fad_kad_sweep``).  ``values`` [B] = scale * MMD^2 at ``bandwidths`` [B] (the sigma values used, in the
+    order asked for); ``mixture`` = the mean of ``values``: scale * MMD^2 under the mixture kernel (1 / B) sum_b k_b, exact by linearity
+    of the U-statistic.  ``details``: hip.kad_sweep's arrays."""
+    values: np.ndarray
+    bandwidths: np.ndarray
+    mixture: float
+    scale: float
+    kernel: str
+    details: dict = field(repr=False, default_factory=dict)
+
+
+def _sweep_request(bandwidths, factors):
+    """-> (bandwidths, factors) with exactly one of them set: ``bandwidths`` overrides the default ``factors``; giving both is a
+    ValueError, as is a list hip.kad_sweep_bandwidths refuses -- before any file is read or the native library is loaded."""
+    from .hip import kad_sweep_bandwidths
+    if bandwidths is not None:
+        if factors is not None and factors is not SWEEP_FACTORS:
+            raise ValueError("KAD sweep: give bandwidths or factors, not both")
+        factors = None
+    kad_sweep_bandwidths(bandwidths, factors)
+    return bandwidths, factors
+
+
+def calc_kernel_audio_distance_sweep(x, y, bandwidths=None, factors=SWEEP_FACTORS, scale: float = 1.0, device: int = 0,
+                                     kernel: str = "gaussian") -> KadSweep:
+    """scale * MMD^2 between the rows of x (baseline) and y at several bandwidths, in one GPU call (``fad_kad_sweep``) -> KadSweep.
+    ``factors`` (default 0.25, 0.5, 1, 2, 4) are multiples of the median pairwise distance of x; ``bandwidths`` gives the sigma values
+    themselves and overrides the default factors (giving both is an error); 1 .. 32 finite values > 0 either way.  Each value carries the
+    bits of calc_kernel_audio_distance at that bandwidth.  Shapes, dtypes and ``kernel`` as calc_kernel_audio_distance takes them."""
+    _check_kernel(kernel)
+    bandwidths, factors = _sweep_request(bandwidths, factors)
+    sx, sy = _shape_of(x), _shape_of(y)
+    if len(sx) != 2 or len(sy) != 2:
+        raise ValueError(f"KAD needs two 2-D row matrices, got shapes {sx} and {sy}")
+    if sx[1] != sy[1]:
+        raise ValueError(f"KAD: the sets have different dimensions ({sx[1]} and {sy[1]})")
+    if sx[0] < 2 or sy[0] < 2:
+        raise ValueError(f"KAD needs at least 2 rows per set, got {sx[0]} and {sy[0]}")
+    from . import hip
+    res = hip.kad_sweep(x, y, bandwidths=bandwidths, factors=factors, device=device, kernel=kernel)
+    scale = float(scale)
+    values = scale * res["mmd2"]
+    return KadSweep(values=values, bandwidths=res["bandwidth"], mixture=float(np.mean(values)), scale=scale, kernel=kernel, details=res)
 
 
 def calc_kernel_audio_distance_individual(x, songs: Sequence, bandwidth: Optional[float] = None, scale: float = 1.0, device: int = 0,
@@ -314,6 +368,23 @@ class KernelAudioDistance:
         return calc_kernel_audio_distance(x, y, bandwidth=bandwidth, scale=scale, device=self.device_index, details=details,
                                           kernel=kernel)
 
+    def score_sweep(self, baseline: PathLike, eval: PathLike, bandwidths=None, factors=SWEEP_FACTORS, scale: float = 1.0,
+                    kernel: str = "gaussian") -> KadSweep:
+        """KAD of ``eval`` against ``baseline`` at several bandwidths in one GPU call (calc_kernel_audio_distance_sweep), the rows
+        narrowed as ``score`` narrows them."""
+        _check_kernel(kernel)
+        bandwidths, factors = _sweep_request(bandwidths, factors)
+        x = self.load_rows(baseline)
+        y = self.load_rows(eval)
+        if x.dtype == np.float64:
+            x = x.astype(np.float32)
+        if y.dtype == np.float64:
+            y = y.astype(np.float32)
+        if x.dtype != y.dtype:
+            x, y = x.astype(np.float32), y.astype(np.float32)
+        return calc_kernel_audio_distance_sweep(x, y, bandwidths=bandwidths, factors=factors, scale=scale, device=self.device_index,
+                                                kernel=kernel)
+
     def score_many(self, baseline: PathLike, eval_dirs: Sequence[PathLike], bandwidth: Optional[float] = None,
                    scale: float = 1.0, kernel: str = "gaussian") -> KadUncertainty:
         """KAD of every directory in ``eval_dirs`` against one baseline, with standard errors and their covariance, in one GPU call
@@ -391,6 +462,11 @@ class KernelAudioDistance:
         return csv
 
 
+def _float_list(text: str):
+    """argparse type of --bandwidths / --bandwidth-factors: comma-separated numbers"""
+    return [float(t) for t in text.split(",")]
+
+
 def main(argv=None):
     from .cli import _registry, _setup_logging
     _setup_logging()
@@ -402,7 +478,12 @@ def main(argv=None):
     p.add_argument("eval", type=str, help="directory to evaluate")
     p.add_argument("csv", type=str, nargs="?", help="append the result to this CSV; with --indiv: where per-song scores go "
                                                     "(default kad-individual-results.csv)")
-    p.add_argument("--bandwidth", type=float, default=None, help="kernel sigma (default: median pairwise distance of the baseline)")
+    bw = p.add_mutually_exclusive_group()
+    bw.add_argument("--bandwidth", type=float, default=None, help="kernel sigma (default: median pairwise distance of the baseline)")
+    bw.add_argument("--bandwidths", type=_float_list, default=None, metavar="S1,S2,...",
+                    help="several kernel sigmas in one fused pass: one CSV row and one printed value per bandwidth (1 .. 32 values > 0)")
+    bw.add_argument("--bandwidth-factors", type=_float_list, default=None, metavar="F1,F2,...",
+                    help="as --bandwidths, each a multiple of the median pairwise distance of the baseline (1 is the default bandwidth)")
     p.add_argument("--kernel", type=str, choices=list(KAD_KERNELS), default="gaussian",
                    help="gaussian exp(-t), iq 1 / (1 + t) or imq 1 / sqrt(1 + t), t = d^2 / (2 sigma^2) (default gaussian); a CSV written "
                         "for iq or imq has one more column, kernel")
@@ -410,6 +491,14 @@ def main(argv=None):
     p.add_argument("-w", "--workers", type=int, default=8, help="number of workers")
     p.add_argument("--indiv", action="store_true", help="one score per song of the eval directory")
     a = p.parse_args(argv)
+    sweep = a.bandwidths is not None or a.bandwidth_factors is not None
+    if sweep and a.indiv:
+        p.error("--bandwidths / --bandwidth-factors cannot be combined with --indiv")
+    if sweep:
+        try:
+            _sweep_request(a.bandwidths, a.bandwidth_factors)
+        except ValueError as e:
+            p.error(str(e))
     model = models[a.model]
     if a.csv and not a.indiv:
         check_csv(a.csv, CSV_HEADER, a.kernel)             # before any work: a CSV of the other form is refused
@@ -424,6 +513,20 @@ def main(argv=None):
         out = Path(a.csv or "kad-individual-results.csv")
         kad.score_individual(a.baseline, a.eval, out, bandwidth=a.bandwidth, scale=a.scale, kernel=a.kernel)
         log.info(f"Individual KAD scores saved to {out}")
+        return
+    if sweep:
+        r = kad.score_sweep(a.baseline, a.eval, bandwidths=a.bandwidths, factors=a.bandwidth_factors, scale=a.scale, kernel=a.kernel)
+        values, sigmas = [float(v) for v in r.values], [float(s) for s in r.bandwidths]
+        if a.csv:                                          # one row per bandwidth; no mixture row: the header has one bandwidth column
+            now = time.time()
+            append_csv(a.csv, CSV_HEADER, [f"{model.name},{a.baseline},{a.eval},{v!r},{s!r},{a.scale!r},{now}" for v, s in zip(values, sigmas)],
+                       a.kernel)
+            log.info(f"{len(values)} KAD scores appended to {a.csv}")
+        for v, s in zip(values, sigmas):
+            log.info(f"The KAD {model.name} score between {a.baseline} and {a.eval} is: {v} (bandwidth {s})")
+        log.info(f"The KAD {model.name} score between {a.baseline} and {a.eval} under the mixture of these {len(values)} kernels is: {r.mixture}")
+        for v in values:
+            print(v)
         return
     value, res = kad.score(a.baseline, a.eval, bandwidth=a.bandwidth, scale=a.scale, details=True, kernel=a.kernel)
     if a.csv:

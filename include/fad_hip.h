@@ -361,6 +361,24 @@ int fad_kad_permutation_test_k(const void* x, int64_t n, int64_t ldx, const void
                                int on_device, double bandwidth, int kernel, const uint32_t* labels, int64_t n_perm,
                                int labels_on_device, fad_kad_result_t* observed, double* null /* [n_perm] host */, double* p_value,
                                int device, void* stream);
+/* ------------------------------------------------------------------ KAD at several bandwidths (bandwidth sweep)
+ * fad_kad_k at n_bw bandwidths (1 .. FAD_KAD_MAX_BANDWIDTHS) in one call: both sets are packed once, and each of the three passes forms
+ * a tile's dot products once for up to 8 bandwidths, whose kernel values go into sums of their own.  relative == 0: bandwidths[b] is
+ * sigma_b itself and no median is computed; relative != 0: bandwidths[b] is a factor, sigma_b = bandwidths[b] * the median pairwise
+ * distance of x (found once; a median of 0 -> FAD_ERR_INVALID), so the factor 1.0 gives fad_kad_k's default result, bandwidth included.
+ * Every entry must be finite and > 0 in both modes ("<= 0 means the median" does not exist here: ask for the factor 1); duplicates and
+ * any order are allowed.  out[b] is fad_kad_k's result for sigma_b, in the caller's order -- bit for bit whenever the two calls cut
+ * their passes into the same launches (always when a pass fits one launch of both: 16-bit rows up to D = 512 at n = m = 100 000, for
+ * one; past that the float32 partial sums are still the same and only the float64 order of adding them differs).  The mean of the
+ * n_bw mmd2 is MMD^2 under the mixture kernel (1 / n_bw) sum_b k_b, exactly, by linearity.  Argument errors come before any device
+ * call, with fad_kad_k's codes: NULL pointers, n_bw outside 1 .. 32, an entry that is not finite and > 0, an unknown kernel, dtype, d,
+ * ld < d, n or m < 2 -> FAD_ERR_TOO_FEW_ROWS.
+ * A NaN/Inf row norm -> FAD_ERR_NOT_FINITE; a sigma_b whose kernel constant leaves float32 -> FAD_ERR_INVALID, the message naming b.
+ * Any refusal fails the whole call and leaves `out` untouched.  No float atomics: the same bits on every run.  Synchronises `stream`. */
+#define FAD_KAD_MAX_BANDWIDTHS 32
+int fad_kad_sweep(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype, int on_device,
+                  const double* bandwidths, int n_bw, int relative, int kernel, fad_kad_result_t* out /* [n_bw] */, int device,
+                  void* stream);
 /* ------------------------------------------------------------------ per-song KAD (--indiv)
  * For every song s (rows [offsets[s], offsets[s+1]) of `rows` [n_rows x d]), KAD between the baseline x [n x d] and that song alone,
  * with one sigma for all songs: what fad_kad(x, song_s, bandwidth = sigma) gives, in one call that packs the baseline, finds sigma
