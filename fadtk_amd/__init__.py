@@ -21,6 +21,7 @@ def __getattr__(name):
     if name in ("KernelAudioDistance", "calc_kernel_audio_distance", "calc_kernel_audio_distance_individual",
                 "calc_kernel_audio_distance_uncertainty", "KadUncertainty",
                 "calc_kernel_audio_distance_permutation_test", "calc_kernel_audio_distance_sweep", "KadSweep",
+                "calc_kernel_audio_distance_aggregated_test",
                 "KAD_KERNELS"):      # lazy: `python -m fadtk_amd.kad` runs the module itself
         from . import kad
         return getattr(kad, name)

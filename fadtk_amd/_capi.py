@@ -145,6 +145,9 @@ SIGNATURES = {
                                              C.c_int, C.POINTER(FadKadResult), _P, C.POINTER(C.c_double), C.c_int, _P]),
     "fad_kad_sweep": (C.c_int, [_P, _I64, _I64, _P, _I64, _I64, _I64, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int,
                                 C.POINTER(FadKadResult), C.c_int, _P]),
+    "fad_kad_permutation_sweep": (C.c_int, [_P, _I64, _I64, _P, _I64, _I64, _I64, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int,
+                                            C.c_int, _P, _I64, C.c_int, C.POINTER(FadKadResult), _P, _P, C.POINTER(C.c_double), C.c_int, _P]),
+    "fad_kad_aggregate": (C.c_int, [_P, C.c_int, _I64, _P, C.POINTER(C.c_double)]),
     "fad_prdc": (C.c_int, [_P, _I64, _I64, _P, _I64, _I64, _I64, C.c_int, C.c_int, C.c_int, C.POINTER(FadPrdcResult),
                            C.POINTER(FadPrdcDetail), C.c_int, _P]),
     "fad_nearest": (C.c_int, [_P, _I64, _I64, _P, _I64, _I64, _I64, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P,

@@ -1,7 +1,7 @@
 // Kernel Audio Distance: the unbiased Gaussian-kernel MMD^2 between two sets of embedding rows, and the median pairwise distance
 // of one set (the default bandwidth).  DESIGN.md 4.6.  Per-song KAD (4.7), the k-NN precision / recall / density / coverage (4.8),
-// KAD's standard errors (4.9), its permutation test (4.10), the nearest baseline rows with authenticity (4.11) and KAD at several
-// bandwidths in one pass (4.12) run on the same main loop.
+// KAD's standard errors (4.9), its permutation test (4.10), the nearest baseline rows with authenticity (4.11), KAD at several
+// bandwidths in one pass (4.12) and the permutation test at several bandwidths, aggregated (4.13) run on the same main loop.
 //
 // Every pass is one GEMM-shaped walk over 128 x 128 tiles of a pair space (kad_tiles.h) whose n x m matrix is never stored:
 //   - pack:   each set is copied once into a zero-padded [n_pad x dp] image of its own dtype (dp: D rounded up to 128 bytes, n_pad:
@@ -22,6 +22,7 @@
 #include "kad_song_tiles.h"
 #include "kad_unc_tiles.h"
 #include "kad_perm_tiles.h"
+#include "kad_perm_sweep_tiles.h"
 
 #include <algorithm>
 #include <cmath>
@@ -614,6 +615,74 @@ __global__ void __launch_bounds__(kThreads, 2) kad_unc_cols_kernel(ColArgs p) {
 
 constexpr size_t kLdsUnc = 2 * kOpBytes + 2 * kTile * 4 + kTile * sizeof(double);
 
+// fad_kad_permutation_sweep's r pass: kad_unc_cols_kernel with NB constants.  A tile's accumulators are formed once and
+// col_sums runs on them once per bandwidth, into that bandwidth's own dcol; at the unit's end bandwidth b's columns meet as above and go
+// to slots[b * bstride + u * kTile + column].  Bandwidth b therefore adds what kad_unc_cols_kernel adds under c[b], in the same order,
+// whatever the launch cut: a unit's slot is written by one workgroup.  Rows b >= nb of the kernel are idle (a uniform branch).
+template <int NB>
+struct ColSweepArgs {
+    ColArgs p;                                 // p.c is not read; p.slots: bandwidth 0's unit slots
+    int nb;
+    int64_t bstride;                           // doubles between two bandwidths' unit slots
+    float c[NB];
+};
+
+template <int DT, int KF, int NB>
+__global__ void __launch_bounds__(kThreads, 2) kad_unc_cols_sweep_kernel(ColSweepArgs<NB> q) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    double* lx = reinterpret_cast<double*>(lds + 2 * kOpBytes + 2 * kTile * 4);       // [NB][kTile]: the wm = 1 waves' column sums of a unit
+    const ColArgs& p = q.p;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
+    const int rbase = wm * 64, cbase = wn * 64;
+    const int64_t G = gridDim.x, nslots = kad::launch_slots(p.cnt);
+
+    for (int64_t L = blockIdx.x; L < nslots; L += G) {
+        bool live;
+        const int64_t v = kad::slot_tile(L, p.cnt, &live);
+        if (!live) continue;                                                          // uniform over the workgroup
+        const int64_t u = p.u0 + v;
+        const kad::Unit un = p.units[u];
+        double dcol[NB][2];
+#pragma unroll
+        for (int b = 0; b < NB; ++b) dcol[b][0] = dcol[b][1] = 0.0;
+
+        for (int64_t I = un.I0; I < un.I1; ++I) {
+            f32x16 acc[2][2];
+            tile_mfma<DT>(p.a, p.b, p.ha, p.hb, p.pitch, p.nchunks, I, un.J, lds, [](int) {}, acc);
+#pragma unroll
+            for (int b = 0; b < NB; ++b) {
+                if (b >= q.nb) continue;                                              // uniform
+                if (I == un.J) col_sums<3, KF>(acc, q.c[b], rbase, cbase, lane, nullptr, true, dcol[b]);
+                else col_sums<0, KF>(acc, q.c[b], rbase, cbase, lane, nullptr, false, dcol[b]);
+            }
+        }
+
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+#pragma unroll
+            for (int bj = 0; bj < 2; ++bj) dcol[b][bj] += __shfl_xor(dcol[b][bj], 32, 64);
+            if (wm == 1 && lane < 32) {
+#pragma unroll
+                for (int bj = 0; bj < 2; ++bj) lx[b * kTile + cbase + bj * 32 + lane] = dcol[b][bj];
+            }
+        }
+        __syncthreads();
+        if (wm == 0 && lane < 32) {
+#pragma unroll
+            for (int b = 0; b < NB; ++b) {
+                if (b >= q.nb) continue;
+                double* slot = p.slots + b * q.bstride + u * kTile;
+#pragma unroll
+                for (int bj = 0; bj < 2; ++bj) slot[cbase + bj * 32 + lane] = dcol[b][bj] + lx[b * kTile + cbase + bj * 32 + lane];
+            }
+        }
+    }
+}
+
+template <int NB>
+constexpr size_t lds_unc_sweep() { return 2 * kOpBytes + 2 * kTile * 4 + NB * kTile * sizeof(double); }
+
 // the sets of an uncertainty call as the reduction kernels see them (passed by value)
 struct UncSets {
     int64_t n, TX;
@@ -874,6 +943,125 @@ __global__ void __launch_bounds__(kThreads, 2) kad_perm_kernel(PermArgs p) {
 
 constexpr size_t kLdsPerm = 2 * kOpBytes + 2 * kTile * 4;
 static_assert(4 * 32 * kad::kPermWords * sizeof(double) <= kLdsPerm, "the slot reduction reuses the tiles' LDS");
+
+// fad_kad_permutation_sweep's pass: kad_perm_kernel with NB pairs (c, c0).  One tile_mfma per tile; then bandwidth by
+// bandwidth the A operands f16(k_b - c0_b) are built from the same accumulators as above and the word loop runs over that bandwidth's
+// words, into row b of the lane's partials: dq[b * (kPermWords / NB) + w], the same kPermWords float64 values per lane.  At the end
+// bandwidth b's partials meet as above and are added into b's own slots, slots[b * bstride + workgroup * 32 nw ..].  Bandwidth b
+// therefore adds what kad_perm_kernel adds under (c[b], c0[b]), in the same order: the same bits wherever the two make the same launch
+// cut.  Rows b >= nb of the kernel are idle (a uniform branch): a run of 3 bandwidths takes the kernel of 4.
+template <int NB>
+struct PermSweepArgs {
+    PermArgs p;                                // p.c and p.c0 are not read; p.nw <= kPermWords / NB; p.slots: bandwidth 0's slots of the walk
+    int nb;
+    int64_t bstride;                           // doubles between two bandwidths' slots: the walk's slots x 32 nw
+    float c[NB], c0[NB];
+};
+
+template <int DT, int KF, int NB>
+__global__ void __launch_bounds__(kThreads, 2) kad_perm_sweep_kernel(PermSweepArgs<NB> q) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    constexpr int NWB = kad::kPermWords / NB;                                         // words per bandwidth at most
+    const PermArgs& p = q.p;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), wm = wave >> 1, wn = wave & 1;
+    const int rbase = wm * 64, cbase = wn * 64, hh = lane >> 5, pl = lane & 31;
+    const int64_t G = gridDim.x, nslots = kad::launch_slots(p.cnt);
+    double dq[kad::kPermWords];
+#pragma unroll
+    for (int w = 0; w < kad::kPermWords; ++w) dq[w] = 0.0;
+
+    for (int64_t L = blockIdx.x; L < nslots; L += G) {
+        bool live;
+        const int64_t v = kad::slot_tile(L, p.cnt, &live);
+        if (!live) continue;                                                          // uniform over the workgroup
+        const kad::Tile t = kad::tri_tile(p.u0 + v, p.TZ);
+        f32x16 acc[2][2];
+        tile_mfma<DT>(p.z, p.z, p.h, p.h, p.pitch, p.nchunks, t.I, t.J, lds, [](int) {}, acc);
+
+        const bool diag = t.I == t.J;
+        int lrow = rbase + 4 * hh - (cbase + pl);
+        asm volatile("" : "+v"(lrow));                        // per tile, not hoisted out of the tile loop as lane masks (tile_sum)
+        const int64_t b0 = t.I * 4 + wm * 2;                                          // the wave's first 32-row word of Z
+        int nb = q.nb;
+        asm volatile("" : "+s"(nb));                          // per tile: the NB tests b < nb are not kept as SGPR pairs around the tile loop
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            if (b >= nb) continue;                                                    // uniform
+            // the A operands of bandwidth b: k_b - c0_b in f16, [bi][bj][k-step s], as kad_perm_kernel builds them
+            f16x8 af[2][2][2];
+#pragma unroll
+            for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+                for (int bj = 0; bj < 2; ++bj)
+#pragma unroll
+                    for (int g = 0; g < 16; ++g) {
+                        float e = kernel_value<KF>(acc[bi][bj][g], q.c[b]) - q.c0[b];  // every read of the accumulator is kernel_value's
+                        if (diag) e = (bj * 32 - bi * 32 - (g & 3) - 8 * (g >> 2)) > lrow ? e : 0.f;
+                        af[bi][bj][g >> 3][g & 7] = (_Float16)e;
+                    }
+
+            // the word loop of kad_perm_kernel over this bandwidth's words (strides and offsets opaque, as there)
+            int64_t rstride = p.z_pad, cstride = p.z_pad;
+            int nw = p.nw;
+            asm volatile("" : "+s"(rstride), "+s"(cstride), "+s"(nw));
+            const uint32_t* rw = p.rowbits + b0 * 32 + pl;
+            int64_t cb = t.J * kTile + cbase;
+#pragma unroll
+            for (int w = 0; w < NWB; ++w, rw += rstride, cb += cstride) {
+                if (w >= nw) continue;                                                // uniform
+                u32x4 bf[2][2];                                                       // [bi][s]
+#pragma unroll
+                for (int bi = 0; bi < 2; ++bi) {
+                    const uint32_t th = rw[bi * 32] >> (8 * hh);
+#pragma unroll
+                    for (int s = 0; s < 2; ++s)
+#pragma unroll
+                        for (int qq = 0; qq < 4; ++qq) bf[bi][s][qq] = (th << (10 - (4 * s + qq))) & kLabelOne;
+                }
+                float sq = 0.f;
+#pragma unroll
+                for (int bj = 0; bj < 2; ++bj) {
+                    int64_t co = cb + bj * 32;
+                    asm volatile("" : "+s"(co));
+                    const kConst uint32_t* cw = (const kConst uint32_t*)p.colbits + co;
+                    f32x16 v2 = {};
+#pragma unroll
+                    for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+                        for (int s = 0; s < 2; ++s)
+                            v2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[bi][bj][s], __builtin_bit_cast(f16x8, bf[bi][s]), v2, 0, 0, 0);
+#pragma unroll
+                    for (int g = 0; g < 16; ++g) {
+                        const int jl = (g & 3) + 8 * (g >> 2);
+                        const uint64_t mask = (uint64_t)cw[jl] | (uint64_t)cw[jl + 4] << 32;
+                        sq += __builtin_amdgcn_inverse_ballot_w64(mask) ? v2[g] : 0.f;
+                    }
+                }
+                dq[b * NWB + w] += (double)sq;
+            }
+        }
+    }
+
+    // a (bandwidth, labelling): the two lane halves, then the four waves in order, into the bandwidth's slot of the workgroup
+    double* lq = reinterpret_cast<double*>(lds);                                      // [4][32 kPermWords]
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < kad::kPermWords; ++i) {
+        if ((i % NWB) >= p.nw || (i / NWB) >= q.nb) continue;
+        const double s = dq[i] + __shfl_xor(dq[i], 32, 64);
+        if (lane < 32) lq[wave * 32 * kad::kPermWords + i * 32 + pl] = s;
+    }
+    __syncthreads();
+    for (int b = 0; b < q.nb; ++b) {
+        double* slot = p.slots + b * q.bstride + (int64_t)blockIdx.x * 32 * p.nw;     // launches of a walk add in order
+        const double* lb = lq + b * NWB * 32;
+        for (int i = tid; i < 32 * p.nw; i += kThreads) {
+            const int o = 32 * kad::kPermWords;
+            slot[i] += ((lb[i] + lb[o + i]) + lb[2 * o + i]) + lb[3 * o + i];
+        }
+    }
+}
 
 // Row words: for labelling word w (labellings 32w .. 32w + 31), 32-row word b of Z and labelling 32w + l, the 32 labels of the rows of
 // word b rearranged for the B fragments: pair k = 4s + q (k-step s, elements 2q, 2q + 1) of lane half h holds rows
@@ -1684,6 +1872,121 @@ static int nearest_pass(const Packed& x, const Packed& y, int k, int dtype, int 
     return FAD_OK;
 }
 
+// The argument checks, the pooled image with its labelling words, and nothing else, of fad_kad_permutation_test_k -- shared with
+// fad_kad_permutation_sweep, which takes the same rows and labellings.
+static int perm_check_args(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype,
+                           const uint32_t* labels, int64_t n_perm) {
+    FAD_TRY(check_rows(x, n, ldx, d, dtype, "fad_kad_permutation_test (x)"));
+    FAD_TRY(check_rows(y, m, ldy, d, dtype, "fad_kad_permutation_test (y)"));
+    if (n_perm < 1 || n_perm > kad::kPermMax)
+        return set_error(FAD_ERR_INVALID, "fad_kad_permutation_test: %lld permutations (1 .. %lld)", (long long)n_perm, (long long)kad::kPermMax);
+    if (!labels) return set_error(FAD_ERR_INVALID, "fad_kad_permutation_test: NULL labels");
+    const int64_t N = n + m;
+    if (N > INT32_MAX - kTile) return set_error(FAD_ERR_INVALID, "fad_kad_permutation_test: %lld rows in all (at most %d)", (long long)N, INT32_MAX - kTile);
+    return FAD_OK;
+}
+
+// host labellings: every one with exactly n ones and no bit at or past N (device labellings are counted on the device)
+static int perm_check_labels(int64_t n, int64_t m, const uint32_t* labels, int64_t n_perm, int labels_on_device) {
+    const int64_t N = n + m;
+    const int64_t nwl = cdiv(N, 32);                                                   // words per labelling in the ABI
+    if (!labels_on_device) {
+        const uint32_t tail = N % 32 ? (1u << (N % 32)) - 1u : 0xffffffffu;
+        for (int64_t q = 0; q < n_perm; ++q) {
+            const uint32_t* row = labels + q * nwl;
+            int64_t ones = 0;
+            for (int64_t b = 0; b < nwl; ++b) ones += __builtin_popcount(row[b]);
+            if (ones != n || (row[nwl - 1] & ~tail))
+                return set_error(FAD_ERR_INVALID, "fad_kad_permutation_test: labelling %lld has %lld ones%s; every labelling needs exactly n = %lld"
+                                 " and no bit at or past N = %lld", (long long)q, (long long)ones, (row[nwl - 1] & ~tail) ? " and a bit past N" : "",
+                                 (long long)n, (long long)N);
+        }
+    }
+    return FAD_OK;
+}
+
+// Z's image and h, the labellings (the observed one first) and their row and column words, all on the device
+struct PermPrep {
+    char* zimg; float* zh;
+    int64_t N, TZ, z_pad, nwz, dp, pitch, NL, W;
+    uint32_t* lab; uint32_t* rows_d; uint32_t* cols_d;
+    double norm_sum;
+};
+
+static int perm_prepare(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype, int on_device,
+                        const uint32_t* labels, int64_t n_perm, int labels_on_device, hipStream_t st, KadWorkspace& ws, PermPrep* out) {
+    const int64_t N = n + m, nwl = cdiv(N, 32);
+    // Z = [X; Y] in one image, contiguously: kad_pack_kernel at row 0 (n rows, no padding) and at row n (Y, then Z's padding rows)
+    const size_t es = dtype_size(dtype);
+    const int64_t TZ = kad::blocks(N), z_pad = TZ * kTile, nwz = z_pad / 32, dp = depth_elems(d, dtype), pitch = dp * (int64_t)es;
+    const int64_t NL = n_perm + 1, W = kad::perm_words(NL);                            // labellings with the observed one; their words
+    FAD_TRY(ws.img[0].reserve((size_t)(z_pad * pitch)));
+    FAD_TRY(ws.h[0].reserve((size_t)z_pad * sizeof(float)));
+    FAD_TRY(ws.small.reserve(4096 * sizeof(double) + 2 * kHistBins * sizeof(unsigned long long)));
+    if (!on_device) FAD_TRY(ws.raw[0].reserve((size_t)(N * d) * es));
+    char* zimg = static_cast<char*>(ws.img[0].p);
+    float* zh = static_cast<float*>(ws.h[0].p);
+    for (int s = 0; s < 2; ++s) {
+        const void* src = s ? y : x;
+        int64_t rn = s ? m : n, ld = s ? ldy : ldx;
+        const int64_t r0 = s ? n : 0, r_pad = s ? z_pad - n : n;
+        if (!on_device) {
+            char* raw = static_cast<char*>(ws.raw[0].p) + (size_t)(r0 * d) * es;
+            FAD_HIP_TRY(hipMemcpy2DAsync(raw, (size_t)d * es, src, (size_t)ld * es, (size_t)d * es, (size_t)rn, hipMemcpyHostToDevice, st));
+            src = raw;
+            ld = d;
+        }
+        const dim3 grid((unsigned)cdiv(r_pad, 4));
+        char* img = zimg + r0 * pitch;
+        switch (dtype) {
+            case FAD_F16: kad_pack_kernel<_Float16><<<grid, 256, 0, st>>>(static_cast<const _Float16*>(src), rn, ld, d, reinterpret_cast<_Float16*>(img), dp, r_pad, zh + r0); break;
+            case FAD_BF16: kad_pack_kernel<__bf16><<<grid, 256, 0, st>>>(static_cast<const __bf16*>(src), rn, ld, d, reinterpret_cast<__bf16*>(img), dp, r_pad, zh + r0); break;
+            default: kad_pack_kernel<float><<<grid, 256, 0, st>>>(static_cast<const float*>(src), rn, ld, d, reinterpret_cast<float*>(img), dp, r_pad, zh + r0); break;
+        }
+        FAD_HIP_TRY(hipGetLastError());
+    }
+    double* info_d = static_cast<double*>(ws.small.p) + 1024;                          // norm sum, non-finite rows, bad labellings
+    unsigned long long* bad_d = reinterpret_cast<unsigned long long*>(info_d + 2);
+    kad_norm_info_kernel<<<1, 256, 0, st>>>(zh, N, info_d);
+    FAD_HIP_TRY(hipGetLastError());
+
+    // the labellings: the observed one (Z's first n rows), then the caller's, at a row pitch of nwz words (Z's padding rows are 0)
+    FAD_TRY(ws.perm_lab.reserve((size_t)(NL * nwz) * sizeof(uint32_t)));
+    uint32_t* lab = static_cast<uint32_t*>(ws.perm_lab.p);
+    std::vector<uint32_t> obs_row((size_t)nwz, 0u);
+    for (int64_t b = 0; b < n / 32; ++b) obs_row[(size_t)b] = 0xffffffffu;
+    if (n % 32) obs_row[(size_t)(n / 32)] = (1u << (n % 32)) - 1u;
+    FAD_HIP_TRY(hipMemsetAsync(lab, 0, (size_t)(NL * nwz) * sizeof(uint32_t), st));
+    FAD_HIP_TRY(hipMemcpyAsync(lab, obs_row.data(), (size_t)nwz * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    FAD_HIP_TRY(hipMemcpy2DAsync(lab + nwz, (size_t)nwz * sizeof(uint32_t), labels, (size_t)nwl * sizeof(uint32_t), (size_t)nwl * sizeof(uint32_t),
+                                 (size_t)n_perm, labels_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+    FAD_HIP_TRY(hipMemsetAsync(bad_d, 0, sizeof(unsigned long long), st));
+    kad_perm_check_kernel<<<(unsigned)n_perm, 256, 0, st>>>(lab, nwz, N, n, bad_d);
+    FAD_HIP_TRY(hipGetLastError());
+    double info[2];
+    unsigned long long bad = 0;
+    FAD_HIP_TRY(hipMemcpyAsync(info, info_d, sizeof(info), hipMemcpyDeviceToHost, st));
+    FAD_HIP_TRY(hipMemcpyAsync(&bad, bad_d, sizeof(bad), hipMemcpyDeviceToHost, st));
+    FAD_HIP_TRY(hipStreamSynchronize(st));
+    if (bad) return set_error(FAD_ERR_INVALID, "fad_kad_permutation_test: %llu labellings do not have exactly n = %lld ones below N = %lld", bad,
+                              (long long)n, (long long)N);
+    if (info[1] != 0.0)
+        return set_error(FAD_ERR_NOT_FINITE, "KAD: %lld of %lld rows of x and y have a NaN/Inf norm", (long long)info[1], (long long)N);
+
+    // the row and column words of every labelling word
+    FAD_TRY(ws.perm_rows.reserve((size_t)(W * z_pad) * sizeof(uint32_t)));
+    FAD_TRY(ws.perm_cols.reserve((size_t)(W * z_pad) * sizeof(uint32_t)));
+    uint32_t* rows_d = static_cast<uint32_t*>(ws.perm_rows.p);
+    uint32_t* cols_d = static_cast<uint32_t*>(ws.perm_cols.p);
+    kad_perm_rowbits_kernel<<<(unsigned)cdiv(W * z_pad, 256), 256, 0, st>>>(lab, NL, nwz, W, rows_d);
+    FAD_HIP_TRY(hipGetLastError());
+    kad_perm_colbits_kernel<<<(unsigned)cdiv(W * cdiv(nwz, 2), 4), 256, 0, st>>>(lab, NL, nwz, W, cols_d);
+    FAD_HIP_TRY(hipGetLastError());
+
+    *out = PermPrep{zimg, zh, N, TZ, z_pad, nwz, dp, pitch, NL, W, lab, rows_d, cols_d, info[0]};
+    return FAD_OK;
+}
+
 }  // namespace
 
 }  // namespace fad
@@ -2277,103 +2580,27 @@ int fad_kad_permutation_test_k(const void* x, int64_t n, int64_t ldx, const void
     using namespace fad;
     if (!observed || !null_out || !p_value) return set_error(FAD_ERR_INVALID, "fad_kad_permutation_test: NULL output");
     FAD_TRY(check_kernel(kernel, "fad_kad_permutation_test"));
-    FAD_TRY(check_rows(x, n, ldx, d, dtype, "fad_kad_permutation_test (x)"));
-    FAD_TRY(check_rows(y, m, ldy, d, dtype, "fad_kad_permutation_test (y)"));
-    if (n_perm < 1 || n_perm > kad::kPermMax)
-        return set_error(FAD_ERR_INVALID, "fad_kad_permutation_test: %lld permutations (1 .. %lld)", (long long)n_perm, (long long)kad::kPermMax);
-    if (!labels) return set_error(FAD_ERR_INVALID, "fad_kad_permutation_test: NULL labels");
-    const int64_t N = n + m;
-    if (N > INT32_MAX - kTile) return set_error(FAD_ERR_INVALID, "fad_kad_permutation_test: %lld rows in all (at most %d)", (long long)N, INT32_MAX - kTile);
+    FAD_TRY(perm_check_args(x, n, ldx, y, m, ldy, d, dtype, labels, n_perm));
     if (std::isnan(bandwidth) || std::isinf(bandwidth))
         return set_error(FAD_ERR_INVALID, "fad_kad_permutation_test: bandwidth %g is not finite", bandwidth);
-    const int64_t nwl = cdiv(N, 32);                                                   // words per labelling in the ABI
-    if (!labels_on_device) {
-        const uint32_t tail = N % 32 ? (1u << (N % 32)) - 1u : 0xffffffffu;
-        for (int64_t q = 0; q < n_perm; ++q) {
-            const uint32_t* row = labels + q * nwl;
-            int64_t ones = 0;
-            for (int64_t b = 0; b < nwl; ++b) ones += __builtin_popcount(row[b]);
-            if (ones != n || (row[nwl - 1] & ~tail))
-                return set_error(FAD_ERR_INVALID, "fad_kad_permutation_test: labelling %lld has %lld ones%s; every labelling needs exactly n = %lld"
-                                 " and no bit at or past N = %lld", (long long)q, (long long)ones, (row[nwl - 1] & ~tail) ? " and a bit past N" : "",
-                                 (long long)n, (long long)N);
-        }
-    }
+    FAD_TRY(perm_check_labels(n, m, labels, n_perm, labels_on_device));
     FAD_TRY(check_device(device));
     DeviceGuard g(device);
     if (!g.ok) return set_error(FAD_ERR_HIP, "hipSetDevice(%d) failed", device);
     hipStream_t st = static_cast<hipStream_t>(stream);
     KadWorkspace& ws = workspace(device);
 
-    // Z = [X; Y] in one image, contiguously: kad_pack_kernel at row 0 (n rows, no padding) and at row n (Y, then Z's padding rows)
-    const size_t es = dtype_size(dtype);
-    const int64_t TZ = kad::blocks(N), z_pad = TZ * kTile, nwz = z_pad / 32, dp = depth_elems(d, dtype), pitch = dp * (int64_t)es;
-    const int64_t NL = n_perm + 1, W = kad::perm_words(NL);                            // labellings with the observed one; their words
-    FAD_TRY(ws.img[0].reserve((size_t)(z_pad * pitch)));
-    FAD_TRY(ws.h[0].reserve((size_t)z_pad * sizeof(float)));
-    FAD_TRY(ws.small.reserve(4096 * sizeof(double) + 2 * kHistBins * sizeof(unsigned long long)));
-    if (!on_device) FAD_TRY(ws.raw[0].reserve((size_t)(N * d) * es));
-    char* zimg = static_cast<char*>(ws.img[0].p);
-    float* zh = static_cast<float*>(ws.h[0].p);
-    for (int s = 0; s < 2; ++s) {
-        const void* src = s ? y : x;
-        int64_t rn = s ? m : n, ld = s ? ldy : ldx;
-        const int64_t r0 = s ? n : 0, r_pad = s ? z_pad - n : n;
-        if (!on_device) {
-            char* raw = static_cast<char*>(ws.raw[0].p) + (size_t)(r0 * d) * es;
-            FAD_HIP_TRY(hipMemcpy2DAsync(raw, (size_t)d * es, src, (size_t)ld * es, (size_t)d * es, (size_t)rn, hipMemcpyHostToDevice, st));
-            src = raw;
-            ld = d;
-        }
-        const dim3 grid((unsigned)cdiv(r_pad, 4));
-        char* img = zimg + r0 * pitch;
-        switch (dtype) {
-            case FAD_F16: kad_pack_kernel<_Float16><<<grid, 256, 0, st>>>(static_cast<const _Float16*>(src), rn, ld, d, reinterpret_cast<_Float16*>(img), dp, r_pad, zh + r0); break;
-            case FAD_BF16: kad_pack_kernel<__bf16><<<grid, 256, 0, st>>>(static_cast<const __bf16*>(src), rn, ld, d, reinterpret_cast<__bf16*>(img), dp, r_pad, zh + r0); break;
-            default: kad_pack_kernel<float><<<grid, 256, 0, st>>>(static_cast<const float*>(src), rn, ld, d, reinterpret_cast<float*>(img), dp, r_pad, zh + r0); break;
-        }
-        FAD_HIP_TRY(hipGetLastError());
-    }
-    double* info_d = static_cast<double*>(ws.small.p) + 1024;                          // norm sum, non-finite rows, bad labellings
-    unsigned long long* bad_d = reinterpret_cast<unsigned long long*>(info_d + 2);
-    kad_norm_info_kernel<<<1, 256, 0, st>>>(zh, N, info_d);
-    FAD_HIP_TRY(hipGetLastError());
-
-    // the labellings: the observed one (Z's first n rows), then the caller's, at a row pitch of nwz words (Z's padding rows are 0)
-    FAD_TRY(ws.perm_lab.reserve((size_t)(NL * nwz) * sizeof(uint32_t)));
-    uint32_t* lab = static_cast<uint32_t*>(ws.perm_lab.p);
-    std::vector<uint32_t> obs_row((size_t)nwz, 0u);
-    for (int64_t b = 0; b < n / 32; ++b) obs_row[(size_t)b] = 0xffffffffu;
-    if (n % 32) obs_row[(size_t)(n / 32)] = (1u << (n % 32)) - 1u;
-    FAD_HIP_TRY(hipMemsetAsync(lab, 0, (size_t)(NL * nwz) * sizeof(uint32_t), st));
-    FAD_HIP_TRY(hipMemcpyAsync(lab, obs_row.data(), (size_t)nwz * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    FAD_HIP_TRY(hipMemcpy2DAsync(lab + nwz, (size_t)nwz * sizeof(uint32_t), labels, (size_t)nwl * sizeof(uint32_t), (size_t)nwl * sizeof(uint32_t),
-                                 (size_t)n_perm, labels_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-    FAD_HIP_TRY(hipMemsetAsync(bad_d, 0, sizeof(unsigned long long), st));
-    kad_perm_check_kernel<<<(unsigned)n_perm, 256, 0, st>>>(lab, nwz, N, n, bad_d);
-    FAD_HIP_TRY(hipGetLastError());
-    double info[2];
-    unsigned long long bad = 0;
-    FAD_HIP_TRY(hipMemcpyAsync(info, info_d, sizeof(info), hipMemcpyDeviceToHost, st));
-    FAD_HIP_TRY(hipMemcpyAsync(&bad, bad_d, sizeof(bad), hipMemcpyDeviceToHost, st));
-    FAD_HIP_TRY(hipStreamSynchronize(st));
-    if (bad) return set_error(FAD_ERR_INVALID, "fad_kad_permutation_test: %llu labellings do not have exactly n = %lld ones below N = %lld", bad,
-                              (long long)n, (long long)N);
-    if (info[1] != 0.0)
-        return set_error(FAD_ERR_NOT_FINITE, "KAD: %lld of %lld rows of x and y have a NaN/Inf norm", (long long)info[1], (long long)N);
-
-    // the row and column words of every labelling word
-    FAD_TRY(ws.perm_rows.reserve((size_t)(W * z_pad) * sizeof(uint32_t)));
-    FAD_TRY(ws.perm_cols.reserve((size_t)(W * z_pad) * sizeof(uint32_t)));
-    uint32_t* rows_d = static_cast<uint32_t*>(ws.perm_rows.p);
-    uint32_t* cols_d = static_cast<uint32_t*>(ws.perm_cols.p);
-    kad_perm_rowbits_kernel<<<(unsigned)cdiv(W * z_pad, 256), 256, 0, st>>>(lab, NL, nwz, W, rows_d);
-    FAD_HIP_TRY(hipGetLastError());
-    kad_perm_colbits_kernel<<<(unsigned)cdiv(W * cdiv(nwz, 2), 4), 256, 0, st>>>(lab, NL, nwz, W, cols_d);
-    FAD_HIP_TRY(hipGetLastError());
+    PermPrep pp;
+    FAD_TRY(perm_prepare(x, n, ldx, y, m, ldy, d, dtype, on_device, labels, n_perm, labels_on_device, st, ws, &pp));
+    char* zimg = pp.zimg;
+    float* zh = pp.zh;
+    uint32_t* lab = pp.lab;
+    uint32_t* rows_d = pp.rows_d;
+    uint32_t* cols_d = pp.cols_d;
+    const int64_t N = pp.N, TZ = pp.TZ, z_pad = pp.z_pad, nwz = pp.nwz, dp = pp.dp, pitch = pp.pitch, NL = pp.NL, W = pp.W;
 
     // sigma: the given one, or the median pairwise distance of Z (fad_kad_median_distance on the pooled rows, bit for bit)
-    const Packed pz{zimg, zh, N, pitch, (int)(pitch / kChunk), info[0]};
+    const Packed pz{zimg, zh, N, pitch, (int)(pitch / kChunk), pp.norm_sum};
     double sigma;
     float c;
     FAD_TRY(resolve_sigma(pz, bandwidth, kernel, dtype, device, st, ws, "fad_kad_permutation_test", &sigma, &c));
@@ -2481,6 +2708,216 @@ int fad_kad_permutation_test_k(const void* x, int64_t n, int64_t ldx, const void
         ge += t[(size_t)q + 1] >= t[0];
     }
     *p_value = (double)(1 + ge) / (double)(n_perm + 1);
+    return FAD_OK;
+}
+
+int fad_kad_aggregate(const double* t, int n_bw, int64_t n_lab, double* p_values, double* p_aggregated) {
+    using namespace fad;
+    if (!t || !p_values || !p_aggregated) return set_error(FAD_ERR_INVALID, "fad_kad_aggregate: NULL argument");
+    if (n_bw < 1) return set_error(FAD_ERR_INVALID, "fad_kad_aggregate: %d bandwidths; at least 1", n_bw);
+    if (n_lab < 2 || n_lab > kad::kPermMax + 1)
+        return set_error(FAD_ERR_INVALID, "fad_kad_aggregate: %lld labellings (the observed one and 1 .. %lld more)", (long long)n_lab,
+                         (long long)kad::kPermMax);
+    kad::perm_aggregate(t, n_bw, n_lab, p_values, p_aggregated);
+    return FAD_OK;
+}
+
+int fad_kad_permutation_sweep(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype,
+                              int on_device, const double* bandwidths, int n_bw, int relative, int kernel, const uint32_t* labels,
+                              int64_t n_perm, int labels_on_device, fad_kad_result_t* observed, double* null_out, double* p_values,
+                              double* p_aggregated, int device, void* stream) {
+    using namespace fad;
+    const char* who = "fad_kad_permutation_sweep";
+    if (!observed || !null_out || !p_values || !p_aggregated) return set_error(FAD_ERR_INVALID, "%s: NULL output", who);
+    if (!bandwidths) return set_error(FAD_ERR_INVALID, "%s: NULL bandwidths", who);
+    if (n_bw < 1 || n_bw > FAD_KAD_PERM_MAX_BANDWIDTHS)
+        return set_error(FAD_ERR_INVALID, "%s: %d bandwidths, outside 1 .. %d", who, n_bw, FAD_KAD_PERM_MAX_BANDWIDTHS);
+    FAD_TRY(check_kernel(kernel, who));
+    FAD_TRY(perm_check_args(x, n, ldx, y, m, ldy, d, dtype, labels, n_perm));
+    for (int b = 0; b < n_bw; ++b)
+        if (!(bandwidths[b] > 0) || !std::isfinite(bandwidths[b]))
+            return set_error(FAD_ERR_INVALID, "%s: %s %d is %g; every one must be finite and > 0 (the pooled median is the factor 1)", who,
+                             relative ? "factor" : "bandwidth", b, bandwidths[b]);
+    FAD_TRY(perm_check_labels(n, m, labels, n_perm, labels_on_device));
+    FAD_TRY(check_device(device));
+    DeviceGuard g(device);
+    if (!g.ok) return set_error(FAD_ERR_HIP, "hipSetDevice(%d) failed", device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    KadWorkspace& ws = workspace(device);
+
+    PermPrep pp;
+    FAD_TRY(perm_prepare(x, n, ldx, y, m, ldy, d, dtype, on_device, labels, n_perm, labels_on_device, st, ws, &pp));
+    const int64_t N = pp.N, TZ = pp.TZ, z_pad = pp.z_pad, nwz = pp.nwz, dp = pp.dp, pitch = pp.pitch, NL = pp.NL;
+    const Packed pz{pp.zimg, pp.zh, N, pitch, (int)(pitch / kChunk), pp.norm_sum};
+
+    // sigma_b: the given ones, or factors of the median pairwise distance of Z (found once); c_b as fad_kad_sweep forms it
+    double median = 1.0;
+    if (relative) {
+        FAD_TRY(median_of_packed(pz, dtype, device, st, ws, &median));
+        if (!(median > 0) || !std::isfinite(median))
+            return set_error(FAD_ERR_INVALID, "%s: the median pairwise distance of the pooled rows is %g; it must be > 0 -- are all rows"
+                             " identical?", who, median);
+    }
+    const int B = n_bw;
+    double sigma[FAD_KAD_PERM_MAX_BANDWIDTHS];
+    float c[FAD_KAD_PERM_MAX_BANDWIDTHS], c0[FAD_KAD_PERM_MAX_BANDWIDTHS];
+    for (int b = 0; b < B; ++b) {
+        sigma[b] = relative ? bandwidths[b] * median : bandwidths[b];
+        if (sigma_constant(sigma[b], kernel, &c[b]) != SIGMA_OK)
+            return set_error(FAD_ERR_INVALID, "%s: bandwidth %d (%g) is outside the float32 range of the kernel", who, b, sigma[b]);
+    }
+
+    // the r pass's units are fad_kad_permutation_test_k's: a unit's slot is one workgroup's, so r_b has the single call's bits at any size
+    const bool f32 = dtype == FAD_F32;
+    const std::vector<int64_t> blk = kad::unc_blocks(N, nullptr, 0);
+    const int64_t rr = kad::unc_rows_per_unit(kad::unc_tiles(blk), kad::tiles_per_launch_for(dp, f32, kad::kUncEpilogue));
+    std::vector<kad::Unit> units;
+    std::vector<int64_t> seg_start;
+    kad::unc_units(blk, rr, &units, &seg_start);
+    const int64_t U = (int64_t)units.size();
+
+    // the walks of the permutation pass; per bandwidth its word groups as kad_perm_stats_kernel reads them: walk i holds its bandwidths'
+    // slots one after the other, [nb][walk slots][32 nw]
+    const std::vector<kad::PermSweepWalk> walks = kad::perm_sweep_walks(B, NL);
+    std::vector<int64_t> wslots;
+    const std::vector<kad::PermSweepLaunch> pl = kad::perm_sweep_launches(TZ, walks, dp, f32, grid_cap(device), &wslots);
+    int64_t ngmax = 1, nslot_doubles = 0;
+    for (const kad::PermSweepWalk& w : walks) ngmax = std::max(ngmax, w.wgs);
+    std::vector<PermGroup> groups((size_t)(B * ngmax));
+    std::vector<int> ngs((size_t)B, 0);
+    std::vector<int64_t> walk_off(walks.size());
+    for (size_t i = 0; i < walks.size(); ++i) {
+        const kad::PermSweepWalk& w = walks[i];
+        walk_off[i] = nslot_doubles;
+        const int64_t per_bw = wslots[i] * 32 * w.nw;
+        for (int b = 0; b < w.nb; ++b) {
+            groups[(size_t)((w.b0 + b) * ngmax + w.wg)] = PermGroup{w.w0, w.nw, nslot_doubles + b * per_bw, wslots[i]};
+            ngs[(size_t)(w.b0 + b)] = (int)w.wgs;
+        }
+        nslot_doubles += w.nb * per_bw;
+    }
+
+    // units | seg_start | r [B][z_pad] | T [B] | groups [B][ngmax] | t [B][NL] | observed sums [B][3] | permutation slots
+    size_t at[9];
+    at[0] = 0;
+    at[1] = at[0] + align256((size_t)U * sizeof(kad::Unit));
+    at[2] = at[1] + align256(seg_start.size() * sizeof(int64_t));
+    at[3] = at[2] + align256((size_t)(B * z_pad) * sizeof(double));
+    at[4] = at[3] + align256((size_t)B * sizeof(double));
+    at[5] = at[4] + align256(groups.size() * sizeof(PermGroup));
+    at[6] = at[5] + align256((size_t)(B * NL) * sizeof(double));
+    at[7] = at[6] + align256((size_t)(3 * B) * sizeof(double));
+    at[8] = at[7] + align256((size_t)nslot_doubles * sizeof(double));
+    FAD_TRY(ws.perm.reserve(at[8]));
+    const int rg = std::min(B, kad::kPermSweepNB);                                     // bandwidths per r pass at most
+    FAD_TRY(ws.unc_slots.reserve((size_t)(rg * U * kTile) * sizeof(double)));
+    char* pb = static_cast<char*>(ws.perm.p);
+    kad::Unit* units_d = reinterpret_cast<kad::Unit*>(pb + at[0]);
+    int64_t* seg_d = reinterpret_cast<int64_t*>(pb + at[1]);
+    double* r_d = reinterpret_cast<double*>(pb + at[2]);
+    double* tot_d = reinterpret_cast<double*>(pb + at[3]);
+    PermGroup* groups_d = reinterpret_cast<PermGroup*>(pb + at[4]);
+    double* t_d = reinterpret_cast<double*>(pb + at[5]);
+    double* obs_d = reinterpret_cast<double*>(pb + at[6]);
+    double* pslots = reinterpret_cast<double*>(pb + at[7]);
+    FAD_HIP_TRY(hipMemcpyAsync(units_d, units.data(), (size_t)U * sizeof(kad::Unit), hipMemcpyHostToDevice, st));
+    FAD_HIP_TRY(hipMemcpyAsync(seg_d, seg_start.data(), seg_start.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    FAD_HIP_TRY(hipMemcpyAsync(groups_d, groups.data(), groups.size() * sizeof(PermGroup), hipMemcpyHostToDevice, st));
+
+    // r_b = K_b'1 and T_b = 1'r_b, up to kPermSweepNB bandwidths per walk over Z x Z; a launch of NB bandwidths weighs NB epilogues
+    ColArgs ca{};
+    ca.a = ca.b = pp.zimg; ca.ha = ca.hb = pp.zh; ca.pitch = pitch; ca.nchunks = pz.nchunks;
+    ca.units = units_d; ca.slots = static_cast<double*>(ws.unc_slots.p); ca.slot_pitch = kTile;
+    for (int b0 = 0; b0 < B; b0 += kad::kPermSweepNB) {
+        const int nb = std::min(kad::kPermSweepNB, B - b0), knb = kad::perm_sweep_kernel_nb(nb);
+        const int64_t per = std::max<int64_t>(1, kad::tiles_per_launch_for(dp, f32, kad::kUncEpilogue * knb) / rr);
+        for (const kad::Launch& l : kad::launches(U, knb == 1 ? kad::unc_units_per_launch(rr, dp, f32) : per, grid_cap(device))) {
+            ca.u0 = l.u0; ca.cnt = l.cnt; ca.c = c[b0];
+            auto sweep = [&](auto nbc) {
+                constexpr int NB = decltype(nbc)::value;
+                ColSweepArgs<NB> q;
+                q.p = ca; q.nb = nb; q.bstride = U * kTile;
+                for (int b = 0; b < NB; ++b) q.c[b] = c[b0 + std::min(b, nb - 1)];
+                return with_dtype_kernel(dtype, kernel, [&](auto dt, auto kf) {
+                    kad_unc_cols_sweep_kernel<dt, kf, NB><<<(unsigned)l.grid, kThreads, lds_unc_sweep<NB>(), st>>>(q);
+                });
+            };
+            if (knb == 1) {
+                FAD_TRY(with_dtype_kernel(dtype, kernel, [&](auto dt, auto kf) {
+                    kad_unc_cols_kernel<dt, kf><<<(unsigned)l.grid, kThreads, kLdsUnc, st>>>(ca);
+                }));
+            } else if (knb == 2) {
+                FAD_TRY(sweep(std::integral_constant<int, 2>{}));
+            } else {
+                FAD_TRY(sweep(std::integral_constant<int, 4>{}));
+            }
+        }
+        for (int b = 0; b < nb; ++b) {
+            kad_perm_rows_kernel<<<(unsigned)cdiv(z_pad, 256), 256, 0, st>>>(ca.slots + b * U * kTile, seg_d, N, z_pad, r_d + (b0 + b) * z_pad);
+            FAD_HIP_TRY(hipGetLastError());
+            kad_perm_total_kernel<<<1, 256, 0, st>>>(r_d + (b0 + b) * z_pad, N, tot_d + b0 + b);
+            FAD_HIP_TRY(hipGetLastError());
+        }
+    }
+    double T[FAD_KAD_PERM_MAX_BANDWIDTHS];
+    FAD_HIP_TRY(hipMemcpyAsync(T, tot_d, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
+    FAD_HIP_TRY(hipStreamSynchronize(st));
+    // the shift of bandwidth b: the mean off-diagonal kernel value of Z under sigma_b, as the single call's under a given sigma
+    for (int b = 0; b < B; ++b) c0[b] = (float)(T[b] / ((double)N * (double)(N - 1)));
+
+    FAD_HIP_TRY(hipMemsetAsync(pslots, 0, (size_t)nslot_doubles * sizeof(double), st));
+    PermArgs pa{};
+    pa.z = pp.zimg; pa.h = pp.zh; pa.pitch = pitch; pa.nchunks = pz.nchunks; pa.TZ = TZ; pa.nwz = nwz; pa.z_pad = z_pad;
+    for (const kad::PermSweepLaunch& l : pl) {
+        const kad::PermSweepWalk& w = walks[(size_t)l.walk];
+        pa.nw = (int)w.nw; pa.u0 = l.u0; pa.cnt = l.cnt;
+        pa.rowbits = pp.rows_d + w.w0 * z_pad;
+        pa.colbits = pp.cols_d + w.w0 * z_pad;
+        pa.slots = pslots + walk_off[(size_t)l.walk];
+        pa.c = c[w.b0]; pa.c0 = c0[w.b0];
+        auto sweep = [&](auto nbc) {
+            constexpr int NB = decltype(nbc)::value;
+            PermSweepArgs<NB> q;
+            q.p = pa; q.nb = w.nb; q.bstride = wslots[(size_t)l.walk] * 32 * w.nw;
+            for (int b = 0; b < NB; ++b) { q.c[b] = c[w.b0 + std::min(b, w.nb - 1)]; q.c0[b] = c0[w.b0 + std::min(b, w.nb - 1)]; }
+            return with_dtype_kernel(dtype, kernel, [&](auto dt, auto kf) {
+                kad_perm_sweep_kernel<dt, kf, NB><<<(unsigned)l.grid, kThreads, kLdsPerm, st>>>(q);
+            });
+        };
+        if (w.kernel_nb == 1) {                // one bandwidth: fad_kad_permutation_test_k's own kernel and cut
+            FAD_TRY(with_dtype_kernel(dtype, kernel, [&](auto dt, auto kf) {
+                kad_perm_kernel<dt, kf><<<(unsigned)l.grid, kThreads, kLdsPerm, st>>>(pa);
+            }));
+        } else if (w.kernel_nb == 2) {
+            FAD_TRY(sweep(std::integral_constant<int, 2>{}));
+        } else {
+            FAD_TRY(sweep(std::integral_constant<int, 4>{}));
+        }
+    }
+    for (int b = 0; b < B; ++b) {
+        kad_perm_stats_kernel<<<(unsigned)NL, 256, 0, st>>>(pslots, groups_d + b * ngmax, ngs[(size_t)b], pp.lab, nwz, r_d + b * z_pad, tot_d + b,
+                                                            (double)c0[b], n, m, t_d + b * NL, obs_d + 3 * b);
+        FAD_HIP_TRY(hipGetLastError());
+    }
+    std::vector<double> t((size_t)(B * NL));
+    double obs[3 * FAD_KAD_PERM_MAX_BANDWIDTHS];
+    FAD_HIP_TRY(hipMemcpyAsync(t.data(), t_d, t.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    FAD_HIP_TRY(hipMemcpyAsync(obs, obs_d, (size_t)(3 * B) * sizeof(double), hipMemcpyDeviceToHost, st));
+    FAD_HIP_TRY(hipStreamSynchronize(st));
+
+    const double nd = (double)n, md = (double)m;
+    for (int b = 0; b < B; ++b) {              // only now: a refusal above leaves the outputs as they were
+        fad_kad_result_t& r = observed[b];
+        r.mmd2 = t[(size_t)(b * NL)];
+        r.kxx_mean = obs[3 * b] / (nd * (nd - 1.0));
+        r.kyy_mean = obs[3 * b + 1] / (md * (md - 1.0));
+        r.kxy_mean = obs[3 * b + 2] / (nd * md);
+        r.bandwidth = sigma[b];
+        r.n = n;
+        r.m = m;
+        for (int64_t q = 0; q < n_perm; ++q) null_out[b * n_perm + q] = t[(size_t)(b * NL + q + 1)];
+    }
+    kad::perm_aggregate(t.data(), B, NL, p_values, p_aggregated);
     return FAD_OK;
 }
 

@@ -921,6 +921,63 @@ def kad_permutation_test(x, y, labels, bandwidth: Optional[float] = None, device
     return out
 
 
+KAD_PERM_MAX_BANDWIDTHS = 16
+
+
+def _kad_perm_sweep_bandwidths(bandwidths=None, factors=None):
+    """kad_sweep_bandwidths for the permutation sweep: the same list and refusals, 1 .. 16 values."""
+    bw, relative = kad_sweep_bandwidths(bandwidths, factors)
+    if bw.size > KAD_PERM_MAX_BANDWIDTHS:
+        raise ValueError(f"KAD permutation sweep takes 1 .. {KAD_PERM_MAX_BANDWIDTHS} {'factors' if relative else 'bandwidths'}, got {bw.size}")
+    return bw, relative
+
+
+def kad_permutation_sweep(x, y, labels, bandwidths=None, factors=None, device: int = 0, kernel: str = "gaussian") -> dict:
+    """``fad_kad_permutation_sweep``: ``kad_permutation_test`` at B bandwidths on the same labellings in one call, and the min-p
+    aggregate over them -> dict of float64 arrays ``mmd2``, ``kxx_mean``, ``kyy_mean``, ``kxy_mean``, ``bandwidth``, ``p_values`` [B]
+    in the order given, ``null`` [B, P], ``p_aggregated``, ``n`` and ``m``.  ``bandwidths``: the sigma values themselves; ``factors``:
+    multiples of the median pairwise distance of the POOLED rows (found once; every test stays exact, and the factor 1 is
+    ``kad_permutation_test``'s default sigma).  Exactly one of the two, 1 .. 16 finite values > 0.  Entry b carries the bits of
+    ``kad_permutation_test(x, y, labels, bandwidth=sigma_b)``.  x, y, ``labels`` and ``kernel`` as ``kad_permutation_test`` takes
+    them."""
+    kf = kad_kernel_code(kernel)
+    bw, relative = _kad_perm_sweep_bandwidths(bandwidths, factors)
+    lib = K.load_library()
+    (px, n, d, ldx, cx, dev_x, kx), (py, m, dy, ldy, cy, dev_y, ky) = _kad_pair(x, y, "y", device)
+    if d != dy:
+        raise ValueError(f"KAD: x has D = {d}, y has D = {dy}")
+    if cx != cy:
+        raise ValueError("KAD: x and y must have the same dtype")
+    pl, P, dev_l, kl = _kad_labels(labels, n + m, device)
+    if not 1 <= P <= KAD_MAX_PERMUTATIONS:
+        raise ValueError(f"KAD permutation test takes 1 .. {KAD_MAX_PERMUTATIONS} labellings, got {P}")
+    B = int(bw.size)
+    res = (K.FadKadResult * B)()
+    null = np.zeros((B, P))
+    pv = np.zeros(B)
+    pa = C.c_double()
+    K.check(lib.fad_kad_permutation_sweep(px, n, ldx, py, m, ldy, d, cx, dev_x, bw.ctypes.data_as(C.POINTER(C.c_double)), B, relative, kf,
+                                          pl, P, dev_l, res, null.ctypes.data, pv.ctypes.data, C.byref(pa), int(device),
+                                          K.current_stream_ptr(device)), "fad_kad_permutation_sweep")
+    out = {k: np.array([getattr(r, k) for r in res], dtype=np.float64) for k in ("mmd2", "kxx_mean", "kyy_mean", "kxy_mean", "bandwidth")}
+    out.update(n=int(res[0].n), m=int(res[0].m), null=null, p_values=pv, p_aggregated=float(pa.value))
+    return out
+
+
+def kad_aggregate(t) -> dict:
+    """``fad_kad_aggregate`` (host only, no GPU): the min-p aggregate of permutation statistics ``t`` [B, P + 1] (float64, column 0 the
+    observed labelling) -> dict ``p_values`` [B] (p_b = #{i : t_b(i) >= t_b(0)} / (P + 1)) and ``p_aggregated`` =
+    #{j : min_b p_b(j) <= min_b p_b(0)} / (P + 1), p_b(j) the same count for labelling j."""
+    t = np.ascontiguousarray(np.asarray(t, dtype=np.float64))
+    if t.ndim != 2 or t.shape[0] < 1 or t.shape[1] < 2:
+        raise ValueError(f"KAD aggregate: t must be [B >= 1, P + 1 >= 2], got shape {t.shape}")
+    lib = K.load_library()
+    pv = np.zeros(t.shape[0])
+    pa = C.c_double()
+    K.check(lib.fad_kad_aggregate(t.ctypes.data, int(t.shape[0]), int(t.shape[1]), pv.ctypes.data, C.byref(pa)), "fad_kad_aggregate")
+    return {"p_values": pv, "p_aggregated": float(pa.value)}
+
+
 # ------------------------------------------------------------------------ precision, recall, density, coverage (k-NN manifold metrics)
 PRDC_MAX_K = 16
 

@@ -336,6 +336,64 @@ def calc_kernel_audio_distance_permutation_test(x, y, permutations: int = 1000, 
     return out
 
 
+AGGREGATE_FACTORS = (0.125, 0.25, 0.5, 1, 2)   # the default ladder of the aggregated test: down from the pooled median, where a median-sigma test is blind
+
+
+def _aggregate_request(bandwidths, factors):
+    """-> (bandwidths, factors) with exactly one of them set, as _sweep_request: ``bandwidths`` overrides the default ``factors``;
+    giving both, or a list hip.kad_permutation_sweep refuses, is a ValueError -- before any file is read or the library is loaded."""
+    from .hip import _kad_perm_sweep_bandwidths
+    if bandwidths is not None:
+        if factors is not None and factors is not AGGREGATE_FACTORS:
+            raise ValueError("KAD aggregated test: give bandwidths or factors, not both")
+        factors = None
+    _kad_perm_sweep_bandwidths(bandwidths, factors)
+    return bandwidths, factors
+
+
+def calc_kernel_audio_distance_aggregated_test(x, y, permutations: int = 1000, seed: int = 0, factors=AGGREGATE_FACTORS, bandwidths=None,
+                                               kernel: str = "gaussian", scale: float = 1.0, labels=None, return_labels: bool = False,
+                                               device: int = 0) -> dict:
+    """Is y distinguishable from the baseline x at any of several scales?  calc_kernel_audio_distance_permutation_test at B bandwidths
+    on the same labellings in one fused GPU call (``fad_kad_permutation_sweep``), and one p-value over all of them: the single-step
+    min-p correction with uniform weights, exact under exchangeability.  A test at the pooled median alone is blind to differences
+    that live at another scale.  ``factors`` (default 1/8, 1/4, 1/2, 1, 2) are multiples of the median pairwise distance of the POOLED
+    rows; ``bandwidths`` gives the sigma values themselves and overrides the default factors (giving both is an error); 1 .. 16 finite
+    values > 0.  -> dict: ``p_aggregated``, ``p_values`` [B], ``kad`` [B] (scale * MMD^2), ``mmd2`` [B], ``bandwidths`` [B] (the sigma
+    values used), ``null`` [B, P], ``kxx_mean``, ``kyy_mean``, ``kxy_mean`` [B], ``n``, ``m``, ``permutations``, ``seed`` (None when
+    labels are given) and, with ``return_labels``, ``labels``.  Everything else as calc_kernel_audio_distance_permutation_test."""
+    _check_kernel(kernel)
+    bandwidths, factors = _aggregate_request(bandwidths, factors)
+    from . import hip
+    sx, sy = _shape_of(x), _shape_of(y)
+    if len(sx) != 2 or len(sy) != 2:
+        raise ValueError(f"KAD needs two 2-D row matrices, got shapes {sx} and {sy}")
+    if sx[1] != sy[1]:
+        raise ValueError(f"KAD: the sets have different dimensions ({sx[1]} and {sy[1]})")
+    if sx[0] < 2 or sy[0] < 2:
+        raise ValueError(f"KAD needs at least 2 rows per set, got {sx[0]} and {sy[0]}")
+    if labels is None:
+        if not 1 <= int(permutations) <= hip.KAD_MAX_PERMUTATIONS:
+            raise ValueError(f"KAD permutation test takes 1 .. {hip.KAD_MAX_PERMUTATIONS} permutations, got {permutations}")
+        labels = random_labellings(sx[0], sy[0], int(permutations), seed=seed, device=device)
+    else:
+        seed = None
+    if hip.K._is_torch(x) and hip.K._is_torch(y):
+        if x.dtype != y.dtype:
+            x, y = x.float(), y.float()
+    elif not hip.K._is_torch(x) and not hip.K._is_torch(y):
+        x, y = np.asarray(x), np.asarray(y)
+        if x.dtype != y.dtype:
+            x, y = x.astype(np.float32), y.astype(np.float32)
+    res = hip.kad_permutation_sweep(x, y, labels, bandwidths=bandwidths, factors=factors, device=device, kernel=kernel)
+    out = {"p_aggregated": res["p_aggregated"], "p_values": res["p_values"], "kad": float(scale) * res["mmd2"], "mmd2": res["mmd2"],
+           "bandwidths": res["bandwidth"], "null": res["null"], "kxx_mean": res["kxx_mean"], "kyy_mean": res["kyy_mean"],
+           "kxy_mean": res["kxy_mean"], "n": res["n"], "m": res["m"], "permutations": int(res["null"].shape[1]), "seed": seed}
+    if return_labels:
+        out["labels"] = labels
+    return out
+
+
 class KernelAudioDistance:
     """KAD between two directories of audio, over the embedding caches FrechetAudioDistance writes and reads."""
 
@@ -407,6 +465,19 @@ class KernelAudioDistance:
             x, y = x.astype(np.float32), y.astype(np.float32)
         return calc_kernel_audio_distance_permutation_test(x, y, permutations=permutations, seed=seed, bandwidth=bandwidth, scale=scale,
                                                            device=self.device_index, kernel=kernel)
+
+    def aggregated_test(self, baseline: PathLike, eval_dir: PathLike, permutations: int = 1000, seed: int = 0, factors=AGGREGATE_FACTORS,
+                        bandwidths=None, scale: float = 1.0, kernel: str = "gaussian") -> dict:
+        """The aggregated KAD permutation test of ``eval_dir`` against ``baseline`` over several bandwidths
+        (calc_kernel_audio_distance_aggregated_test), factors of the pooled median by default."""
+        _check_kernel(kernel)
+        bandwidths, factors = _aggregate_request(bandwidths, factors)
+        x = self.load_rows(baseline)
+        y = self.load_rows(eval_dir)
+        if x.dtype != y.dtype or x.dtype == np.float64:
+            x, y = x.astype(np.float32), y.astype(np.float32)
+        return calc_kernel_audio_distance_aggregated_test(x, y, permutations=permutations, seed=seed, factors=factors, bandwidths=bandwidths,
+                                                          kernel=kernel, scale=scale, device=self.device_index)
 
     def score_individual(self, baseline: PathLike, eval_dir: PathLike, csv_name: Union[Path, str], bandwidth: Optional[float] = None,
                          scale: float = 1.0, kernel: str = "gaussian") -> Path:

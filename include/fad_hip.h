@@ -442,6 +442,39 @@ int fad_kad_uncertainty(const void* x, int64_t n, int64_t ldx, const void* const
 int fad_kad_permutation_test(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype,
                              int on_device, double bandwidth, const uint32_t* labels, int64_t n_perm, int labels_on_device,
                              fad_kad_result_t* observed, double* null /* [n_perm] host */, double* p_value, int device, void* stream);
+/* ------------------------------------------------------------------ KAD permutation test at several bandwidths, aggregated
+ * fad_kad_permutation_test_k at n_bw bandwidths (1 .. FAD_KAD_PERM_MAX_BANDWIDTHS) on the same labellings in one call, and one p-value
+ * over all of them.  A test at one sigma is blind to differences that live at another scale; the aggregate does not depend on having
+ * picked the right one.  Z is packed once, the labellings and their two bit layouts are prepared once, the row-sum pass forms a tile's
+ * dot products once for up to 4 bandwidths, and a triangle walk of the permutation pass carries up to 4 bandwidths wherever their
+ * labelling words fit its 32 partial sums per lane together (4 bandwidths x 8 words of 32 labellings, 2 x 16, or 1 x 32: as few walks as
+ * that allows, about n_bw (n_perm + 1) / 1024 of them).
+ * relative == 0: bandwidths[b] is sigma_b.  relative != 0: bandwidths[b] is a factor of the median pairwise distance of the POOLED rows
+ * (found once; a median of 0 -> FAD_ERR_INVALID): sigma_b is then a function of the pooled rows alone and every test stays exact; the
+ * factor 1.0 gives the single test's default sigma bit for bit.  Every entry must be finite and > 0; duplicates and any order are
+ * allowed.  The shift c0_b is always the mean off-diagonal kernel value of Z under sigma_b, which is what the single call uses under
+ * a given sigma.  observed[b], null[b * n_perm + p] and p_values[b] are fad_kad_permutation_test_k(bandwidth = sigma_b)'s, in the
+ * caller's order -- bit for bit whenever both calls run the permutation pass over Z's triangle as one launch (the row sums agree at any
+ * size); past that the per-tile float32 sums are the same and only the float64 order of adding them differs.
+ * Aggregation (fad_kad_aggregate: host, float64, pure counting; the sweep calls it on its own statistics).  t is [n_bw][n_lab]
+ * row-major, labelling 0 the observed one (n_lab = n_perm + 1 >= 2):
+ *   p_b(j) = #{i : t_b(i) >= t_b(j)} / n_lab        p_values[b] = p_b(0), the single test's p-value
+ *   m(j)   = min_b p_b(j)                           p_aggregated = #{j : m(j) <= m(0)} / n_lab
+ * the single-step min-p correction on the same labellings with uniform weights over the bandwidths (the weights of MMDAgg, Schrab et
+ * al. 2023).  It is exact under exchangeability, because the observed labelling goes through the same code as every other.  With one
+ * bandwidth p_aggregated == p_values[0]; a bandwidth given twice changes nothing.
+ * Argument errors come before any device call, with the single test's codes: NULL pointers, n_bw outside 1 .. 16, an entry that is not
+ * finite and > 0, an unknown kernel, and everything fad_kad_permutation_test_k refuses about rows and labellings.  A sigma_b whose
+ * kernel constant leaves float32 -> FAD_ERR_INVALID, the message naming b.  Any refusal fails the whole call and leaves every output
+ * untouched.  No float atomics: the same bits on every run.  Synchronises `stream`. */
+#define FAD_KAD_PERM_MAX_BANDWIDTHS 16
+int fad_kad_permutation_sweep(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype,
+                              int on_device, const double* bandwidths, int n_bw, int relative, int kernel, const uint32_t* labels,
+                              int64_t n_perm, int labels_on_device, fad_kad_result_t* observed /* [n_bw] */,
+                              double* null /* [n_bw][n_perm] host */, double* p_values /* [n_bw] */, double* p_aggregated, int device,
+                              void* stream);
+int fad_kad_aggregate(const double* t /* [n_bw][n_lab], labelling 0 observed */, int n_bw, int64_t n_lab,
+                      double* p_values /* [n_bw] */, double* p_aggregated);
 
 /* ------------------------------------------------------------------ precision, recall, density, coverage (k-NN manifold metrics)
  * Not in the reference: Kynkaanniemi et al. 2019 (precision, recall) and Naeem et al. 2020 (density, coverage) between the baseline

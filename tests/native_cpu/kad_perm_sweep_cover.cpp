@@ -1,0 +1,111 @@
+// CPU check of fadtk_amd/csrc/kad_perm_sweep_tiles.h, the plan of the KAD permutation sweep (fad_kad_permutation_sweep, kad.hip): over
+// the walks the host cuts a call into, the launches of each walk and the persistent walk of each launch's workgroups, every (bandwidth,
+// labelling word, triangle tile) is taken exactly once; a walk holds kernel_nb * nw <= kPermWords partials per lane and nb <= kernel_nb
+// bandwidths; every launch stays under tiles_per_launch_for(.., perm_epilogue(kernel_nb * nw)); a walk's slots are as many as its widest
+// launch's workgroups; the walks are as few as any uniform cut into runs of 1, 2 or 4 bandwidths gives, the smaller run at a tie (one walk per bandwidth
+// when the labellings fill kPermWords words); and a
+// walk of one bandwidth is cut exactly as kad_perm_tiles.h cuts the single test.
+#include "../../fadtk_amd/csrc/kad_perm_sweep_tiles.h"
+
+#include <cstdio>
+#include <vector>
+
+using namespace fad::kad;
+
+static int fails = 0;
+#define CHECK(c, ...) do { if (!(c)) { if (fails++ < 20) { printf("FAIL %s:%d: ", __FILE__, __LINE__); printf(__VA_ARGS__); printf("\n"); } } } while (0)
+
+static void check(int64_t N, int n_bw, int64_t labellings, int64_t depth, bool f32, int64_t cap, const char* label) {
+    const int64_t TZ = blocks(N), tiles = tri_tiles(TZ), W = perm_words(labellings);
+    const std::vector<PermSweepWalk> walks = perm_sweep_walks(n_bw, labellings);
+    std::vector<int64_t> wslots;
+    const std::vector<PermSweepLaunch> ls = perm_sweep_launches(TZ, walks, depth, f32, cap, &wslots);
+    CHECK(wslots.size() == walks.size(), "%s: %zu slot counts for %zu walks", label, wslots.size(), walks.size());
+
+    // as few walks as a uniform cut gives, ties to the smaller NB
+    const int NB = perm_sweep_nb(n_bw, W);
+    for (int other = 1; other <= kPermSweepNB; other *= 2) {
+        const int64_t mine = perm_sweep_walk_count(n_bw, W, NB), theirs = perm_sweep_walk_count(n_bw, W, other);
+        CHECK(mine < theirs || (mine == theirs && NB <= other), "%s: NB %d gives %lld walks, NB %d gives %lld", label, NB, (long long)mine, other,
+              (long long)theirs);
+    }
+    CHECK((int64_t)walks.size() == perm_sweep_walk_count(n_bw, W, NB), "%s: %zu walks", label, walks.size());
+    if (W == kPermWords)                                                                // a full group of words: the single test's kernel, once per bandwidth
+        CHECK(NB == 1 && (int64_t)walks.size() == n_bw, "%s: %lld words do not run one walk per bandwidth", label, (long long)W);
+    CHECK((int64_t)walks.size() * kPermWords >= (int64_t)n_bw * W, "%s: %zu walks cannot hold %d x %lld words", label, walks.size(), n_bw, (long long)W);
+
+    std::vector<int> word_seen((size_t)(n_bw * W), 0);
+    std::vector<unsigned char> seen((size_t)tiles);
+    size_t at = 0;
+    for (size_t i = 0; i < walks.size(); ++i) {
+        const PermSweepWalk& w = walks[i];
+        CHECK(w.nb >= 1 && w.nb <= w.kernel_nb && (w.kernel_nb == 1 || w.kernel_nb == 2 || w.kernel_nb == 4) && w.kernel_nb == perm_sweep_kernel_nb(w.nb),
+              "%s: walk %zu runs %d bandwidths in the kernel of %d", label, i, w.nb, w.kernel_nb);
+        CHECK(w.nw >= 1 && w.kernel_nb * w.nw <= kPermWords, "%s: walk %zu holds %d x %lld words", label, i, w.kernel_nb, (long long)w.nw);
+        CHECK(w.b0 >= 0 && w.b0 + w.nb <= n_bw && w.w0 >= 0 && w.w0 + w.nw <= W && w.wg >= 0 && w.wg < w.wgs, "%s: walk %zu out of range", label, i);
+        for (int b = w.b0; b < w.b0 + w.nb; ++b)
+            for (int64_t x = w.w0; x < w.w0 + w.nw; ++x) word_seen[(size_t)(b * W + x)]++;
+        std::fill(seen.begin(), seen.end(), 0);
+        const int64_t per = tiles_per_launch_for(depth, f32, perm_epilogue(w.kernel_nb * w.nw));
+        int64_t slot = 0, next_u = 0;
+        for (; at < ls.size() && ls[at].walk == (int64_t)i; ++at) {
+            const PermSweepLaunch& l = ls[at];
+            CHECK(l.cnt >= 1 && l.cnt <= per, "%s: a launch of %lld tiles, cap %lld", label, (long long)l.cnt, (long long)per);
+            CHECK(l.u0 == next_u, "%s: launch starts at tile %lld, not %lld", label, (long long)l.u0, (long long)next_u);
+            CHECK(l.grid % kXcds == 0 && l.grid >= kXcds && l.grid <= launch_slots(l.cnt) && l.grid <= cap, "%s: grid %lld", label, (long long)l.grid);
+            next_u += l.cnt;
+            slot = l.grid > slot ? l.grid : slot;
+            for (int64_t g = 0; g < l.grid; ++g)
+                for (int64_t L = g; L < launch_slots(l.cnt); L += l.grid) {
+                    bool live;
+                    const int64_t v = slot_tile(L, l.cnt, &live);
+                    if (!live) continue;
+                    const int64_t u = l.u0 + v;
+                    CHECK(v >= 0 && v < l.cnt && u < tiles, "%s: slot %lld -> tile %lld", label, (long long)L, (long long)u);
+                    if (u >= 0 && u < tiles) seen[(size_t)u]++;
+                }
+        }
+        CHECK(next_u == tiles, "%s: walk %zu covers %lld of %lld tiles", label, i, (long long)next_u, (long long)tiles);
+        CHECK(wslots[i] == slot, "%s: walk %zu has %lld slots, its widest launch %lld", label, i, (long long)wslots[i], (long long)slot);
+        int64_t bad = 0;
+        for (int64_t u = 0; u < tiles; ++u) bad += seen[(size_t)u] != 1;
+        CHECK(bad == 0, "%s: walk %zu: %lld tiles not taken exactly once", label, i, (long long)bad);
+    }
+    CHECK(at == ls.size(), "%s: %zu launches outside any walk", label, ls.size() - at);
+    int64_t bad = 0;
+    for (int v : word_seen) bad += v != 1;
+    CHECK(bad == 0, "%s: %lld (bandwidth, word) pairs not covered exactly once", label, (long long)bad);
+
+    // one bandwidth: the single test's own groups and launches
+    if (n_bw == 1) {
+        std::vector<int64_t> gslots;
+        const std::vector<PermLaunch> single = perm_launches(TZ, labellings, depth, f32, cap, &gslots);
+        CHECK(single.size() == ls.size() && gslots == wslots, "%s: one bandwidth is not cut as the single test", label);
+        for (size_t i = 0; i < single.size() && i < ls.size(); ++i)
+            CHECK(single[i].u0 == ls[i].u0 && single[i].cnt == ls[i].cnt && single[i].grid == ls[i].grid && single[i].w0 == walks[(size_t)ls[i].walk].w0 &&
+                  single[i].nw == walks[(size_t)ls[i].walk].nw, "%s: launch %zu differs from the single test's", label, i);
+    }
+    printf("%s: N %lld B %d labellings %lld NB %d walks %zu launches %zu\n", label, (long long)N, n_bw, (long long)labellings, NB, walks.size(), ls.size());
+}
+
+int main() {
+    for (int B = 1; B <= kPermSweepMax; ++B)
+        for (int64_t P : {1, 31, 32, 199, 255, 256, 300, 511, 512, 999, 1023, 1024, 2048})
+            check(512, B, P + 1, 128, false, 512, "n + m = 512");
+    check(4, 4, 2, 128, false, 512, "n = m = 2, P = 1, B = 4");
+    check(512, 3, 301, 64, true, 64, "f32, B = 3, P = 300");
+    check(5000, 16, 65537, 2048, false, 512, "P = 65536, B = 16");
+    check(200000, 4, 200, 512, false, 512, "config-3, B = 4, P = 199");
+    check(200000, 4, 1000, 128, false, 512, "config-3, B = 4, P = 999");
+    check(200000, 5, 200, 512, false, 512, "config-3, B = 5, P = 199");
+    check(2000000, 2, 400, 128, false, 512, "N = 2e6, B = 2, P = 399");
+    check(2000000, 3, 2049, 2048, true, 64, "N = 2e6 f32, B = 3, P = 2048");
+    // the plans the GPU tests rely on: 4 x 7 words share one walk; 10 words force several
+    CHECK(perm_sweep_walks(4, 200).size() == 1 && perm_sweep_walks(4, 200)[0].kernel_nb == 4, "B = 4, P = 199 is not one walk of 4");
+    CHECK(perm_sweep_walks(4, 301).size() == 2 && perm_sweep_walks(4, 301)[0].kernel_nb == 2, "B = 4, P = 300 is not two walks of 2");
+    CHECK(perm_sweep_walks(3, 200).size() == 1 && perm_sweep_walks(3, 200)[0].nb == 3, "B = 3, P = 199 is not one walk of 3 in the kernel of 4");
+    CHECK(perm_sweep_walks(5, 200).size() == 2 && perm_sweep_walks(5, 200)[1].kernel_nb == 1, "B = 5, P = 199 is not 4 + 1");
+    if (fails) { printf("%d failures\n", fails); return 1; }
+    printf("OK\n");
+    return 0;
+}
