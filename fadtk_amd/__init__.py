@@ -31,6 +31,9 @@ def __getattr__(name):
     if name in ("NearestNeighbours", "calc_nearest_neighbours", "calc_authenticity"):      # lazy, as KAD's
         from . import nearest
         return getattr(nearest, name)
+    if name in ("NearestNeighbourTest", "calc_nearest_neighbour_test"):      # lazy, as KAD's
+        from . import nn_test
+        return getattr(nn_test, name)
     if name == "cache_embedding_files":
         from .fad_batch import cache_embedding_files
         return cache_embedding_files

@@ -74,6 +74,15 @@ class FadNearestResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class FadNnTestResult(C.Structure):
+    _fields_ = [("accuracy", C.c_double), ("accuracy_x", C.c_double), ("accuracy_y", C.c_double), ("p_value", C.c_double),
+                ("p_value_low", C.c_double), ("correct_x", C.c_int64), ("correct_y", C.c_int64), ("n", C.c_int64), ("m", C.c_int64),
+                ("k", C.c_int)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 _P = C.c_void_p
 _I64 = C.c_int64
 # name -> (restype, argtypes)     -- one entry per declaration in include/fad_hip.h
@@ -152,6 +161,8 @@ SIGNATURES = {
                            C.POINTER(FadPrdcDetail), C.c_int, _P]),
     "fad_nearest": (C.c_int, [_P, _I64, _I64, _P, _I64, _I64, _I64, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P,
                               C.POINTER(FadNearestResult), C.c_int, _P]),
+    "fad_nn_test": (C.c_int, [_P, _I64, _I64, _P, _I64, _I64, _I64, C.c_int, C.c_int, C.c_int, _P, _I64, C.c_int,
+                              C.POINTER(FadNnTestResult), _P, _P, _P, _P, C.c_int, _P]),
 }
 
 _lib = None

@@ -1,7 +1,8 @@
 // Kernel Audio Distance: the unbiased Gaussian-kernel MMD^2 between two sets of embedding rows, and the median pairwise distance
 // of one set (the default bandwidth).  DESIGN.md 4.6.  Per-song KAD (4.7), the k-NN precision / recall / density / coverage (4.8),
 // KAD's standard errors (4.9), its permutation test (4.10), the nearest baseline rows with authenticity (4.11), KAD at several
-// bandwidths in one pass (4.12) and the permutation test at several bandwidths, aggregated (4.13) run on the same main loop.
+// bandwidths in one pass (4.12), the permutation test at several bandwidths, aggregated (4.13) and the leave-one-out k-NN two-sample
+// test on the pooled rows (4.14) run on the same main loop.
 //
 // Every pass is one GEMM-shaped walk over 128 x 128 tiles of a pair space (kad_tiles.h) whose n x m matrix is never stored:
 //   - pack:   each set is copied once into a zero-padded [n_pad x dp] image of its own dtype (dp: D rounded up to 128 bytes, n_pad:
@@ -23,6 +24,7 @@
 #include "kad_unc_tiles.h"
 #include "kad_perm_tiles.h"
 #include "kad_perm_sweep_tiles.h"
+#include "nn_vote.h"
 
 #include <algorithm>
 #include <cmath>
@@ -1508,6 +1510,86 @@ __global__ void __launch_bounds__(kThreads, 2) nearest_cross_kernel(PrdcArgs p, 
     }
 }
 
+// fad_nn_test's self pass: nearest_cross_kernel's walk over Z x Z, every pooled row's k nearest OTHER pooled rows.  The
+// same keys, list, LDS merge and slots.  On a tile I == J the accumulator of the pair row == column is set to -inf before the keys are
+// formed (self_mask; self excluded by index, so a duplicate row is a neighbour at d^2 = 0): its d^2 = max(-2 S', 0) = +inf, the key of
+// a padding row, which sorts after every real row's and never reaches an output (k <= N - 1).  Off-diagonal tiles pay nothing.  Masking
+// the accumulators in place, ahead of one epilogue for all tiles, keeps KB = 1 at nearest_cross_kernel's 164 VGPRs; a second epilogue
+// that replaced the self key itself took 208 (2 waves per SIMD instead of 3).
+__device__ __forceinline__ void self_mask(f32x16 (&acc)[2][2], int rbase, int cbase, int lane) {
+    int lrow = rbase + 4 * (lane >> 5), lcol = cbase + (lane & 31);
+    asm volatile("" : "+v"(lrow), "+v"(lcol));                   // per tile, not hoisted out of the tile loop as lane masks (topk_tile)
+#pragma unroll
+    for (int bj = 0; bj < 2; ++bj)
+#pragma unroll
+        for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+            for (int g = 0; g < 16; ++g)
+                acc[bi][bj][g] = lcol + bj * 32 == lrow + bi * 32 + (g & 3) + 8 * (g >> 2) ? -INFINITY : acc[bi][bj][g];
+}
+
+// a tile's keys into the lane's list: nearest_cross_kernel's epilogue
+template <int KB>
+__device__ __forceinline__ void keys_tile(const f32x16 (&acc)[2][2], uint32_t i0, uint64_t (&t)[KB]) {
+#pragma unroll
+    for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+        for (int g = 0; g < 16; ++g) {
+            // lane half h holds column bj = h at rows r (first) and r + 4 (second)
+            const auto s = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[bi][0][g]), __float_as_uint(acc[bi][1][g]), false, false);
+            const uint32_t r = i0 + bi * 32 + (g & 3) + 8 * (g >> 2);
+            const uint64_t k0 = d2_key(__uint_as_float(s[0]), r), k1 = d2_key(__uint_as_float(s[1]), r + 4);
+            if constexpr (KB == 1) {
+                t[0] = k0 < t[0] ? k0 : t[0];
+                t[0] = k1 < t[0] ? k1 : t[0];
+            } else {
+                if (__ballot(k0 < t[0])) key_insert(t, k0);                          // wave-uniform skip
+                if (__ballot(k1 < t[0])) key_insert(t, k1);
+            }
+        }
+}
+
+template <int DT, int KB>
+__global__ void __launch_bounds__(kThreads, 2) nearest_self_kernel(PrdcArgs p, uint64_t* __restrict__ lists) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    uint64_t* lx = reinterpret_cast<uint64_t*>(lds + 2 * kOpBytes + 2 * kTile * 4);     // the wm = 1 waves' lists of a unit [128][KB]
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
+    const int rbase = wm * 64, c = wn * 64 + (lane >> 5) * 32 + (lane & 31);          // the lane's column of the tile (after the swap)
+    const int64_t G = gridDim.x, nslots = kad::launch_slots(p.cnt);
+
+    for (int64_t L = blockIdx.x; L < nslots; L += G) {
+        bool live;
+        const int64_t v = kad::slot_tile(L, p.cnt, &live);
+        if (!live) continue;                                                          // uniform over the workgroup
+        const int64_t u = p.u0 + v;
+        const kad::Unit un = kad::cross_unit(u, p.TI, p.TJ, p.rr);
+        uint64_t t[KB];
+        key_init(t, p.k);
+
+        for (int64_t I = un.I0; I < un.I1; ++I) {
+            f32x16 acc[2][2];
+            tile_mfma<DT>(p.a, p.b, p.ha, p.hb, p.pitch, p.nchunks, I, un.J, lds, [](int) {}, acc);
+            if (I == un.J) self_mask(acc, rbase, wn * 64, lane);                      // uniform over the workgroup
+            keys_tile(acc, (uint32_t)(I * kTile + rbase), t);
+        }
+
+        if (wm == 1) {
+#pragma unroll
+            for (int q = 0; q < KB; ++q) lx[c * KB + q] = t[q];
+        }
+        __syncthreads();
+        if (wm == 0) {
+#pragma unroll
+            for (int q = 0; q < KB; ++q) key_insert(t, q < p.k ? lx[c * KB + q] : ~0ull);
+            uint64_t* out = lists + ((u / p.TJ) * p.list_pitch + un.J * kTile + c) * p.k;
+#pragma unroll
+            for (int q = 0; q < KB; ++q)
+                if (q < p.k) out[q] = t[q];
+        }
+    }
+}
+
 template <int KB>
 constexpr size_t lds_nearest() { return 2 * kOpBytes + 2 * kTile * 4 + kTile * KB * sizeof(uint64_t); }
 
@@ -1554,7 +1636,7 @@ struct KadWorkspace {
     DevBuf lists, prdc;                              // fad_prdc: the radius passes' top-k slots; radii, counts, flags and totals
     DevBuf unc_slots, unc;                           // fad_kad_uncertainty: column slots of the pass; unit tables and per-row outputs
     DevBuf perm_lab, perm_rows, perm_cols, perm;     // fad_kad_permutation_test: labellings, row and column words; slots and tables
-    DevBuf near;                                     // fad_nearest: index, dist2, radii, nn radii, copied count
+    DevBuf near;                                     // fad_nearest: index, dist2, radii, nn radii, copied count; fad_nn_test: index, dist2, counts
     void release_all() {
         for (int i = 0; i < 2; ++i) { raw[i].release(); img[i].release(); h[i].release(); }
         slots.release(); small.release(); cross.release(); band.release(); songs.release(); lists.release(); prdc.release();
@@ -1868,6 +1950,27 @@ static int nearest_pass(const Packed& x, const Packed& y, int k, int dtype, int 
         }));
     }
     nearest_reduce_kernel<<<(unsigned)cdiv(y.n, 256), 256, 0, st>>>(lists, q.NR, p.list_pitch, k, y.n, index, dist2);
+    FAD_HIP_TRY(hipGetLastError());
+    return FAD_OK;
+}
+
+// index / dist2 [N x k] (device) = the k nearest OTHER rows of z to every row of z, ascending in (d^2, i): nearest_pass over Z x Z with
+// the self pair masked; `lists` holds NR * TZ * 128 * k keys
+static int nearest_self_pass(const Packed& z, int k, int dtype, int device, hipStream_t st, uint64_t* lists, int32_t* index, float* dist2) {
+    const PrdcPlan q = prdc_plan(z, z, dtype, kad::kNearestEpilogue);
+    PrdcArgs p{};
+    p.a = p.b = z.img; p.ha = p.hb = z.h; p.pitch = z.pitch; p.nchunks = z.nchunks; p.k = k;
+    p.TI = q.TI; p.TJ = q.TJ; p.rr = q.rr; p.list_pitch = q.TJ * kTile;
+    for (const kad::Launch& l : kad::launches(q.NR * q.TJ, q.per_launch, grid_cap(device))) {
+        p.u0 = l.u0; p.cnt = l.cnt;
+        FAD_TRY(with_dtype(dtype, [&](auto dt) {
+            if (k == 1) nearest_self_kernel<dt, 1><<<(unsigned)l.grid, kThreads, lds_nearest<1>(), st>>>(p, lists);
+            else if (k <= 4) nearest_self_kernel<dt, 4><<<(unsigned)l.grid, kThreads, lds_nearest<4>(), st>>>(p, lists);
+            else if (k <= 8) nearest_self_kernel<dt, 8><<<(unsigned)l.grid, kThreads, lds_nearest<8>(), st>>>(p, lists);
+            else nearest_self_kernel<dt, kMaxK><<<(unsigned)l.grid, kThreads, lds_nearest<kMaxK>(), st>>>(p, lists);
+        }));
+    }
+    nearest_reduce_kernel<<<(unsigned)cdiv(z.n, 256), 256, 0, st>>>(lists, q.NR, p.list_pitch, k, z.n, index, dist2);
     FAD_HIP_TRY(hipGetLastError());
     return FAD_OK;
 }
@@ -2561,6 +2664,76 @@ int fad_nearest(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m,
 
     out->authenticity = authenticity ? 1.0 - (double)copied / (double)m : NAN;
     out->copied = authenticity ? (int64_t)copied : -1;
+    out->n = n;
+    out->m = m;
+    out->k = k;
+    return FAD_OK;
+}
+
+int fad_nn_test(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype, int on_device, int k,
+                const uint32_t* labels, int64_t n_perm, int labels_on_device, fad_nn_test_result_t* out, int64_t* null_correct_x,
+                int64_t* null_correct_y, int32_t* index, float* dist2, int device, void* stream) {
+    using namespace fad;
+    if (!out || !null_correct_x || !null_correct_y) return set_error(FAD_ERR_INVALID, "fad_nn_test: NULL output");
+    if (k < 1 || k > nnv::kMaxVotes || k % 2 == 0)
+        return set_error(FAD_ERR_INVALID, "fad_nn_test: k = %d must be odd and in 1 .. %d", k, nnv::kMaxVotes);
+    FAD_TRY(perm_check_args(x, n, ldx, y, m, ldy, d, dtype, labels, n_perm));
+    if (k > n + m - 1)
+        return set_error(FAD_ERR_INVALID, "fad_nn_test: k = %d needs at least k + 1 pooled rows, got %lld", k, (long long)(n + m));
+    FAD_TRY(perm_check_labels(n, m, labels, n_perm, labels_on_device));
+    FAD_TRY(check_device(device));
+    DeviceGuard g(device);
+    if (!g.ok) return set_error(FAD_ERR_HIP, "hipSetDevice(%d) failed", device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    KadWorkspace& ws = workspace(device);
+
+    PermPrep pp;
+    FAD_TRY(perm_prepare(x, n, ldx, y, m, ldy, d, dtype, on_device, labels, n_perm, labels_on_device, st, ws, &pp));
+    const int64_t N = pp.N, z_pad = pp.z_pad, NL = pp.NL, W = pp.W;
+    const Packed pz{pp.zimg, pp.zh, N, pp.pitch, (int)(pp.pitch / kChunk), pp.norm_sum};
+    const PrdcPlan q = prdc_plan(pz, pz, dtype, kad::kNearestEpilogue);
+
+    // index | dist2 | counts [32 W][2]
+    size_t at[4];
+    at[0] = 0;
+    at[1] = at[0] + align256((size_t)(N * k) * sizeof(int32_t));
+    at[2] = at[1] + align256((size_t)(N * k) * sizeof(float));
+    at[3] = at[2] + align256((size_t)(64 * W) * sizeof(unsigned long long));
+    FAD_TRY(ws.near.reserve(at[3]));
+    FAD_TRY(ws.lists.reserve((size_t)(q.NR * z_pad * k) * sizeof(uint64_t)));
+    char* nb = static_cast<char*>(ws.near.p);
+    int32_t* index_d = reinterpret_cast<int32_t*>(nb + at[0]);
+    float* dist2_d = reinterpret_cast<float*>(nb + at[1]);
+    unsigned long long* counts_d = reinterpret_cast<unsigned long long*>(nb + at[2]);
+
+    // the graph (it never sees a label), then every labelling's votes on it
+    FAD_TRY(nearest_self_pass(pz, k, dtype, device, st, static_cast<uint64_t*>(ws.lists.p), index_d, dist2_d));
+    FAD_HIP_TRY(hipMemsetAsync(counts_d, 0, (size_t)(64 * W) * sizeof(unsigned long long), st));
+    nnv::nn_vote_kernel<<<dim3((unsigned)cdiv(N, nnv::kVoteRows), (unsigned)W), 256, 0, st>>>(pp.cols_d, z_pad, index_d, k, N, counts_d);
+    FAD_HIP_TRY(hipGetLastError());
+    std::vector<unsigned long long> counts((size_t)(2 * NL));
+    FAD_HIP_TRY(hipMemcpyAsync(counts.data(), counts_d, counts.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    const hipMemcpyKind back = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (index) FAD_HIP_TRY(hipMemcpyAsync(index, index_d, (size_t)(N * k) * sizeof(int32_t), back, st));
+    if (dist2) FAD_HIP_TRY(hipMemcpyAsync(dist2, dist2_d, (size_t)(N * k) * sizeof(float), back, st));
+    FAD_HIP_TRY(hipStreamSynchronize(st));
+
+    const int64_t cx0 = (int64_t)counts[0], cy0 = (int64_t)counts[1], c0 = cx0 + cy0;
+    int64_t ge = 0, le = 0;
+    for (int64_t p = 0; p < n_perm; ++p) {
+        const int64_t cx = (int64_t)counts[(size_t)(2 * (p + 1))], cy = (int64_t)counts[(size_t)(2 * (p + 1) + 1)];
+        null_correct_x[p] = cx;
+        null_correct_y[p] = cy;
+        ge += cx + cy >= c0;
+        le += cx + cy <= c0;
+    }
+    out->accuracy = (double)c0 / (double)N;
+    out->accuracy_x = (double)cx0 / (double)n;
+    out->accuracy_y = (double)cy0 / (double)m;
+    out->p_value = (double)(1 + ge) / (double)(n_perm + 1);
+    out->p_value_low = (double)(1 + le) / (double)(n_perm + 1);
+    out->correct_x = cx0;
+    out->correct_y = cy0;
     out->n = n;
     out->m = m;
     out->k = k;

@@ -1039,3 +1039,63 @@ def nearest(x, y, k: int = 1, authenticity: bool = True, device: int = 0) -> dic
     out = res.as_dict()
     out.update(index=index, dist2=dist2, nn_radius2=nn_r2)
     return out
+
+
+# ------------------------------------------------------------------------ leave-one-out k-NN two-sample test on the pooled rows
+NN_TEST_MAX_K = 15
+
+
+def nn_test_k(k, n_rows: Optional[int] = None) -> int:
+    """-> k as ``fad_nn_test`` takes it: odd, 1 .. 15 and at most n_rows - 1 (when the pooled row count is given); anything else is a
+    ValueError, raised before the native library is touched."""
+    if isinstance(k, bool) or int(k) != k:
+        raise ValueError(f"nearest-neighbour test: k must be an odd integer in 1 .. {NN_TEST_MAX_K}, got {k!r}")
+    k = int(k)
+    if not 1 <= k <= NN_TEST_MAX_K or k % 2 == 0:
+        raise ValueError(f"nearest-neighbour test: k must be odd and in 1 .. {NN_TEST_MAX_K}, got {k}")
+    if n_rows is not None and k > n_rows - 1:
+        raise ValueError(f"nearest-neighbour test: k = {k} needs at least {k + 1} pooled rows, got {n_rows}")
+    return k
+
+
+def nn_test(x, y, labels, k: int = 1, device: int = 0, return_graph: bool = False) -> dict:
+    """``fad_nn_test``: the leave-one-out k-nearest-neighbour two-sample test on the pooled rows Z = [x; y] -> dict of
+    fad_nn_test_result (accuracy, accuracy_x, accuracy_y, p_value, p_value_low, correct_x, correct_y, n, m, k) and
+    ``null_correct_x`` / ``null_correct_y`` [P] (int64, the correct baseline-labelled / evaluation-labelled rows under every labelling
+    of ``labels``).  ``labels`` as ``kad_permutation_test`` takes them; the observed labelling is added by the library.  k is odd,
+    1 .. 15, at most n + m - 1.  ``return_graph=True`` adds ``index`` [N, k] (int32, Z's row numbering) and ``dist2`` [N, k] (float32),
+    every pooled row's k nearest OTHER pooled rows in ascending (d^2, index): numpy arrays for numpy rows, torch tensors on the rows'
+    device for torch CUDA rows."""
+    k = nn_test_k(k)
+    lib = K.load_library()
+    (px, n, d, ldx, cx, dev_x, kx), (py, m, dy, ldy, cy, dev_y, ky) = _kad_pair(x, y, "y", device)
+    if d != dy:
+        raise ValueError(f"nearest-neighbour test: x has D = {d}, y has D = {dy}")
+    if cx != cy:
+        raise ValueError("nearest-neighbour test: x and y must have the same dtype")
+    nn_test_k(k, n + m)
+    pl, P, dev_l, kl = _kad_labels(labels, n + m, device)
+    if not 1 <= P <= KAD_MAX_PERMUTATIONS:
+        raise ValueError(f"nearest-neighbour test takes 1 .. {KAD_MAX_PERMUTATIONS} labellings, got {P}")
+    res = K.FadNnTestResult()
+    null_x = np.zeros(P, np.int64)
+    null_y = np.zeros(P, np.int64)
+    index = dist2 = None
+    pi = pd = None
+    if return_graph:
+        if dev_x:
+            import torch
+            index = torch.zeros((n + m, k), dtype=torch.int32, device=kx.device)
+            dist2 = torch.zeros((n + m, k), dtype=torch.float32, device=kx.device)
+            pi, pd = index.data_ptr(), dist2.data_ptr()
+        else:
+            index = np.zeros((n + m, k), np.int32)
+            dist2 = np.zeros((n + m, k), np.float32)
+            pi, pd = index.ctypes.data, dist2.ctypes.data
+    K.check(lib.fad_nn_test(px, n, ldx, py, m, ldy, d, cx, dev_x, k, pl, P, dev_l, C.byref(res), null_x.ctypes.data, null_y.ctypes.data,
+                            pi, pd, int(device), K.current_stream_ptr(device)), "fad_nn_test")
+    out = res.as_dict()
+    out.update(null_correct_x=null_x, null_correct_y=null_y)
+    if return_graph:
+        out.update(index=index, dist2=dist2)
+    return out

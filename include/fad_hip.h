@@ -525,6 +525,41 @@ int fad_nearest(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m,
                 int k, int authenticity, int32_t* index, float* dist2, float* nn_radius2 /* may be NULL */, fad_nearest_result_t* out,
                 int device, void* stream);
 
+/* ------------------------------------------------------------------ leave-one-out k-NN two-sample test on the pooled rows
+ * Not in the reference.  Is y distinguishable from x at all, with no bandwidth to choose?  (Schilling 1986, Henze 1988; the classifier
+ * two-sample test of Lopez-Paz & Oquab 2017 with a k-NN classifier.)  Z = [x; y] pooled, N = n + m rows; k odd, 1 <= k <= 15,
+ * k <= N - 1.  For every row j of Z, nn(j, 0 .. k-1) are the k rows i != j of Z in ascending order of the key (d^2, i): d^2 is the
+ * float32 max(-2 S', 0) that fad_nearest forms, equal d^2 go to the smaller index, and self is excluded by index (a duplicate row is a
+ * neighbour at d^2 = 0).  The graph is fully determined and a function of the pooled rows alone.
+ * A labelling u is what fad_kad_permutation_test takes: packed bits [n_perm x ceil(N / 32)], exactly n ones, no bit at or past N;
+ * labelling 0 is the observed one (Z's first n rows), added by the library.  Under u, row j is PREDICTED BASELINE when more than k / 2
+ * of u[nn(j, .)] are 1, and CORRECT when the prediction equals u[j]:
+ *   correct_x(u) = #{j correct : u[j] = 1}    correct_y(u) = #{j correct : u[j] = 0}    c(u) = correct_x(u) + correct_y(u)
+ *   accuracy = c(u_0) / N      accuracy_x = correct_x(u_0) / n      accuracy_y = correct_y(u_0) / m
+ *   p_value     = (1 + #{p : c(u_p) >= c(u_0)}) / (n_perm + 1)      upper tail: distinguishable (accuracy above chance)
+ *   p_value_low = (1 + #{p : c(u_p) <= c(u_0)}) / (n_perm + 1)      lower tail: memorised (evaluation rows sit on baseline rows)
+ * The counts are compared as integers; both p-values are exact under exchangeability because the graph never sees a label.
+ * accuracy_y near 1 with a low accuracy_x: mode collapse; both low: memorisation.  null_correct_x[p] / null_correct_y[p] (host,
+ * n_perm entries each) = correct_x / correct_y of the caller's labelling p.  index [N x k] (int32) and dist2 [N x k] (float32), each
+ * NULL or an array on the side of the rows (host or device per on_device), hold the graph in ascending key order with Z's row
+ * numbering (y_j is row n + j).
+ * One pass of fad_nearest's kernel over Z x Z (the full square) finds the graph; all labellings are then classified by one bit-parallel
+ * kernel, 32 labellings per word (csrc/nn_vote.h).  Argument errors come before any device call: everything
+ * fad_kad_permutation_test refuses about rows and labellings with its codes (n or m < 2 -> FAD_ERR_TOO_FEW_ROWS); k even, outside
+ * 1 .. 15 or > N - 1, a NULL out or null array -> FAD_ERR_INVALID.  Device labels with a wrong count -> FAD_ERR_INVALID; a NaN/Inf row
+ * norm -> FAD_ERR_NOT_FINITE.  Any refusal leaves every output untouched.  Integers and float32 bits only: the same bits on every run.
+ * Workspace: Z's image, the labelling words, N k (4 + 4) bytes of graph and 8 k bytes of keys per row and row range.  Synchronises
+ * `stream`. */
+typedef struct fad_nn_test_result {
+    double accuracy, accuracy_x, accuracy_y, p_value, p_value_low;
+    int64_t correct_x, correct_y, n, m;
+    int k;
+} fad_nn_test_result_t;
+int fad_nn_test(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype, int on_device,
+                int k, const uint32_t* labels, int64_t n_perm, int labels_on_device, fad_nn_test_result_t* out,
+                int64_t* null_correct_x /* [n_perm] host */, int64_t* null_correct_y /* [n_perm] host */,
+                int32_t* index /* [N * k] or NULL */, float* dist2 /* [N * k] or NULL */, int device, void* stream);
+
 /* ------------------------------------------------------------------ diagnostics (NOT part of the drop-in surface)
  * Nothing in fadtk corresponds to these two calls and no binding of the reference needs them: they exist for bench.py's
  * roofline object (HIP events around the tile kernel on the stream it is launched on) and for the GPU tests that check

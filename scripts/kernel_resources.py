@@ -2,13 +2,17 @@
 flags of fadtk_amd/build.py, one line per kernel (VGPRs, AGPRs, scratch bytes per lane, static LDS bytes, waves per SIMD, and the SGPRs and
 VGPRs the compiler spilled: SGPRs go to VGPR lanes, VGPRs to scratch).
     python scripts/kernel_resources.py [substring ...] > profiles/rNN_kernel_resources.txt
-No GPU needed (hipcc cross-compiles gfx950)."""
+    python scripts/kernel_resources.py nn_test > profiles/nn_test_kernel_resources.txt
+`nn_test` stands for the kernels of fad_nn_test and the ones they sit beside (GROUPS).  No GPU needed (hipcc cross-compiles gfx950)."""
 import re, subprocess, sys, pathlib
 sys.path.insert(0, str(pathlib.Path(__file__).resolve().parents[1]))
 from fadtk_amd import build as B
 
-want = sys.argv[1:]
+GROUPS = {"nn_test": ["nearest_self_kernel", "nn_vote_kernel", "nearest_cross_kernel", "nearest_reduce_kernel", "prdc_"]}
+want = [n for w in sys.argv[1:] for n in GROUPS.get(w, [w])]
 src = sorted((pathlib.Path(B.__file__).parent / "csrc").glob("*.hip"))
+if want and all(w in GROUPS for w in sys.argv[1:]):
+    src = [s for s in src if s.name == "kad.hip"]              # every group's kernels live in kad.hip
 print("# hipcc -Rpass-analysis=kernel-resource-usage (gfx950, the flags of fadtk_amd/build.py): registers, scratch, LDS and occupancy")
 print("kernel | VGPRs | AGPRs | scratch B/lane | LDS B (static) | waves/SIMD | file | SGPRs spilled | VGPRs spilled")
 for s in src:
