@@ -34,6 +34,9 @@ def __getattr__(name):
     if name in ("NearestNeighbourTest", "calc_nearest_neighbour_test"):      # lazy, as KAD's
         from . import nn_test
         return getattr(nn_test, name)
+    if name in ("KernelDistance", "calc_kernel_distance", "calc_kernel_distance_full"):      # lazy, as KAD's
+        from . import kid
+        return getattr(kid, name)
     if name == "cache_embedding_files":
         from .fad_batch import cache_embedding_files
         return cache_embedding_files

@@ -83,6 +83,14 @@ class FadNnTestResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class FadKidResult(C.Structure):
+    _fields_ = [("mmd2", C.c_double), ("kxx_mean", C.c_double), ("kyy_mean", C.c_double), ("kxy_mean", C.c_double),
+                ("gamma", C.c_double), ("coef0", C.c_double), ("degree", C.c_int), ("n", C.c_int64), ("m", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 _P = C.c_void_p
 _I64 = C.c_int64
 # name -> (restype, argtypes)     -- one entry per declaration in include/fad_hip.h
@@ -163,6 +171,10 @@ SIGNATURES = {
                               C.POINTER(FadNearestResult), C.c_int, _P]),
     "fad_nn_test": (C.c_int, [_P, _I64, _I64, _P, _I64, _I64, _I64, C.c_int, C.c_int, C.c_int, _P, _I64, C.c_int,
                               C.POINTER(FadNnTestResult), _P, _P, _P, _P, C.c_int, _P]),
+    "fad_kid": (C.c_int, [_P, _I64, _I64, _P, _I64, _I64, _I64, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(FadKidResult),
+                          C.c_int, _P]),
+    "fad_kid_subsets": (C.c_int, [_P, _I64, _I64, _P, _I64, _I64, _I64, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _P, _P, _I64, _I64,
+                                  C.c_int, _P, _P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, _P]),
 }
 
 _lib = None

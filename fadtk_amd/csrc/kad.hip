@@ -1,8 +1,8 @@
 // Kernel Audio Distance: the unbiased Gaussian-kernel MMD^2 between two sets of embedding rows, and the median pairwise distance
 // of one set (the default bandwidth).  DESIGN.md 4.6.  Per-song KAD (4.7), the k-NN precision / recall / density / coverage (4.8),
 // KAD's standard errors (4.9), its permutation test (4.10), the nearest baseline rows with authenticity (4.11), KAD at several
-// bandwidths in one pass (4.12), the permutation test at several bandwidths, aggregated (4.13) and the leave-one-out k-NN two-sample
-// test on the pooled rows (4.14) run on the same main loop.
+// bandwidths in one pass (4.12), the permutation test at several bandwidths, aggregated (4.13), the leave-one-out k-NN two-sample
+// test on the pooled rows (4.14) and the polynomial-kernel distance of the KID protocol (4.15) run on the same main loop.
 //
 // Every pass is one GEMM-shaped walk over 128 x 128 tiles of a pair space (kad_tiles.h) whose n x m matrix is never stored:
 //   - pack:   each set is copied once into a zero-padded [n_pad x dp] image of its own dtype (dp: D rounded up to 128 bytes, n_pad:
@@ -24,6 +24,7 @@
 #include "kad_unc_tiles.h"
 #include "kad_perm_tiles.h"
 #include "kad_perm_sweep_tiles.h"
+#include "kid_tiles.h"
 #include "nn_vote.h"
 
 #include <algorithm>
@@ -1629,6 +1630,220 @@ __global__ void __launch_bounds__(256) nearest_copied_kernel(const int32_t* __re
     if (threadIdx.x == 0 && n_hit) atomicAdd(copied, (unsigned long long)n_hit);     // integer counts: order does not matter
 }
 
+// ---------------------------------------------------------------------------- polynomial-kernel distance, KID
+// k(a, b) = (gamma a.b + c0)^p is a function of the dot product, so the row markers take h's place: 0 on a row, -inf on a padding row
+// (NaN on a row whose float32 squared norm is not finite, so that such a row can never pass for padding).  The accumulators then start
+// at 0 + 0 and end at S = a.b exactly as the MFMAs form it, or at -inf where either row is padding.  Epilogue: u = fma(S, gamma, c0)
+// -- the ordinary VALU op that reads the MFMA result, as kernel_value's -- k = u^p by a chain of p - 1 multiplies, and a pair whose
+// S is -inf is dropped by a select: it adds exactly nothing.  A real pair's S is finite (|S| <= |a| |b|, both finite), so the marker
+// cannot be taken for data.  p is uniform over the launch: one branch per tile, no instantiation per degree.
+struct KidArgs {
+    PassArgs p;                                // p.ha, p.hb: the row markers; p.c is not read.  Subsets: a = the x images, b = the y images
+    float gamma, coef0;
+    int degree;                                // 1 .. 4
+    double* units;                             // subsets: one float64 per unit of the group
+};
+
+template <bool MASK, int P>
+__device__ __forceinline__ float kid_tile_sum_p(const f32x16 (&acc)[2][2], float gamma, float coef0, int rbase, int cbase, int lane) {
+    int lrow = rbase + 4 * (lane >> 5) - (cbase + (lane & 31));
+    if (MASK) asm volatile("" : "+v"(lrow));                                         // as tile_sum: the mask compares stay in the tile
+    float s = 0.f;
+#pragma unroll
+    for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+        for (int bj = 0; bj < 2; ++bj)
+#pragma unroll
+            for (int g = 0; g < 16; ++g) {
+                const float a = acc[bi][bj][g];
+                const float u = fmaf(a, gamma, coef0);
+                float k = u;
+#pragma unroll
+                for (int e = 1; e < P; ++e) k *= u;
+                bool keep = a != -INFINITY;
+                if (MASK) keep = keep && (bj * 32 - bi * 32 - (g & 3) - 8 * (g >> 2)) > lrow;     // column > row
+                s += keep ? k : 0.f;
+            }
+    return s;
+}
+
+// (gamma S + c0)^degree summed over the wave's 64 x 64 pairs of a tile; MASK: a diagonal tile of a triangle counts only column > row
+template <bool MASK>
+__device__ __forceinline__ float kid_tile_sum(const f32x16 (&acc)[2][2], const KidArgs& q, int rbase, int cbase, int lane) {
+    switch (q.degree) {
+        case 1: return kid_tile_sum_p<MASK, 1>(acc, q.gamma, q.coef0, rbase, cbase, lane);
+        case 2: return kid_tile_sum_p<MASK, 2>(acc, q.gamma, q.coef0, rbase, cbase, lane);
+        case 3: return kid_tile_sum_p<MASK, 3>(acc, q.gamma, q.coef0, rbase, cbase, lane);
+        default: return kid_tile_sum_p<MASK, 4>(acc, q.gamma, q.coef0, rbase, cbase, lane);
+    }
+}
+
+// fad_kid's sum pass: kad_pass_kernel<DT, MODE_SUM> with the polynomial epilogue -- the same walk, slots and final sum.
+template <int DT>
+__global__ void __launch_bounds__(kThreads, 2) kid_pass_kernel(KidArgs q) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    double* lred = reinterpret_cast<double*>(lds + 2 * kOpBytes + 2 * kTile * 4);
+    const PassArgs& p = q.p;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
+    const int64_t G = gridDim.x, nslots = kad::launch_slots(p.cnt);
+    double dsum = 0.0;
+    for (int64_t L = blockIdx.x; L < nslots; L += G) {
+        bool live;
+        const int64_t v = kad::slot_tile(L, p.cnt, &live);
+        if (!live) continue;                                                          // uniform over the workgroup
+        const kad::Tile t = p.tri ? kad::tri_tile(p.u0 + v, p.tiles_j) : kad::rect_tile(p.u0 + v, p.tiles_j);
+        f32x16 acc[2][2];
+        tile_mfma<DT>(p.a, p.b, p.ha, p.hb, p.pitch, p.nchunks, t.I, t.J, lds, [](int) {}, acc);
+        const float s = (p.tri && t.I == t.J) ? kid_tile_sum<true>(acc, q, wm * 64, wn * 64, lane) : kid_tile_sum<false>(acc, q, wm * 64, wn * 64, lane);
+        dsum += (double)s;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) dsum += __shfl_xor(dsum, off, 64);
+    if (lane == 0) lred[wave] = dsum;
+    __syncthreads();
+    if (tid == 0) p.slots[blockIdx.x] = ((lred[0] + lred[1]) + lred[2]) + lred[3];
+}
+
+// table[u] = unit u of a group (kid::unit_of, kid_tiles.h) as the pass reads it: the first image row of its subset, its block and its
+// tile.  The map's 64-bit divisions and the triangle's root are taken here, once per unit, not in the pass: inlined there they cost the
+// pass 6 VGPRs and 88 spilled SGPRs, and with them the third workgroup per CU.
+struct KidUnitRow { int64_t row0; int32_t block, I, J, pad; };
+__global__ void __launch_bounds__(256) kid_unit_table_kernel(int64_t total, int64_t T, int64_t img_rows, KidUnitRow* __restrict__ table) {
+    const int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (u >= total) return;
+    const kid::Unit t = kid::unit_of(u, T);
+    table[u] = KidUnitRow{t.q * img_rows, t.block, (int32_t)t.I, (int32_t)t.J, 0};
+}
+
+// fad_kid_subsets' pass over a group of subsets: unit p.u0 + v (kid_tiles.h) is one tile of one block of one subset and writes one
+// float64, the tile's sum: the lanes' float32 sums in float64 through the wave's butterfly and ((w0 + w1) + w2) + w3.  A value depends
+// on its tile alone -- not on the launch cut, the grid or the group.
+template <int DT>
+__global__ void __launch_bounds__(kThreads, 2) kid_units_kernel(KidArgs q, const KidUnitRow* __restrict__ table) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    double* lred = reinterpret_cast<double*>(lds + 2 * kOpBytes + 2 * kTile * 4);
+    const PassArgs& p = q.p;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
+    const int64_t G = gridDim.x, nslots = kad::launch_slots(p.cnt);
+    for (int64_t L = blockIdx.x; L < nslots; L += G) {
+        bool live;
+        const int64_t v = kad::slot_tile(L, p.cnt, &live);
+        if (!live) continue;                                                          // uniform over the workgroup
+        const KidUnitRow t = table[p.u0 + v];
+        const bool ay = t.block == kid::YY, bx = t.block == kid::XX;
+        f32x16 acc[2][2];
+        tile_mfma<DT>((ay ? p.b : p.a) + t.row0 * p.pitch, (bx ? p.a : p.b) + t.row0 * p.pitch, (ay ? p.hb : p.ha) + t.row0,
+                      (bx ? p.ha : p.hb) + t.row0, p.pitch, p.nchunks, t.I, t.J, lds, [](int) {}, acc);
+        const float s = (t.block != kid::XY && t.I == t.J) ? kid_tile_sum<true>(acc, q, wm * 64, wn * 64, lane)
+                                                           : kid_tile_sum<false>(acc, q, wm * 64, wn * 64, lane);
+        double dsum = (double)s;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) dsum += __shfl_xor(dsum, off, 64);
+        if (lane == 0) lred[wave] = dsum;                                             // read before the next tile's first barrier
+        __syncthreads();
+        if (tid == 0) q.units[p.u0 + v] = ((lred[0] + lred[1]) + lred[2]) + lred[3];
+    }
+}
+
+// One wave per image row.  Image t (of n_img) holds s rows in img_rows: its row r is x[index[t * s + r]] (index NULL: x[r], a whole
+// set), zero-padded to dp columns, the rows past s all zero.  mark: 0 on a row, -inf past s, NaN where the row's float32 squared norm
+// is not finite.  The index was checked by kid_index_check_kernel before this kernel reads a row through it.
+template <typename T>
+__global__ void __launch_bounds__(256) kid_pack_kernel(const T* __restrict__ x, int64_t ld, int64_t d, const int32_t* __restrict__ index,
+                                                       int64_t s, int64_t img_rows, int64_t n_img, T* __restrict__ out, int64_t dp,
+                                                       float* __restrict__ mark) {
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= n_img * img_rows) return;
+    const int64_t t = row / img_rows, r = row % img_rows;
+    const bool real = r < s;
+    const int64_t src = real ? (index ? (int64_t)index[t * s + r] : r) : 0;
+    float sq = 0.f;
+    for (int64_t c = lane; c < dp; c += 64) {
+        T v = T(0.f);
+        if (real && c < d) v = x[src * ld + c];
+        out[row * dp + c] = v;
+        const float f = (float)v;
+        sq = fmaf(f, f, sq);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) sq += __shfl_xor(sq, off, 64);
+    if (lane == 0) mark[row] = real ? (isfinite(sq) ? 0.f : NAN) : -INFINITY;
+}
+
+// bad += the entries of ix outside [0, n) and of iy outside [0, m) (count entries each)
+__global__ void __launch_bounds__(256) kid_index_check_kernel(const int32_t* __restrict__ ix, const int32_t* __restrict__ iy, int64_t count,
+                                                              int64_t n, int64_t m, unsigned long long* __restrict__ bad) {
+    int mine = 0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (int64_t)gridDim.x * 256) {
+        const int64_t a = ix[i], b = iy[i];
+        mine += (a < 0 || a >= n) + (b < 0 || b >= m);
+    }
+    __shared__ int red[256];
+    red[threadIdx.x] = mine;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && red[0]) atomicAdd(bad, (unsigned long long)red[0]);      // integer counts: order does not matter
+}
+
+// sums[(q0 + q) * 3 + block] = the units of block `block` of the group's subset q, summed in a fixed order (workgroup (q, block)):
+// thread t takes the units t, t + 256, ... in unit order, then the tree of kad_slots_sum_kernel.
+__global__ void __launch_bounds__(256) kid_subset_sums_kernel(const double* __restrict__ units, int64_t T, int64_t q0, double* __restrict__ sums) {
+    __shared__ double red[256];
+    const int64_t q = blockIdx.x, tt = kad::tri_tiles(T), U = kid::units_per_subset(T);
+    const int block = blockIdx.y;
+    const int64_t b = q * U + (block == kid::XX ? 0 : block == kid::YY ? tt : 2 * tt), e = q * U + (block == kid::XX ? tt : block == kid::YY ? 2 * tt : U);
+    double s = 0.0;
+    for (int64_t i = b + threadIdx.x; i < e; i += 256) s += units[i];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) sums[(q0 + q) * 3 + block] = red[0];
+}
+
+// One workgroup.  Per subset q: the three means (the triangles' sums count every pair i != j twice) and MMD^2, as fad_kid forms them;
+// then stats[0] = the mean of MMD^2 over q and stats[1] = its population standard deviation, two passes, each a strided float64 sum
+// and the same tree: a fixed order.
+__global__ void __launch_bounds__(256) kid_stats_kernel(const double* __restrict__ sums, int64_t nq, int64_t s, double* __restrict__ mmd2,
+                                                        double* __restrict__ terms, double* __restrict__ stats) {
+    __shared__ double red[256];
+    const double pairs = (double)s * (double)(s - 1), square = (double)s * (double)s;
+    double acc = 0.0;
+    for (int64_t q = threadIdx.x; q < nq; q += 256) {
+        const double kxx = 2.0 * sums[3 * q] / pairs, kyy = 2.0 * sums[3 * q + 1] / pairs, kxy = sums[3 * q + 2] / square;
+        terms[3 * q] = kxx; terms[3 * q + 1] = kyy; terms[3 * q + 2] = kxy;
+        const double v = kxx + kyy - 2.0 * kxy;
+        mmd2[q] = v;
+        acc += v;
+    }
+    double mean = 0.0;
+    for (int pass = 0; pass < 2; ++pass) {
+        red[threadIdx.x] = acc;
+        __syncthreads();
+        for (int w = 128; w > 0; w >>= 1) {
+            if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+            __syncthreads();
+        }
+        const double total = red[0];
+        __syncthreads();
+        if (pass == 0) {
+            mean = total / (double)nq;
+            acc = 0.0;
+            for (int64_t q = threadIdx.x; q < nq; q += 256) acc += (mmd2[q] - mean) * (mmd2[q] - mean);
+        } else if (threadIdx.x == 0) {
+            stats[0] = mean;
+            stats[1] = sqrt(total / (double)nq);
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------------------------ host side
 struct KadWorkspace {
     DevBuf raw[2], img[2], h[2], slots, small;       // small: info, pass offsets, pass sums, histograms
@@ -1637,11 +1852,12 @@ struct KadWorkspace {
     DevBuf unc_slots, unc;                           // fad_kad_uncertainty: column slots of the pass; unit tables and per-row outputs
     DevBuf perm_lab, perm_rows, perm_cols, perm;     // fad_kad_permutation_test: labellings, row and column words; slots and tables
     DevBuf near;                                     // fad_nearest: index, dist2, radii, nn radii, copied count; fad_nn_test: index, dist2, counts
+    DevBuf kid_index, kid;                           // fad_kid_subsets: the two index lists; the bad-index count, sums and results
     void release_all() {
         for (int i = 0; i < 2; ++i) { raw[i].release(); img[i].release(); h[i].release(); }
         slots.release(); small.release(); cross.release(); band.release(); songs.release(); lists.release(); prdc.release();
         unc_slots.release(); unc.release(); perm_lab.release(); perm_rows.release(); perm_cols.release(); perm.release();
-        near.release();
+        near.release(); kid_index.release(); kid.release();
     }
 };
 
@@ -2088,6 +2304,56 @@ static int perm_prepare(const void* x, int64_t n, int64_t ldx, const void* y, in
 
     *out = PermPrep{zimg, zh, N, TZ, z_pad, nwz, dp, pitch, NL, W, lab, rows_d, cols_d, info[0]};
     return FAD_OK;
+}
+
+// ---------------------------------------------------------------------------------------- polynomial-kernel distance
+struct KidParams { float gamma, coef0; int degree; };
+
+// degree, gamma (<= 0: 1 / d) and coef0 as the kernels take them, in float32
+static int kid_params(int degree, double gamma, double coef0, int64_t d, const char* who, KidParams* out) {
+    if (degree < 1 || degree > 4) return set_error(FAD_ERR_INVALID, "%s: degree %d is outside 1 .. 4", who, degree);
+    if (!std::isfinite(gamma) || !std::isfinite(coef0)) return set_error(FAD_ERR_INVALID, "%s: gamma %g and coef0 %g must be finite", who, gamma, coef0);
+    const float g = gamma > 0 ? (float)gamma : (float)(1.0 / (double)d), c = (float)coef0;
+    if (!std::isfinite(g) || !(g > 0.f) || !std::isfinite(c))
+        return set_error(FAD_ERR_INVALID, "%s: gamma %g or coef0 %g is outside the float32 range", who, gamma, coef0);
+    *out = KidParams{g, c, degree};
+    return FAD_OK;
+}
+
+// n_img images of s rows each (img_rows with the padding) of the rows of x, through `index` (device) or, index NULL, x's own rows:
+// slot's image and markers.  Host rows are staged whole, once, in ws.raw[slot] (*staged keeps the device copy for the next group).
+static int kid_pack(int slot, const void* x, int64_t n, int64_t ld, int64_t d, int dtype, int on_device, const int32_t* index, int64_t s,
+                    int64_t img_rows, int64_t n_img, hipStream_t st, KadWorkspace& ws, const void** staged, Packed* out) {
+    const size_t es = dtype_size(dtype);
+    const int64_t dp = depth_elems(d, dtype);
+    if (!on_device) {
+        if (!*staged) {
+            FAD_TRY(ws.raw[slot].reserve((size_t)(n * d) * es));
+            FAD_HIP_TRY(hipMemcpy2DAsync(ws.raw[slot].p, (size_t)d * es, x, (size_t)ld * es, (size_t)d * es, (size_t)n, hipMemcpyHostToDevice, st));
+            *staged = ws.raw[slot].p;
+        }
+        x = *staged;
+        ld = d;
+    }
+    const int64_t rows = n_img * img_rows;
+    FAD_TRY(ws.img[slot].reserve((size_t)(rows * dp) * es));
+    FAD_TRY(ws.h[slot].reserve((size_t)rows * sizeof(float)));
+    float* h = static_cast<float*>(ws.h[slot].p);
+    const dim3 grid((unsigned)cdiv(rows, 4));
+    switch (dtype) {
+        case FAD_F16: kid_pack_kernel<_Float16><<<grid, 256, 0, st>>>(static_cast<const _Float16*>(x), ld, d, index, s, img_rows, n_img, static_cast<_Float16*>(ws.img[slot].p), dp, h); break;
+        case FAD_BF16: kid_pack_kernel<__bf16><<<grid, 256, 0, st>>>(static_cast<const __bf16*>(x), ld, d, index, s, img_rows, n_img, static_cast<__bf16*>(ws.img[slot].p), dp, h); break;
+        default: kid_pack_kernel<float><<<grid, 256, 0, st>>>(static_cast<const float*>(x), ld, d, index, s, img_rows, n_img, static_cast<float*>(ws.img[slot].p), dp, h); break;
+    }
+    FAD_HIP_TRY(hipGetLastError());
+    *out = Packed{static_cast<const char*>(ws.img[slot].p), h, s, dp * (int64_t)es, (int)(dp * (int64_t)es / kChunk), 0.0};
+    return FAD_OK;
+}
+
+static KidArgs kid_args(const PassArgs& p, const KidParams& k) {
+    KidArgs q{};
+    q.p = p; q.gamma = k.gamma; q.coef0 = k.coef0; q.degree = k.degree;
+    return q;
 }
 
 }  // namespace
@@ -3091,6 +3357,169 @@ int fad_kad_permutation_sweep(const void* x, int64_t n, int64_t ldx, const void*
         for (int64_t q = 0; q < n_perm; ++q) null_out[b * n_perm + q] = t[(size_t)(b * NL + q + 1)];
     }
     kad::perm_aggregate(t.data(), B, NL, p_values, p_aggregated);
+    return FAD_OK;
+}
+
+int fad_kid(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype, int on_device,
+            int degree, double gamma, double coef0, fad_kid_result_t* out, int device, void* stream) {
+    using namespace fad;
+    if (!out) return set_error(FAD_ERR_INVALID, "fad_kid: NULL output");
+    FAD_TRY(check_rows(x, n, ldx, d, dtype, "fad_kid (x)"));
+    FAD_TRY(check_rows(y, m, ldy, d, dtype, "fad_kid (y)"));
+    KidParams k;
+    FAD_TRY(kid_params(degree, gamma, coef0, d, "fad_kid", &k));
+    FAD_TRY(check_device(device));
+    DeviceGuard g(device);
+    if (!g.ok) return set_error(FAD_ERR_HIP, "hipSetDevice(%d) failed", device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    KadWorkspace& ws = workspace(device);
+    FAD_TRY(ws.small.reserve(4096 * sizeof(double) + 2 * kHistBins * sizeof(unsigned long long)));
+
+    Packed px, py;
+    const void* staged[2] = {nullptr, nullptr};
+    FAD_TRY(kid_pack(0, x, n, ldx, d, dtype, on_device, nullptr, n, kad::blocks(n) * kTile, 1, st, ws, &staged[0], &px));
+    FAD_TRY(kid_pack(1, y, m, ldy, d, dtype, on_device, nullptr, m, kad::blocks(m) * kTile, 1, st, ws, &staged[1], &py));
+
+    // passes as fad_kad's: XX and YY over their triangles, XY over the rectangle with the larger set as the row operand; slots as
+    // sum_passes lays them out, summed by kad_slots_sum_kernel
+    const bool x_rows = n >= m;
+    const PassArgs passes[3] = {pass_args(px, px, true, 0.f), pass_args(py, py, true, 0.f), pass_args(x_rows ? px : py, x_rows ? py : px, false, 0.f)};
+    std::vector<kad::Launch> launches[3];
+    int64_t off[4] = {0};
+    for (int q = 0; q < 3; ++q) {
+        launches[q] = pass_launches(passes[q], dtype, false, device);
+        off[q + 1] = off[q];
+        for (const kad::Launch& l : launches[q]) off[q + 1] += l.grid;
+    }
+    FAD_TRY(ws.slots.reserve((size_t)off[3] * sizeof(double)));
+    int64_t* off_d = reinterpret_cast<int64_t*>(static_cast<double*>(ws.small.p) + 8);
+    double* sums_d = static_cast<double*>(ws.small.p) + 16;
+    FAD_HIP_TRY(hipMemcpyAsync(off_d, off, sizeof(off), hipMemcpyHostToDevice, st));
+    for (int q = 0; q < 3; ++q) {
+        KidArgs a = kid_args(passes[q], k);
+        a.p.slots = static_cast<double*>(ws.slots.p) + off[q];
+        for (const kad::Launch& l : launches[q]) {
+            a.p.u0 = l.u0; a.p.cnt = l.cnt;
+            FAD_TRY(with_dtype(dtype, [&](auto dt) { kid_pass_kernel<dt><<<(unsigned)l.grid, kThreads, kLdsSum, st>>>(a); }));
+            a.p.slots += l.grid;
+        }
+    }
+    kad_slots_sum_kernel<<<3, 256, 0, st>>>(static_cast<const double*>(ws.slots.p), off_d, sums_d);
+    FAD_HIP_TRY(hipGetLastError());
+    double sums[3];
+    FAD_HIP_TRY(hipMemcpyAsync(sums, sums_d, sizeof(sums), hipMemcpyDeviceToHost, st));
+    FAD_HIP_TRY(hipStreamSynchronize(st));
+    for (int q = 0; q < 3; ++q)
+        if (!std::isfinite(sums[q]))
+            return set_error(FAD_ERR_NOT_FINITE, "fad_kid: the kernel sum of %s is not finite (NaN/Inf rows, or (gamma a.b + coef0)^%d beyond float32)",
+                             q == 0 ? "x-x" : q == 1 ? "y-y" : "x-y", degree);
+
+    out->kxx_mean = 2.0 * sums[0] / ((double)n * (double)(n - 1));
+    out->kyy_mean = 2.0 * sums[1] / ((double)m * (double)(m - 1));
+    out->kxy_mean = sums[2] / ((double)n * (double)m);
+    out->mmd2 = out->kxx_mean + out->kyy_mean - 2.0 * out->kxy_mean;
+    out->gamma = (double)k.gamma;
+    out->coef0 = (double)k.coef0;
+    out->degree = degree;
+    out->n = n;
+    out->m = m;
+    return FAD_OK;
+}
+
+int fad_kid_subsets(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype, int on_device,
+                    int degree, double gamma, double coef0, const int32_t* index_x, const int32_t* index_y, int64_t n_subsets,
+                    int64_t subset_size, int index_on_device, double* mmd2, double* terms, double* mean, double* std_out, int device,
+                    void* stream) {
+    using namespace fad;
+    if (!mmd2 || !mean || !std_out) return set_error(FAD_ERR_INVALID, "fad_kid_subsets: NULL output");
+    if (!index_x || !index_y) return set_error(FAD_ERR_INVALID, "fad_kid_subsets: NULL index");
+    FAD_TRY(check_rows(x, n, ldx, d, dtype, "fad_kid_subsets (x)"));
+    FAD_TRY(check_rows(y, m, ldy, d, dtype, "fad_kid_subsets (y)"));
+    KidParams k;
+    FAD_TRY(kid_params(degree, gamma, coef0, d, "fad_kid_subsets", &k));
+    const int64_t s = subset_size;
+    if (s < 2) return set_error(FAD_ERR_TOO_FEW_ROWS, "fad_kid_subsets: a subset needs at least 2 rows, got %lld", (long long)s);
+    if (s > std::min(n, m))
+        return set_error(FAD_ERR_INVALID, "fad_kid_subsets: subset size %lld is larger than the smaller set (%lld rows)", (long long)s,
+                         (long long)std::min(n, m));
+    if (n_subsets < 1) return set_error(FAD_ERR_INVALID, "fad_kid_subsets: %lld subsets (at least 1)", (long long)n_subsets);
+    if (n > INT32_MAX || m > INT32_MAX) return set_error(FAD_ERR_INVALID, "fad_kid_subsets: the index is 32-bit, at most %d rows per set", INT32_MAX);
+    FAD_TRY(check_device(device));
+    DeviceGuard g(device);
+    if (!g.ok) return set_error(FAD_ERR_HIP, "hipSetDevice(%d) failed", device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    KadWorkspace& ws = workspace(device);
+
+    // the index lists on the device, checked there before any row is read through them
+    const int64_t count = n_subsets * s;
+    const int32_t* ix = index_x;
+    const int32_t* iy = index_y;
+    if (!index_on_device) {
+        FAD_TRY(ws.kid_index.reserve((size_t)(2 * count) * sizeof(int32_t)));
+        int32_t* both = static_cast<int32_t*>(ws.kid_index.p);
+        FAD_HIP_TRY(hipMemcpyAsync(both, index_x, (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        FAD_HIP_TRY(hipMemcpyAsync(both + count, index_y, (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        ix = both;
+        iy = both + count;
+    }
+    // ws.kid: the bad-index count (32 doubles' room), then sums [3 S], mmd2 [S], terms [3 S], stats [2]
+    FAD_TRY(ws.kid.reserve((size_t)(32 + 7 * n_subsets + 2) * sizeof(double)));
+    unsigned long long* bad_d = static_cast<unsigned long long*>(ws.kid.p);
+    double* sums_d = static_cast<double*>(ws.kid.p) + 32;
+    double* mmd2_d = sums_d + 3 * n_subsets;
+    double* terms_d = mmd2_d + n_subsets;
+    double* stats_d = terms_d + 3 * n_subsets;
+    FAD_HIP_TRY(hipMemsetAsync(bad_d, 0, sizeof(unsigned long long), st));
+    kid_index_check_kernel<<<(unsigned)std::min<int64_t>(cdiv(count, 256), 1024), 256, 0, st>>>(ix, iy, count, n, m, bad_d);
+    FAD_HIP_TRY(hipGetLastError());
+    unsigned long long bad = 0;
+    FAD_HIP_TRY(hipMemcpyAsync(&bad, bad_d, sizeof(bad), hipMemcpyDeviceToHost, st));
+    FAD_HIP_TRY(hipStreamSynchronize(st));
+    if (bad) return set_error(FAD_ERR_INVALID, "fad_kid_subsets: %llu index entries are outside [0, %lld) of x or [0, %lld) of y", bad, (long long)n,
+                              (long long)m);
+
+    // the subsets in groups whose two images stay under kid::kImageBudget: gather-pack, one pass over the group's units, the units
+    // of every (subset, block) summed in unit order
+    const int64_t T = kad::blocks(s), img_rows = T * kTile, U = kid::units_per_subset(T);
+    const int64_t row_bytes = depth_elems(d, dtype) * (int64_t)dtype_size(dtype);
+    const int64_t per_launch = kad::tiles_per_launch(row_bytes / (int64_t)dtype_size(dtype), dtype == FAD_F32);
+    const void* staged[2] = {nullptr, nullptr};
+    for (const kid::Group& grp : kid::plan(n_subsets, s, row_bytes, kid::kImageBudget)) {
+        Packed px, py;
+        FAD_TRY(kid_pack(0, x, n, ldx, d, dtype, on_device, ix + grp.q0 * s, s, img_rows, grp.count, st, ws, &staged[0], &px));
+        FAD_TRY(kid_pack(1, y, m, ldy, d, dtype, on_device, iy + grp.q0 * s, s, img_rows, grp.count, st, ws, &staged[1], &py));
+        // ws.slots: the group's units, one float64 each, then the unit table the pass reads
+        const int64_t total = grp.count * U;
+        FAD_TRY(ws.slots.reserve((size_t)total * (sizeof(double) + sizeof(KidUnitRow))));
+        KidArgs a = kid_args(pass_args(px, py, false, 0.f), k);
+        a.units = static_cast<double*>(ws.slots.p);
+        KidUnitRow* table = reinterpret_cast<KidUnitRow*>(a.units + total);
+        kid_unit_table_kernel<<<(unsigned)cdiv(total, 256), 256, 0, st>>>(total, T, img_rows, table);
+        FAD_HIP_TRY(hipGetLastError());
+        for (const kad::Launch& l : kad::launches(total, per_launch, grid_cap(device))) {
+            a.p.u0 = l.u0; a.p.cnt = l.cnt;
+            FAD_TRY(with_dtype(dtype, [&](auto dt) { kid_units_kernel<dt><<<(unsigned)l.grid, kThreads, kLdsSum, st>>>(a, table); }));
+        }
+        kid_subset_sums_kernel<<<dim3((unsigned)grp.count, 3), 256, 0, st>>>(a.units, T, grp.q0, sums_d);
+        FAD_HIP_TRY(hipGetLastError());
+    }
+    kid_stats_kernel<<<1, 256, 0, st>>>(sums_d, n_subsets, s, mmd2_d, terms_d, stats_d);
+    FAD_HIP_TRY(hipGetLastError());
+    std::vector<double> host((size_t)(7 * n_subsets + 2));
+    FAD_HIP_TRY(hipMemcpyAsync(host.data(), sums_d, host.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    FAD_HIP_TRY(hipStreamSynchronize(st));
+    for (int64_t q = 0; q < n_subsets; ++q)
+        for (int b = 0; b < 3; ++b)
+            if (!std::isfinite(host[(size_t)(3 * q + b)]))
+                return set_error(FAD_ERR_NOT_FINITE, "fad_kid_subsets: the kernel sum of %s of subset %lld is not finite (NaN/Inf rows, or "
+                                 "(gamma a.b + coef0)^%d beyond float32)", b == 0 ? "x-x" : b == 1 ? "y-y" : "x-y", (long long)q, degree);
+
+    const double* r = host.data() + 3 * n_subsets;            // only now: a refusal above leaves the outputs as they were
+    for (int64_t q = 0; q < n_subsets; ++q) mmd2[q] = r[q];
+    if (terms)
+        for (int64_t q = 0; q < 3 * n_subsets; ++q) terms[q] = r[n_subsets + q];
+    *mean = r[4 * n_subsets];
+    *std_out = r[4 * n_subsets + 1];
     return FAD_OK;
 }
 

@@ -1099,3 +1099,81 @@ def nn_test(x, y, labels, k: int = 1, device: int = 0, return_graph: bool = Fals
     if return_graph:
         out.update(index=index, dist2=dist2)
     return out
+
+
+# ------------------------------------------------------------------------ kernel distance with the polynomial kernel (KID)
+def kid_params(degree=3, gamma=None, coef0=1.0):
+    """-> (degree, gamma, coef0) as the C ABI takes them: degree 1 .. 4, gamma None -> 0 (the library's 1 / D) else a finite value > 0,
+    coef0 finite.  Anything else is a ValueError, raised before the native library is touched."""
+    if int(degree) != degree or not 1 <= int(degree) <= 4:
+        raise ValueError(f"KID: degree must be 1 .. 4, got {degree}")
+    g = 0.0 if gamma is None else float(gamma)
+    if gamma is not None and not (g > 0 and np.isfinite(g)):
+        raise ValueError(f"KID: gamma must be finite and > 0 (None: 1 / D), got {gamma}")
+    c = float(coef0)
+    if not np.isfinite(c):
+        raise ValueError(f"KID: coef0 must be finite, got {coef0}")
+    return int(degree), g, c
+
+
+def _kid_pair(x, y, device: int):
+    (px, n, d, ldx, cx, dev_x, kx), (py, m, dy, ldy, cy, dev_y, ky) = _kad_pair(x, y, "y", device)
+    if d != dy:
+        raise ValueError(f"KID: x has D = {d}, y has D = {dy}")
+    if cx != cy:
+        raise ValueError("KID: x and y must have the same dtype")
+    return (px, n, ldx, kx), (py, m, ldy, ky), d, cx, dev_x
+
+
+def kid(x, y, degree: int = 3, gamma: Optional[float] = None, coef0: float = 1.0, device: int = 0) -> dict:
+    """``fad_kid``: the unbiased MMD^2 with the polynomial kernel (gamma a.b + coef0)^degree over all rows of x and y -> dict of
+    fad_kid_result (mmd2, kxx_mean, kyy_mean, kxy_mean, gamma and coef0 as used, degree, n, m).  ``gamma=None``: 1 / D.
+    Both sets are numpy arrays or both torch CUDA tensors of one dtype (float16 / bfloat16 / float32)."""
+    degree, g, c = kid_params(degree, gamma, coef0)
+    lib = K.load_library()
+    (px, n, ldx, kx), (py, m, ldy, ky), d, code, on_dev = _kid_pair(x, y, device)
+    res = K.FadKidResult()
+    K.check(lib.fad_kid(px, n, ldx, py, m, ldy, d, code, on_dev, degree, g, c, C.byref(res), int(device), K.current_stream_ptr(device)), "fad_kid")
+    return res.as_dict()
+
+
+def _kid_index(index, what: str, device: int):
+    """-> (int32 [S, s] numpy array or contiguous torch CUDA tensor, on_device)"""
+    if K._is_torch(index):
+        import torch
+        if index.dim() != 2:
+            raise ValueError(f"KID: {what} must be 2-D [subsets, subset_size], got shape {tuple(index.shape)}")
+        if index.is_cuda:
+            return index.to(torch.int32).contiguous(), 1
+        index = index.numpy()
+    a = np.asarray(index)
+    if a.ndim != 2:
+        raise ValueError(f"KID: {what} must be 2-D [subsets, subset_size], got shape {a.shape}")
+    if a.dtype.kind not in "iu":
+        raise ValueError(f"KID: {what} must hold integers, got {a.dtype}")
+    if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+        raise ValueError(f"KID: {what} does not fit 32 bits")
+    return np.ascontiguousarray(a, dtype=np.int32), 0
+
+
+def kid_subsets(x, y, index_x, index_y, degree: int = 3, gamma: Optional[float] = None, coef0: float = 1.0, device: int = 0) -> dict:
+    """``fad_kid_subsets``: the KID protocol, every subset in one fused pass.  ``index_x`` / ``index_y``: integer [S, s] row numbers of
+    x / of y, subset q being x[index_x[q]] against y[index_y[q]] (both numpy, or both torch CUDA tensors used in place as int32).
+    -> dict: ``mmd2`` [S] and ``terms`` [S, 3] (kxx, kyy, kxy means) as float64 numpy arrays, ``mean`` and ``std`` (population) of
+    mmd2, ``subsets``, ``subset_size``."""
+    degree, g, c = kid_params(degree, gamma, coef0)
+    ix, dev_i = _kid_index(index_x, "index_x", device)
+    iy, dev_j = _kid_index(index_y, "index_y", device)
+    if tuple(ix.shape) != tuple(iy.shape):
+        raise ValueError(f"KID: index_x {tuple(ix.shape)} and index_y {tuple(iy.shape)} must have one shape")
+    if dev_i != dev_j:
+        raise ValueError("KID: index_x and index_y must both be numpy arrays or both torch CUDA tensors")
+    S, s = int(ix.shape[0]), int(ix.shape[1])
+    lib = K.load_library()
+    (px, n, ldx, kx), (py, m, ldy, ky), d, code, on_dev = _kid_pair(x, y, device)
+    mmd2, terms = np.zeros(max(S, 1)), np.zeros((max(S, 1), 3))
+    mean, std = C.c_double(), C.c_double()
+    pix, piy = (ix.data_ptr(), iy.data_ptr()) if dev_i else (ix.ctypes.data, iy.ctypes.data)
+    K.check(lib.fad_kid_subsets(px, n, ldx, py, m, ldy, d, code, on_dev, degree, g, c, pix, piy, S, s, dev_i, mmd2.ctypes.data,
+                                terms.ctypes.data, C.byref(mean), C.byref(std), int(device), K.current_stream_ptr(device)), "fad_kid_subsets")
+    return {"mmd2": mmd2[:S], "terms": terms[:S], "mean": float(mean.value), "std": float(std.value), "subsets": S, "subset_size": s}

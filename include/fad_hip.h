@@ -560,6 +560,40 @@ int fad_nn_test(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m,
                 int64_t* null_correct_x /* [n_perm] host */, int64_t* null_correct_y /* [n_perm] host */,
                 int32_t* index /* [N * k] or NULL */, float* dist2 /* [N * k] or NULL */, int device, void* stream);
 
+/* ------------------------------------------------------------------ kernel distance with the polynomial kernel (KID protocol)
+ * Not in the reference.  The unbiased MMD^2 with k(a, b) = (gamma a.b + coef0)^degree -- "KID" / "KD" of the audio evaluation suites
+ * at degree 3, gamma = 1 / D, coef0 = 1 (Binkowski et al. 2018) -- over the whole sets (fad_kid) or averaged over many random subsets
+ * (fad_kid_subsets: usually 100 subsets of 1000 rows, reported as mean +- std).  degree is 1 .. 4; gamma <= 0 means 1 / d; gamma and
+ * coef0 are used as their float32 roundings, and fad_kid's result reports the values actually used.
+ *   kxx_mean = sum_{i != j} k(x_i, x_j) / (n (n - 1))    kyy_mean likewise    kxy_mean = sum_{i, j} k(x_i, y_j) / (n m)
+ *   mmd2 = kxx_mean + kyy_mean - 2 kxy_mean              (the diagonal of kxx / kyy excluded by index, as fad_kad)
+ * Subset q is the rows index_x[q s .. q s + s) of x and index_y[q s .. q s + s) of y (s = subset_size), and
+ *   mmd2[q] = Sxx / (s (s - 1)) + Syy / (s (s - 1)) - 2 Sxy / s^2,   Sxx, Syy over i != j, Sxy over all s^2 pairs, its diagonal included
+ * -- the usual "unbiased" KID estimator; terms[3 q .. 3 q + 3) = the three means; *mean and *std = the mean and the population
+ * standard deviation (ddof = 0; 0 for one subset) of mmd2[].  Repeated indices inside a subset are the caller's business: they are
+ * neither checked nor refused (a repeated row pairs with its copy like with any other row).
+ * Rows are float16 / bfloat16 / float32 as for fad_kad; the dot products run on the matrix cores into float32, u = fma(S, gamma, coef0)
+ * and u^degree in float32, the sums per lane in float32 over one 128 x 128 tile and in float64 from there, in a fixed order: the same
+ * bits on every run, and for fad_kid_subsets independent of how the subsets are grouped through the workspace (groups of subsets whose
+ * gathered images stay under 128 MiB).  Errors: everything fad_kad_k refuses about rows, with its codes; degree outside 1 .. 4, gamma or
+ * coef0 not finite (or outside float32), a NULL output or index, n_subsets < 1, subset_size > min(n, m) -> FAD_ERR_INVALID;
+ * subset_size < 2 -> FAD_ERR_TOO_FEW_ROWS; an index outside [0, n) / [0, m) -> FAD_ERR_INVALID (checked on the device before any row
+ * is read through it); a kernel sum that is not finite -- NaN/Inf rows, a row whose squared norm overflows float32, or u^degree
+ * beyond float32 -- -> FAD_ERR_NOT_FINITE.  Any refusal leaves every output untouched.  Synchronises `stream`. */
+typedef struct fad_kid_result {
+    double mmd2, kxx_mean, kyy_mean, kxy_mean;
+    double gamma, coef0;
+    int degree;
+    int64_t n, m;
+} fad_kid_result_t;
+int fad_kid(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype, int on_device,
+            int degree, double gamma, double coef0, fad_kid_result_t* out, int device, void* stream);
+int fad_kid_subsets(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype, int on_device,
+                    int degree, double gamma, double coef0, const int32_t* index_x, const int32_t* index_y,
+                    int64_t n_subsets, int64_t subset_size, int index_on_device,
+                    double* mmd2 /* [n_subsets] host */, double* terms /* [n_subsets][3]: kxx, kyy, kxy means; may be NULL */,
+                    double* mean, double* std /* population, ddof = 0; 0 for one subset */, int device, void* stream);
+
 /* ------------------------------------------------------------------ diagnostics (NOT part of the drop-in surface)
  * Nothing in fadtk corresponds to these two calls and no binding of the reference needs them: they exist for bench.py's
  * roofline object (HIP events around the tile kernel on the stream it is launched on) and for the GPU tests that check
