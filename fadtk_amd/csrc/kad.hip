@@ -29,6 +29,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <type_traits>
 #include <vector>
 
@@ -1871,6 +1872,17 @@ static KadWorkspace& workspace(int device) {
     return ws.get(device);
 }
 
+// The start of every public entry that plans passes: the launch budget of this call from FAD_KAD_LAUNCH_BUDGET (unset, empty,
+// unparsable or <= 0: kad_tiles.h's 2^30 -- the variable exists for tests, which cut small passes into several launches with it), and
+// an empty tally for fad_kad_last_plan.  Read per call, so a process may change the variable between two calls.
+static void begin_entry() {
+    const char* e = getenv("FAD_KAD_LAUNCH_BUDGET");
+    char* end = nullptr;
+    const long long v = e && *e ? strtoll(e, &end, 10) : 0;
+    kad::set_launch_budget(end && *end == 0 ? (int64_t)v : 0);
+    kad::reset_plan_tally();
+}
+
 static int64_t depth_elems(int64_t d, int dtype) {
     const int64_t per = kChunk / (int64_t)dtype_size(dtype);
     return cdiv(d, per) * per;
@@ -2365,6 +2377,7 @@ extern "C" {
 int fad_kad_median_distance(const void* x, int64_t n, int64_t ld, int64_t d, int dtype, int on_device, double* sigma, int device,
                             void* stream) {
     using namespace fad;
+    begin_entry();
     if (!sigma) return set_error(FAD_ERR_INVALID, "fad_kad_median_distance: NULL output");
     FAD_TRY(check_rows(x, n, ld, d, dtype, "fad_kad_median_distance"));
     FAD_TRY(check_device(device));
@@ -2385,6 +2398,7 @@ int fad_kad(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int
 int fad_kad_k(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype, int on_device,
               double bandwidth, int kernel, fad_kad_result_t* out, int device, void* stream) {
     using namespace fad;
+    begin_entry();
     if (!out) return set_error(FAD_ERR_INVALID, "fad_kad: NULL output");
     FAD_TRY(check_kernel(kernel, "fad_kad"));
     FAD_TRY(check_rows(x, n, ldx, d, dtype, "fad_kad (x)"));
@@ -2428,6 +2442,7 @@ int fad_kad_k(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, i
 int fad_kad_sweep(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype, int on_device,
                   const double* bandwidths, int n_bw, int relative, int kernel, fad_kad_result_t* out, int device, void* stream) {
     using namespace fad;
+    begin_entry();
     if (!out) return set_error(FAD_ERR_INVALID, "fad_kad_sweep: NULL output");
     if (!bandwidths) return set_error(FAD_ERR_INVALID, "fad_kad_sweep: NULL bandwidths");
     if (n_bw < 1 || n_bw > FAD_KAD_MAX_BANDWIDTHS)
@@ -2507,6 +2522,7 @@ int fad_kad_individual_k(const void* x, int64_t n, int64_t ldx, const void* rows
                          int64_t n_songs, int64_t d, int dtype, int on_device, double bandwidth, int kernel, fad_kad_result_t* base,
                          double* out_mmd2, double* out_kyy_mean, double* out_kxy_mean, int32_t* out_status, int device, void* stream) {
     using namespace fad;
+    begin_entry();
     if (!base) return set_error(FAD_ERR_INVALID, "fad_kad_individual: NULL output");
     FAD_TRY(check_kernel(kernel, "fad_kad_individual"));
     FAD_TRY(check_rows(x, n, ldx, d, dtype, "fad_kad_individual (x)"));
@@ -2635,6 +2651,7 @@ int fad_kad_uncertainty_k(const void* x, int64_t n, int64_t ldx, const void* con
                           int64_t d, int dtype, int on_device, double bandwidth, int kernel, fad_kad_result_t* out, double* cov,
                           double* proj_x, double* proj_y, int device, void* stream) {
     using namespace fad;
+    begin_entry();
     if (!out || !cov) return set_error(FAD_ERR_INVALID, "fad_kad_uncertainty: NULL output");
     FAD_TRY(check_kernel(kernel, "fad_kad_uncertainty"));
     if (n_sets < 1 || n_sets > kad::kUncMaxSets)
@@ -2789,6 +2806,7 @@ int fad_kad_uncertainty_k(const void* x, int64_t n, int64_t ldx, const void* con
 int fad_prdc(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype, int on_device, int k,
              fad_prdc_result_t* out, fad_prdc_detail_t* detail, int device, void* stream) {
     using namespace fad;
+    begin_entry();
     if (!out) return set_error(FAD_ERR_INVALID, "fad_prdc: NULL output");
     if (k < 1 || k > kMaxK) return set_error(FAD_ERR_INVALID, "fad_prdc: k = %d is outside 1 .. %d", k, kMaxK);
     if (!x || !y) return set_error(FAD_ERR_INVALID, "fad_prdc: NULL rows");
@@ -2872,6 +2890,7 @@ int fad_prdc(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, in
 int fad_nearest(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype, int on_device, int k,
                 int authenticity, int32_t* index, float* dist2, float* nn_radius2, fad_nearest_result_t* out, int device, void* stream) {
     using namespace fad;
+    begin_entry();
     if (!out || !index || !dist2) return set_error(FAD_ERR_INVALID, "fad_nearest: NULL output");
     if (k < 1 || k > kMaxK) return set_error(FAD_ERR_INVALID, "fad_nearest: k = %d is outside 1 .. %d", k, kMaxK);
     if (!x || !y) return set_error(FAD_ERR_INVALID, "fad_nearest: NULL rows");
@@ -2940,6 +2959,7 @@ int fad_nn_test(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m,
                 const uint32_t* labels, int64_t n_perm, int labels_on_device, fad_nn_test_result_t* out, int64_t* null_correct_x,
                 int64_t* null_correct_y, int32_t* index, float* dist2, int device, void* stream) {
     using namespace fad;
+    begin_entry();
     if (!out || !null_correct_x || !null_correct_y) return set_error(FAD_ERR_INVALID, "fad_nn_test: NULL output");
     if (k < 1 || k > nnv::kMaxVotes || k % 2 == 0)
         return set_error(FAD_ERR_INVALID, "fad_nn_test: k = %d must be odd and in 1 .. %d", k, nnv::kMaxVotes);
@@ -3017,6 +3037,7 @@ int fad_kad_permutation_test_k(const void* x, int64_t n, int64_t ldx, const void
                                int on_device, double bandwidth, int kernel, const uint32_t* labels, int64_t n_perm, int labels_on_device,
                                fad_kad_result_t* observed, double* null_out, double* p_value, int device, void* stream) {
     using namespace fad;
+    begin_entry();
     if (!observed || !null_out || !p_value) return set_error(FAD_ERR_INVALID, "fad_kad_permutation_test: NULL output");
     FAD_TRY(check_kernel(kernel, "fad_kad_permutation_test"));
     FAD_TRY(perm_check_args(x, n, ldx, y, m, ldy, d, dtype, labels, n_perm));
@@ -3150,6 +3171,14 @@ int fad_kad_permutation_test_k(const void* x, int64_t n, int64_t ldx, const void
     return FAD_OK;
 }
 
+int fad_kad_last_plan(int64_t out[5]) {
+    using namespace fad;
+    if (!out) return set_error(FAD_ERR_INVALID, "fad_kad_last_plan: NULL output");
+    const kad::PlanTally& t = kad::plan_tally();
+    out[0] = t.passes; out[1] = t.launches; out[2] = t.min_launches; out[3] = t.max_launches; out[4] = t.max_walk;
+    return FAD_OK;
+}
+
 int fad_kad_aggregate(const double* t, int n_bw, int64_t n_lab, double* p_values, double* p_aggregated) {
     using namespace fad;
     if (!t || !p_values || !p_aggregated) return set_error(FAD_ERR_INVALID, "fad_kad_aggregate: NULL argument");
@@ -3166,6 +3195,7 @@ int fad_kad_permutation_sweep(const void* x, int64_t n, int64_t ldx, const void*
                               int64_t n_perm, int labels_on_device, fad_kad_result_t* observed, double* null_out, double* p_values,
                               double* p_aggregated, int device, void* stream) {
     using namespace fad;
+    begin_entry();
     const char* who = "fad_kad_permutation_sweep";
     if (!observed || !null_out || !p_values || !p_aggregated) return set_error(FAD_ERR_INVALID, "%s: NULL output", who);
     if (!bandwidths) return set_error(FAD_ERR_INVALID, "%s: NULL bandwidths", who);
@@ -3363,6 +3393,7 @@ int fad_kad_permutation_sweep(const void* x, int64_t n, int64_t ldx, const void*
 int fad_kid(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype, int on_device,
             int degree, double gamma, double coef0, fad_kid_result_t* out, int device, void* stream) {
     using namespace fad;
+    begin_entry();
     if (!out) return set_error(FAD_ERR_INVALID, "fad_kid: NULL output");
     FAD_TRY(check_rows(x, n, ldx, d, dtype, "fad_kid (x)"));
     FAD_TRY(check_rows(y, m, ldy, d, dtype, "fad_kid (y)"));
@@ -3431,6 +3462,7 @@ int fad_kid_subsets(const void* x, int64_t n, int64_t ldx, const void* y, int64_
                     int64_t subset_size, int index_on_device, double* mmd2, double* terms, double* mean, double* std_out, int device,
                     void* stream) {
     using namespace fad;
+    begin_entry();
     if (!mmd2 || !mean || !std_out) return set_error(FAD_ERR_INVALID, "fad_kid_subsets: NULL output");
     if (!index_x || !index_y) return set_error(FAD_ERR_INVALID, "fad_kid_subsets: NULL index");
     FAD_TRY(check_rows(x, n, ldx, d, dtype, "fad_kid_subsets (x)"));

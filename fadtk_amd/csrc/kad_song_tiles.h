@@ -40,8 +40,8 @@ KAD_HD inline Unit cross_unit(int64_t u, int64_t TI, int64_t TJ, int64_t rr) {
     return Unit{u % TJ, I0, I0 + rr < TI ? I0 + rr : TI};
 }
 
-// Units per launch of a pass whose units take at most `unit_tiles` tiles each.
-KAD_HD inline int64_t units_per_launch(int64_t unit_tiles, int64_t depth, bool f32) {
+// Units per launch of a pass whose units take at most `unit_tiles` tiles each (host only: kad::launch_budget).
+inline int64_t units_per_launch(int64_t unit_tiles, int64_t depth, bool f32) {
     const int64_t t = tiles_per_launch(depth, f32) / (unit_tiles > 0 ? unit_tiles : 1);
     return t < 1 ? 1 : t;
 }

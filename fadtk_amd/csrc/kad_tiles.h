@@ -63,13 +63,33 @@ KAD_HD inline int64_t launch_grid(int64_t cnt, int64_t cap) {
     return s < cap ? s : cap;
 }
 
+// host only: what kad::launches planned on this thread since the last reset_plan_tally() -- kad.hip resets it at the start of every
+// public entry and reports it through fad_kad_last_plan, so a test reads the cut a call really took instead of redoing the cost formula.
+// A pass is one call of launches() with total > 0 (every pass of kad.hip plans its launches once; the median's three histogram rounds
+// run the same plan and count as one pass).  walk = the slots one workgroup of a launch walks, launch_slots(cnt) / grid rounded up.
+struct PlanTally { int64_t passes, launches, min_launches, max_launches, max_walk; };
+inline PlanTally& plan_tally() {
+    static thread_local PlanTally t{0, 0, 0, 0, 0};
+    return t;
+}
+inline void reset_plan_tally() { plan_tally() = PlanTally{0, 0, 0, 0, 0}; }
+
 // host only: the launches of a pass of `total` tiles (or work units, kad_song_tiles.h), `per_launch` at most each, and their grids
 struct Launch { int64_t u0, cnt, grid; };
 inline std::vector<Launch> launches(int64_t total, int64_t per_launch, int64_t cap) {
     std::vector<Launch> out;
+    PlanTally& t = plan_tally();
     for (int64_t u0 = 0; u0 < total; u0 += per_launch) {
         const int64_t cnt = per_launch < total - u0 ? per_launch : total - u0;
         out.push_back(Launch{u0, cnt, launch_grid(cnt, cap)});
+        const int64_t walk = (launch_slots(cnt) + out.back().grid - 1) / out.back().grid;
+        if (walk > t.max_walk) t.max_walk = walk;
+    }
+    if (const int64_t nl = (int64_t)out.size()) {
+        t.min_launches = t.passes == 0 || nl < t.min_launches ? nl : t.min_launches;
+        t.max_launches = nl > t.max_launches ? nl : t.max_launches;
+        t.passes += 1;
+        t.launches += nl;
     }
     return out;
 }
@@ -84,13 +104,24 @@ inline std::vector<Launch> launches(int64_t total, int64_t per_launch, int64_t c
 // wave-uniform skip per pair, a 16-step insertion where a value enters), kFlagEpilogue for the cross pass's two threshold tests, counts
 // and ballots per pair.  fad_nearest's cross pass weighs kNearestEpilogue: the top-k of 64-bit keys, a permlane swap
 // per two pairs and a u64 compare per pair, six VALU ops per list entry where a key enters.
+// The budget of cost units per launch is a host-side value of the calling thread, 2^30 unless set_launch_budget changed it: kad.hip
+// sets it from FAD_KAD_LAUNCH_BUDGET at the start of every public entry (for tests: a small budget cuts a small pass into several
+// launches), the CPU cover programs set it directly.  The floor of 64 tiles per launch holds at any budget.  Host only, as is
+// everything that derives a launch size from it.
 constexpr int64_t kSumEpilogue = 128, kHistEpilogue = 2048, kTopkEpilogue = 1024, kFlagEpilogue = 512, kNearestEpilogue = 1536;
-KAD_HD inline int64_t tiles_per_launch_for(int64_t depth, bool f32, int64_t epilogue) {
+constexpr int64_t kLaunchBudget = (int64_t)1 << 30;
+inline int64_t& launch_budget_value() {
+    static thread_local int64_t v = kLaunchBudget;
+    return v;
+}
+inline int64_t launch_budget() { return launch_budget_value(); }
+inline void set_launch_budget(int64_t v) { launch_budget_value() = v > 0 ? v : kLaunchBudget; }
+inline int64_t tiles_per_launch_for(int64_t depth, bool f32, int64_t epilogue) {
     const int64_t cost = (f32 ? 16 * depth : depth) + epilogue;
-    const int64_t t = ((int64_t)1 << 30) / cost;
+    const int64_t t = launch_budget() / cost;
     return t < 64 ? 64 : t;
 }
-KAD_HD inline int64_t tiles_per_launch(int64_t depth, bool f32, bool hist = false) {
+inline int64_t tiles_per_launch(int64_t depth, bool f32, bool hist = false) {
     return tiles_per_launch_for(depth, f32, hist ? kHistEpilogue : kSumEpilogue);
 }
 

@@ -84,8 +84,8 @@ inline void unc_units(const std::vector<int64_t>& blk, int64_t rr, std::vector<U
     seg_start->push_back((int64_t)units->size());
 }
 
-// units per launch of the pass: whole units of at most rr tiles under the launch's tile budget
-KAD_HD inline int64_t unc_units_per_launch(int64_t rr, int64_t depth, bool f32) {
+// units per launch of the pass: whole units of at most rr tiles under the launch's tile budget (host only: kad::launch_budget)
+inline int64_t unc_units_per_launch(int64_t rr, int64_t depth, bool f32) {
     const int64_t t = tiles_per_launch_for(depth, f32, kUncEpilogue) / rr;
     return t < 1 ? 1 : t;
 }

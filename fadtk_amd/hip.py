@@ -672,6 +672,14 @@ def kad_kernel_code(kernel: str) -> int:
     return KAD_KERNELS[kernel]
 
 
+def kad_last_plan() -> dict:
+    """``fad_kad_last_plan``: how this thread's last KAD-family call cut its passes into launches -> dict of ``passes``, ``launches``,
+    ``min_launches`` and ``max_launches`` (of one pass) and ``slots_per_workgroup`` (the most any launch's workgroups walk)."""
+    out = (C.c_int64 * 5)()
+    K.check(K.load_library().fad_kad_last_plan(out), "fad_kad_last_plan")
+    return dict(zip(("passes", "launches", "min_launches", "max_launches", "slots_per_workgroup"), map(int, out)))
+
+
 def kad_median_distance(x, device: int = 0) -> float:
     """``fad_kad_median_distance``: np.median(scipy.spatial.distance.pdist(x)) of one set of rows (numpy on the host, or a torch CUDA
     tensor used in place on torch's current stream)."""

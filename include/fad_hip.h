@@ -615,6 +615,14 @@ int fad_moments_set_timing(fad_moments_t* h, int enabled);
 int fad_moments_last_timing(fad_moments_t* h, float* ms_main_kernel, float* ms_reduce_kernel,
                             int* kernel_variant);
 
+/* Diagnostic: how the last KAD-family call of this thread (fad_kad*, fad_prdc, fad_nearest, fad_nn_test, fad_kid*) cut its passes into
+ * launches.  out = { passes planned, launches planned, fewest launches of one pass, most launches of one pass, most slots one
+ * workgroup of a launch walks }; all 0 when the call was refused before it planned a pass.  A pass is one walk of a pair space (the
+ * median's three histogram rounds share one plan and count once; every word group of a permutation pass is one).  The environment
+ * variable FAD_KAD_LAUNCH_BUDGET (cost units per launch, default 2^30, read at the start of every such call; a launch never holds
+ * fewer than 64 tiles) exists for tests, which cut small passes into several launches with it. */
+int fad_kad_last_plan(int64_t out[5]);
+
 /* A HIP stream confined to a subset of the device's CUs (hipExtStreamCreateWithCUMask; `mask` = `words` x 32 bits, bit i = CU i in
  * the runtime's numbering, which on this 8-XCD part walks the XCDs first: bit i -> XCD i % 8).  bench.py's --chain-cus layout
  * experiment puts the square-root chains and the moments kernels on disjoint CU sets with it; nothing in the library uses it.

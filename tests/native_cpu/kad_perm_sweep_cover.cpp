@@ -105,6 +105,14 @@ int main() {
     CHECK(perm_sweep_walks(4, 301).size() == 2 && perm_sweep_walks(4, 301)[0].kernel_nb == 2, "B = 4, P = 300 is not two walks of 2");
     CHECK(perm_sweep_walks(3, 200).size() == 1 && perm_sweep_walks(3, 200)[0].nb == 3, "B = 3, P = 199 is not one walk of 3 in the kernel of 4");
     CHECK(perm_sweep_walks(5, 200).size() == 2 && perm_sweep_walks(5, 200)[1].kernel_nb == 1, "B = 5, P = 199 is not 4 + 1");
+    // under a small launch budget (kad::set_launch_budget, what FAD_KAD_LAUNCH_BUDGET sets in kad.hip): the shapes of the GPU test of the cut
+    for (int64_t budget : {(int64_t)1, (int64_t)1 << 18}) {
+        fad::kad::set_launch_budget(budget);
+        check(2700, 3, 34, 128, false, 512, "cut test, B = 3, P = 33");
+        check(2700, 3, 34, 24, true, 512, "cut test f32, B = 3, P = 33");
+        check(2700, 5, 301, 80, false, 512, "cut test, B = 5, P = 300");
+    }
+    fad::kad::set_launch_budget(0);
     if (fails) { printf("%d failures\n", fails); return 1; }
     printf("OK\n");
     return 0;

@@ -86,6 +86,14 @@ int main() {
     check(200000, 201, 128, false, 512, "config-3, P = 200");
     check(2000000, 1001, 128, false, 512, "N = 2e6, P = 1000");
     check(2000000, 2049, 2048, true, 64, "N = 2e6 f32, P = 2048");
+    // under a small launch budget (kad::set_launch_budget, what FAD_KAD_LAUNCH_BUDGET sets in kad.hip): the shapes of the GPU test of the cut
+    for (int64_t budget : {(int64_t)1, (int64_t)1 << 18}) {
+        fad::kad::set_launch_budget(budget);
+        check(2700, 34, 128, false, 512, "cut test, P = 33");
+        check(2700, 34, 24, true, 512, "cut test f32, P = 33");
+        check(2700, 1100, 80, false, 512, "cut test, two groups");
+    }
+    fad::kad::set_launch_budget(0);
     if (fails) { printf("%d failures\n", fails); return 1; }
     printf("OK\n");
     return 0;

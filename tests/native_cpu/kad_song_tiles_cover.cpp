@@ -144,6 +144,18 @@ int main() {
     for (int k = 0; k < 300; ++k) mixed.push_back(rand() % 400);
     check_band(mixed, 128, false, 512, "a long song among short ones");
 
+    // under a small launch budget (kad::set_launch_budget, what FAD_KAD_LAUNCH_BUDGET sets in kad.hip): the shapes of the GPU test of the cut
+    for (int64_t budget : {(int64_t)1, (int64_t)1 << 18}) {
+        set_launch_budget(budget);
+        CHECK(units_per_launch(1, 128, false) == tiles_per_launch(128, false) && units_per_launch(kBandPiece, 128, false) == tiles_per_launch(128, false) / kBandPiece,
+              "units_per_launch reads the budget");
+        if (budget == 1) CHECK(units_per_launch(1, 128, false) == 64 && units_per_launch(kBandPiece, 2048, true) == 2, "the floor at budget 1");
+        check_cross(1290, 1410, 128, false, 512);
+        check_cross(1290, 1410, 24, true, 512);
+        check_band({0, 1, 2, 127, 129, 300, 851}, 128, false, 512, "the cut test's songs");
+        check_band({0, 1, 2, 127, 129, 300, 851}, 24, true, 512, "the cut test's songs f32");
+    }
+    set_launch_budget(0);
     printf(fails ? "FAILED (%d)\n" : "OK\n", fails);
     return fails ? 1 : 0;
 }

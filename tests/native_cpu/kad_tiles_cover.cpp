@@ -108,6 +108,56 @@ int main() {
         CHECK(tiles_per_launch(depth, false, true) < tiles_per_launch(depth, false), "histogram launches at depth %lld", (long long)depth);
         if (depth <= 128) CHECK(tiles_per_launch(depth, false, true) * 4 <= tiles_per_launch(depth, false), "histogram launches at depth %lld", (long long)depth);
     }
+    // the launch budget (the seam FAD_KAD_LAUNCH_BUDGET sets in kad.hip) and the tally of what launches() planned
+    CHECK(launch_budget() == ((int64_t)1 << 30), "default budget %lld", (long long)launch_budget());
+    CHECK(tiles_per_launch_for(2048, true, kSumEpilogue) == 32640, "D = 2048 f32 sums: %lld tiles per launch", (long long)tiles_per_launch_for(2048, true, kSumEpilogue));
+    CHECK(tiles_per_launch(128, false) == ((int64_t)1 << 30) / 256, "D = 128 16-bit sums: %lld", (long long)tiles_per_launch(128, false));
+    {
+        reset_plan_tally();
+        const std::vector<Launch> l = launches(tri_tiles(257), tiles_per_launch(2048, true), 512);   // 33 153 tiles over 32 640
+        CHECK(l.size() == 2 && l[0].u0 == 0 && l[0].cnt == 32640 && l[1].u0 == 32640 && l[1].cnt == 513, "T = 257 plans %zu launches", l.size());
+        CHECK(l[0].grid == 512 && l[1].grid == 512, "grids %lld and %lld", (long long)l[0].grid, (long long)l[1].grid);
+        const PlanTally t = plan_tally();
+        CHECK(t.passes == 1 && t.launches == 2 && t.min_launches == 2 && t.max_launches == 2, "tally %lld %lld %lld %lld", (long long)t.passes,
+              (long long)t.launches, (long long)t.min_launches, (long long)t.max_launches);
+        CHECK(t.max_walk == (32640 + 511) / 512, "walk %lld", (long long)t.max_walk);
+        launches(tri_tiles(256), tiles_per_launch(2048, true), 512);                                 // 32 896 tiles: still two
+        launches(100, tiles_per_launch(2048, true), 512);                                            // one launch of 104 slots on 104 workgroups
+        launches(0, 64, 512);                                                                        // nothing to plan: not a pass
+        const PlanTally u = plan_tally();
+        CHECK(u.passes == 3 && u.launches == 5 && u.min_launches == 1 && u.max_launches == 2 && u.max_walk == t.max_walk, "tally %lld %lld %lld %lld %lld",
+              (long long)u.passes, (long long)u.launches, (long long)u.min_launches, (long long)u.max_launches, (long long)u.max_walk);
+        reset_plan_tally();
+        CHECK(plan_tally().passes == 0 && plan_tally().launches == 0 && plan_tally().min_launches == 0 && plan_tally().max_walk == 0, "reset");
+    }
+    for (int64_t budget : {(int64_t)1, (int64_t)1000, (int64_t)1 << 18, (int64_t)1 << 24}) {
+        set_launch_budget(budget);
+        CHECK(launch_budget() == budget, "budget %lld", (long long)budget);
+        for (int64_t depth : {8, 24, 128, 512, 2048})
+            for (int f32 = 0; f32 < 2; ++f32)
+                for (int64_t ep : {kSumEpilogue, kHistEpilogue, kTopkEpilogue, kFlagEpilogue, kNearestEpilogue, 8 * kSumEpilogue}) {
+                    const int64_t want = budget / ((f32 ? 16 * depth : depth) + ep), got = tiles_per_launch_for(depth, f32 != 0, ep);
+                    CHECK(got == (want < 64 ? 64 : want), "budget %lld depth %lld f32 %d epilogue %lld: %lld", (long long)budget, (long long)depth, f32,
+                          (long long)ep, (long long)got);
+                    if (budget == 1) CHECK(got == 64, "the floor at budget 1: %lld", (long long)got);
+                }
+        CHECK(tiles_per_launch(128, false) == tiles_per_launch_for(128, false, kSumEpilogue) && tiles_per_launch(128, false, true) == tiles_per_launch_for(128, false, kHistEpilogue),
+              "tiles_per_launch reads the budget");
+    }
+    set_launch_budget((int64_t)1 << 18);                      // 1024 tiles per launch at D = 128 in 16 bit: 46 blocks' triangle is 1024 + 57
+    {
+        reset_plan_tally();
+        const std::vector<Launch> l = launches(tri_tiles(46), tiles_per_launch(128, false), 512);
+        CHECK(l.size() == 2 && l[0].cnt == 1024 && l[1].cnt == 57 && l[1].grid == 64, "46 blocks at 2^18");
+        CHECK(plan_tally().max_walk == 2, "walk %lld", (long long)plan_tally().max_walk);
+    }
+    set_launch_budget(1);                                     // the floor: every pair once when every launch holds 64 tiles
+    check_tri_pairs(1290, tiles_per_launch(128, false), 512);
+    check_rect_pairs(1290, 1410, tiles_per_launch(24, true), 512);
+    for (int64_t bad : {(int64_t)0, (int64_t)-5}) {           // <= 0: the default
+        set_launch_budget(bad);
+        CHECK(launch_budget() == ((int64_t)1 << 30) && tiles_per_launch(2048, true) == 32640, "budget %lld falls back", (long long)bad);
+    }
     printf("kad tiles: %lld pair cases, tiles per launch D=128 f16 %lld (histogram %lld), D=512 f16 %lld (histogram %lld), D=2048 f32 %lld\n",
            (long long)cases, (long long)tiles_per_launch(128, false), (long long)tiles_per_launch(128, false, true),
            (long long)tiles_per_launch(512, false), (long long)tiles_per_launch(512, false, true), (long long)tiles_per_launch(2048, true));

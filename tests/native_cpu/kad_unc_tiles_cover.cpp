@@ -121,6 +121,16 @@ int main() {
     check(1000000, {1000000}, 128, false, caps[0], "n=1e6 S=1");
     check(1000000, ragged(64, 2, 300), 128, false, caps[0], "n=1e6 S=64 ragged");
     check(1000000, ragged(64, 2, 300), 1024, true, caps[1], "n=1e6 S=64 ragged f32");
+    // under a small launch budget (kad::set_launch_budget, what FAD_KAD_LAUNCH_BUDGET sets in kad.hip): the shapes of the GPU test of the cut
+    for (int64_t budget : {(int64_t)1, (int64_t)1 << 18}) {
+        fad::kad::set_launch_budget(budget);
+        if (budget == 1) CHECK(fad::kad::unc_units_per_launch(1, 128, false) == 64 && fad::kad::unc_rows_per_unit(1000000, fad::kad::tiles_per_launch_for(128, false, fad::kad::kUncEpilogue)) == 1,
+                               "the floor at budget 1");
+        check(1290, {1410, 700}, 128, false, caps[0], "cut test, two sets");
+        check(1290, {1410, 700}, 24, true, caps[0], "cut test, two sets f32");
+        check(2700, {}, 128, false, caps[0], "cut test, pooled rows");
+    }
+    fad::kad::set_launch_budget(0);
     if (fails) { printf("%d failures\n", fails); return 1; }
     printf("OK\n");
     return 0;

@@ -99,6 +99,14 @@ int main() {
     CHECK(kid::plan(60, 129, 5120, kid::kImageBudget).size() == 2, "60 subsets of 129 float32 rows at D = 1280: %zu groups",
           kid::plan(60, 129, 5120, kid::kImageBudget).size());
 
+    // under a small launch budget (kad::set_launch_budget, what FAD_KAD_LAUNCH_BUDGET sets in kad.hip): the shapes of the GPU test of the cut
+    for (int64_t budget : {(int64_t)1, (int64_t)1 << 18}) {
+        kad::set_launch_budget(budget);
+        check_units(129, 17, 128, false, 512);
+        check_units(129, 17, 24, true, 512);
+        check_units(300, 100, 16, false, 512);
+    }
+    kad::set_launch_budget(0);
     printf(fails ? "FAILED (%d)\n" : "OK\n", fails);
     return fails ? 1 : 0;
 }

@@ -24,7 +24,8 @@ static void check_pass(int64_t n, int64_t m, int64_t depth, bool f32, int64_t ep
     for (const Launch& l : ls) {
         const int64_t G = l.grid;
         CHECK(G % kXcds == 0 && G >= kXcds && G <= launch_slots(l.cnt) && G <= cap, "grid %lld for %lld units", (long long)G, (long long)l.cnt);
-        CHECK(ls.size() == 1 || l.cnt >= kPrdcLaunchUnits || &l == &ls.back(), "n %lld m %lld: a launch of %lld units", (long long)n,
+        // (a launch budget under kPrdcLaunchUnits tiles -- only a test's FAD_KAD_LAUNCH_BUDGET gives one -- cannot hold that many units)
+        CHECK(ls.size() == 1 || l.cnt >= kPrdcLaunchUnits || &l == &ls.back() || per < kPrdcLaunchUnits, "n %lld m %lld: a launch of %lld units", (long long)n,
               (long long)m, (long long)l.cnt);
         int64_t tiles = 0;
         for (int64_t w = 0; w < G; ++w)
@@ -57,6 +58,17 @@ int main() {
     }
     check_pass(1000000, 1000000, 128, false, kTopkEpilogue, 512);         // n = m = 10^6 at D = 128, float16
     check_pass(1000000, 1000000, 128, false, kFlagEpilogue, 512);
+    // under a small launch budget (kad::set_launch_budget, what FAD_KAD_LAUNCH_BUDGET sets in kad.hip): the shapes of the GPU test of the cut
+    for (int64_t budget : {(int64_t)1, (int64_t)1 << 18, (int64_t)1 << 21}) {
+        set_launch_budget(budget);
+        for (int64_t ep : {kTopkEpilogue, kFlagEpilogue, kNearestEpilogue}) {
+            check_pass(1290, 1410, 128, false, ep, 512);
+            check_pass(2700, 2700, 24, true, ep, 512);
+            check_pass(5800, 1300, 128, false, ep, 512);
+            check_pass(7100, 7100, 24, true, ep, 512);
+        }
+    }
+    set_launch_budget(0);
     printf(fails ? "FAILED (%d)\n" : "OK\n", fails);
     return fails ? 1 : 0;
 }
