@@ -30,6 +30,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <optional>
 #include <type_traits>
 #include <vector>
 
@@ -1872,6 +1873,28 @@ static KadWorkspace& workspace(int device) {
     return ws.get(device);
 }
 
+// What the helpers of one call share: the rows' dtype, the kernel family (FAD_KAD_GAUSSIAN where the entry has none), the device, the
+// stream and this thread's workspace on the device.  A local of its entry, opened once the arguments are checked and never copied: it
+// owns the guard that gives the caller's device back when the entry returns.
+struct Ctx {
+    int dtype = FAD_F32, kernel = FAD_KAD_GAUSSIAN, device = -1;
+    hipStream_t st = nullptr;
+    KadWorkspace* ws = nullptr;
+    std::optional<DeviceGuard> guard;
+    Ctx() = default;
+    Ctx(const Ctx&) = delete;
+    Ctx& operator=(const Ctx&) = delete;
+    int open(int dtype_, int kernel_, int device_, void* stream) {
+        FAD_TRY(check_device(device_));
+        guard.emplace(device_);
+        if (!guard->ok) return set_error(FAD_ERR_HIP, "hipSetDevice(%d) failed", device_);
+        dtype = dtype_; kernel = kernel_; device = device_;
+        st = static_cast<hipStream_t>(stream);
+        ws = &workspace(device_);
+        return FAD_OK;
+    }
+};
+
 // The start of every public entry that plans passes: the launch budget of this call from FAD_KAD_LAUNCH_BUDGET (unset, empty,
 // unparsable or <= 0: kad_tiles.h's 2^30 -- the variable exists for tests, which cut small passes into several launches with it), and
 // an empty tally for fad_kad_last_plan.  Read per call, so a process may change the variable between two calls.
@@ -1900,45 +1923,113 @@ static int check_rows(const void* x, int64_t n, int64_t ld, int64_t d, int dtype
     return FAD_OK;
 }
 
-// rows -> the set's padded image and h (no check of the norms)
-static int pack_image(int slot, const void* x, int64_t n, int64_t ld, int64_t d, int dtype, int on_device, hipStream_t st,
-                      KadWorkspace& ws, Packed* out) {
-    const size_t es = dtype_size(dtype);
-    const int64_t dp = depth_elems(d, dtype), n_pad = kad::blocks(n) * kTile;
-    if (!on_device) {
-        FAD_TRY(ws.raw[slot].reserve((size_t)(n * d) * es));
-        FAD_HIP_TRY(hipMemcpy2DAsync(ws.raw[slot].p, (size_t)d * es, x, (size_t)ld * es, (size_t)d * es, (size_t)n, hipMemcpyHostToDevice, st));
-        x = ws.raw[slot].p;
-        ld = d;
+static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// The regions of one workspace buffer: each starts on a 256-byte boundary, in the order they are added.  add<T>(count) before
+// reserve(buffer), ptr(region) after it.
+template <typename T> struct Region { size_t at; };
+struct Carve {
+    size_t size = 0;
+    char* base = nullptr;
+    template <typename T> Region<T> add(int64_t count) {
+        const Region<T> r{size};
+        size += align256((size_t)count * sizeof(T));
+        return r;
     }
-    FAD_TRY(ws.img[slot].reserve((size_t)(n_pad * dp) * es));
-    FAD_TRY(ws.h[slot].reserve((size_t)n_pad * sizeof(float)));
-    FAD_TRY(ws.small.reserve(4096 * sizeof(double) + 2 * kHistBins * sizeof(unsigned long long)));
-    float* h = static_cast<float*>(ws.h[slot].p);
-    const dim3 grid((unsigned)cdiv(n_pad, 4));
-    switch (dtype) {
-        case FAD_F16: kad_pack_kernel<_Float16><<<grid, 256, 0, st>>>(static_cast<const _Float16*>(x), n, ld, d, static_cast<_Float16*>(ws.img[slot].p), dp, n_pad, h); break;
-        case FAD_BF16: kad_pack_kernel<__bf16><<<grid, 256, 0, st>>>(static_cast<const __bf16*>(x), n, ld, d, static_cast<__bf16*>(ws.img[slot].p), dp, n_pad, h); break;
-        default: kad_pack_kernel<float><<<grid, 256, 0, st>>>(static_cast<const float*>(x), n, ld, d, static_cast<float*>(ws.img[slot].p), dp, n_pad, h); break;
+    int reserve(DevBuf& buf) {
+        FAD_TRY(buf.reserve(size));
+        base = static_cast<char*>(buf.p);
+        return FAD_OK;
+    }
+    template <typename T> T* ptr(Region<T> r) const { return reinterpret_cast<T*>(base + r.at); }
+};
+
+// ws.small as every entry reserves it: 4096 doubles of places (info, offsets, sums, per-set info), then the two histograms
+static int reserve_small(KadWorkspace& ws) { return ws.small.reserve(4096 * sizeof(double) + 2 * kHistBins * sizeof(unsigned long long)); }
+
+// host rows -> ws.raw[slot] (reserved by the caller) from row `raw_row` on, at a pitch of d; device rows stay where they are
+static int stage_rows(const Ctx& cx, int slot, int64_t raw_row, int on_device, const void** src, int64_t rn, int64_t* ld, int64_t d) {
+    if (on_device) return FAD_OK;
+    const size_t es = dtype_size(cx.dtype);
+    char* raw = static_cast<char*>(cx.ws->raw[slot].p) + (size_t)(raw_row * d) * es;
+    FAD_HIP_TRY(hipMemcpy2DAsync(raw, (size_t)d * es, *src, (size_t)*ld * es, (size_t)d * es, (size_t)rn, hipMemcpyHostToDevice, cx.st));
+    *src = raw;
+    *ld = d;
+    return FAD_OK;
+}
+
+// rn rows of `src` -> r_pad rows of an image at `img` (depth dp, zero padding) and their h: the one launch site of kad_pack_kernel
+static int pack_rows(const Ctx& cx, int slot, int64_t raw_row, int on_device, const void* src, int64_t rn, int64_t ld, int64_t d, void* img,
+                     int64_t dp, int64_t r_pad, float* h) {
+    FAD_TRY(stage_rows(cx, slot, raw_row, on_device, &src, rn, &ld, d));
+    const dim3 grid((unsigned)cdiv(r_pad, 4));
+    switch (cx.dtype) {
+        case FAD_F16: kad_pack_kernel<_Float16><<<grid, 256, 0, cx.st>>>(static_cast<const _Float16*>(src), rn, ld, d, static_cast<_Float16*>(img), dp, r_pad, h); break;
+        case FAD_BF16: kad_pack_kernel<__bf16><<<grid, 256, 0, cx.st>>>(static_cast<const __bf16*>(src), rn, ld, d, static_cast<__bf16*>(img), dp, r_pad, h); break;
+        default: kad_pack_kernel<float><<<grid, 256, 0, cx.st>>>(static_cast<const float*>(src), rn, ld, d, static_cast<float*>(img), dp, r_pad, h); break;
     }
     FAD_HIP_TRY(hipGetLastError());
+    return FAD_OK;
+}
+
+// rows -> the set's padded image and h (no check of the norms)
+static int pack_image(const Ctx& cx, int slot, const void* x, int64_t n, int64_t ld, int64_t d, int on_device, Packed* out) {
+    KadWorkspace& ws = *cx.ws;
+    const size_t es = dtype_size(cx.dtype);
+    const int64_t dp = depth_elems(d, cx.dtype), n_pad = kad::blocks(n) * kTile;
+    if (!on_device) FAD_TRY(ws.raw[slot].reserve((size_t)(n * d) * es));
+    FAD_TRY(ws.img[slot].reserve((size_t)(n_pad * dp) * es));
+    FAD_TRY(ws.h[slot].reserve((size_t)n_pad * sizeof(float)));
+    FAD_TRY(reserve_small(ws));
+    float* h = static_cast<float*>(ws.h[slot].p);
+    FAD_TRY(pack_rows(cx, slot, 0, on_device, x, n, ld, d, ws.img[slot].p, dp, n_pad, h));
     *out = Packed{static_cast<const char*>(ws.img[slot].p), h, n, dp * (int64_t)es, (int)(dp * (int64_t)es / kChunk), 0.0};
     return FAD_OK;
 }
 
 // rows -> the set's padded image and h; reads back the norm sum and checks every norm is finite
-static int pack_set(int slot, const void* x, int64_t n, int64_t ld, int64_t d, int dtype, int on_device, hipStream_t st,
-                    KadWorkspace& ws, Packed* out) {
-    FAD_TRY(pack_image(slot, x, n, ld, d, dtype, on_device, st, ws, out));
-    double* info_d = static_cast<double*>(ws.small.p) + 2 * slot;
-    kad_norm_info_kernel<<<1, 256, 0, st>>>(out->h, n, info_d);
+static int pack_set(const Ctx& cx, int slot, const void* x, int64_t n, int64_t ld, int64_t d, int on_device, Packed* out) {
+    FAD_TRY(pack_image(cx, slot, x, n, ld, d, on_device, out));
+    double* info_d = static_cast<double*>(cx.ws->small.p) + 2 * slot;
+    kad_norm_info_kernel<<<1, 256, 0, cx.st>>>(out->h, n, info_d);
     FAD_HIP_TRY(hipGetLastError());
     double info[2];
-    FAD_HIP_TRY(hipMemcpyAsync(info, info_d, sizeof(info), hipMemcpyDeviceToHost, st));
-    FAD_HIP_TRY(hipStreamSynchronize(st));
+    FAD_HIP_TRY(hipMemcpyAsync(info, info_d, sizeof(info), hipMemcpyDeviceToHost, cx.st));
+    FAD_HIP_TRY(hipStreamSynchronize(cx.st));
     if (info[1] != 0.0)
         return set_error(FAD_ERR_NOT_FINITE, "KAD: %lld of %lld rows have a NaN/Inf norm", (long long)info[1], (long long)n);
     out->norm_sum = info[0];
+    return FAD_OK;
+}
+
+// Several sets in one image, Z (ws.img[0] and ws.h[0], z_pad rows): set i packed from image row r0 on, over r_pad rows (its own rows,
+// then zero padding); host rows are staged one set after the other in ws.raw[0].  With set_info, kad_norm_info_kernel of set i follows
+// its pack, into the per-set info of ws.small (doubles 1024 + 2 i).  *z: the whole image, n and norm_sum left to the caller.
+struct RowSet { const void* src; int64_t rows, ld, r0, r_pad; };
+static int pack_sets(const Ctx& cx, const RowSet* sets, int n_sets, int64_t d, int on_device, int64_t z_pad, bool set_info, Packed* z) {
+    KadWorkspace& ws = *cx.ws;
+    const size_t es = dtype_size(cx.dtype);
+    const int64_t dp = depth_elems(d, cx.dtype), pitch = dp * (int64_t)es;
+    int64_t total = 0;
+    for (int i = 0; i < n_sets; ++i) total += sets[i].rows;
+    FAD_TRY(ws.img[0].reserve((size_t)(z_pad * pitch)));
+    FAD_TRY(ws.h[0].reserve((size_t)z_pad * sizeof(float)));
+    FAD_TRY(reserve_small(ws));
+    if (!on_device) FAD_TRY(ws.raw[0].reserve((size_t)(total * d) * es));
+    char* zimg = static_cast<char*>(ws.img[0].p);
+    float* zh = static_cast<float*>(ws.h[0].p);
+    double* info_d = static_cast<double*>(ws.small.p) + 1024;
+    int64_t staged = 0;
+    for (int i = 0; i < n_sets; ++i) {
+        const RowSet& s = sets[i];
+        FAD_TRY(pack_rows(cx, 0, staged, on_device, s.src, s.rows, s.ld, d, zimg + s.r0 * pitch, dp, s.r_pad, zh + s.r0));
+        staged += s.rows;
+        if (set_info) {
+            kad_norm_info_kernel<<<1, 256, 0, cx.st>>>(zh + s.r0, s.rows, info_d + 2 * i);
+            FAD_HIP_TRY(hipGetLastError());
+        }
+    }
+    *z = Packed{zimg, zh, 0, pitch, (int)(pitch / kChunk), 0.0};
     return FAD_OK;
 }
 
@@ -1978,16 +2069,17 @@ static PassArgs pass_args(const Packed& a, const Packed& b, bool tri, float c) {
     return p;
 }
 
-static std::vector<kad::Launch> pass_launches(const PassArgs& p, int dtype, bool hist, int device) {
+static std::vector<kad::Launch> pass_launches(const Ctx& cx, const PassArgs& p, bool hist) {
     const int64_t total = p.tri ? kad::tri_tiles(p.tiles_j) : kad::blocks(p.n_a) * p.tiles_j;
-    return kad::launches(total, kad::tiles_per_launch(p.pitch / (int64_t)dtype_size(dtype), dtype == FAD_F32, hist), grid_cap(device));
+    return kad::launches(total, kad::tiles_per_launch(p.pitch / (int64_t)dtype_size(cx.dtype), cx.dtype == FAD_F32, hist), grid_cap(cx.device));
 }
 
-static int median_of_packed(const Packed& x, int dtype, int device, hipStream_t st, KadWorkspace& ws, double* sigma) {
+static int median_of_packed(const Ctx& cx, const Packed& x, double* sigma) {
+    const hipStream_t st = cx.st;
     const int64_t P = x.n * (x.n - 1) / 2;
     PassArgs p = pass_args(x, x, true, 0.f);
-    p.hist = reinterpret_cast<unsigned long long*>(static_cast<double*>(ws.small.p) + 4096);
-    const auto launches = pass_launches(p, dtype, true, device);
+    p.hist = reinterpret_cast<unsigned long long*>(static_cast<double*>(cx.ws->small.p) + 4096);
+    const auto launches = pass_launches(cx, p, true);
     static const int shifts[3] = {21, 10, 0}, widths[3] = {11, 11, 10};
     uint64_t rank[2] = {(uint64_t)((P - 1) / 2), (uint64_t)(P / 2)};
     unsigned int pref[2] = {0, 0};
@@ -1998,7 +2090,7 @@ static int median_of_packed(const Packed& x, int dtype, int device, hipStream_t 
         p.lo_shift = shifts[pass]; p.bits = widths[pass]; p.hi_shift = shifts[pass] + widths[pass];
         for (const kad::Launch& l : launches) {
             p.u0 = l.u0; p.cnt = l.cnt;
-            FAD_TRY(with_dtype(dtype, [&](auto dt) { kad_pass_kernel<dt, MODE_HIST><<<(unsigned)l.grid, kThreads, kLdsHist, st>>>(p); }));
+            FAD_TRY(with_dtype(cx.dtype, [&](auto dt) { kad_pass_kernel<dt, MODE_HIST><<<(unsigned)l.grid, kThreads, kLdsHist, st>>>(p); }));
         }
         FAD_HIP_TRY(hipMemcpyAsync(hist.data(), p.hist, hist.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
         FAD_HIP_TRY(hipStreamSynchronize(st));
@@ -2025,37 +2117,47 @@ static int median_of_packed(const Packed& x, int dtype, int device, hipStream_t 
 }
 
 // N sum passes into consecutive slot ranges, then sums_d[q] = pass q's slots summed in a fixed order (enqueued, not read back).
-// fad_kad runs XX, YY and XY; fad_kad_individual XX alone, so its Kxx comes from the same launches, slots and sum as fad_kad's.
-template <int N>
-static int sum_passes(const PassArgs (&passes)[N], int dtype, int kernel, int device, hipStream_t st, KadWorkspace& ws, double* sums_d) {
+// launch(p, l) enqueues launch l of a pass with p's slots, u0 and cnt set: kad_pass_kernel for the KAD entries (kad_sum_passes),
+// kid_pass_kernel for fad_kid, which so has the same launches, slots and sum.
+template <int N, typename L>
+static int sum_passes(const Ctx& cx, const PassArgs (&passes)[N], double* sums_d, L&& launch) {
+    KadWorkspace& ws = *cx.ws;
     std::vector<kad::Launch> launches[N];
     int64_t off[N + 1] = {0};
     for (int q = 0; q < N; ++q) {
-        launches[q] = pass_launches(passes[q], dtype, false, device);
+        launches[q] = pass_launches(cx, passes[q], false);
         off[q + 1] = off[q];
         for (const kad::Launch& l : launches[q]) off[q + 1] += l.grid;
     }
     FAD_TRY(ws.slots.reserve((size_t)off[N] * sizeof(double)));
     int64_t* off_d = reinterpret_cast<int64_t*>(static_cast<double*>(ws.small.p) + 8);
-    FAD_HIP_TRY(hipMemcpyAsync(off_d, off, sizeof(off), hipMemcpyHostToDevice, st));
+    FAD_HIP_TRY(hipMemcpyAsync(off_d, off, sizeof(off), hipMemcpyHostToDevice, cx.st));
     for (int q = 0; q < N; ++q) {
         PassArgs p = passes[q];
         p.slots = static_cast<double*>(ws.slots.p) + off[q];
         for (const kad::Launch& l : launches[q]) {
             p.u0 = l.u0; p.cnt = l.cnt;
-            FAD_TRY(with_dtype_kernel(dtype, kernel, [&](auto dt, auto kf) {
-                kad_pass_kernel<dt, MODE_SUM, kf><<<(unsigned)l.grid, kThreads, kLdsSum, st>>>(p);
-            }));
+            FAD_TRY(launch(p, l));
             p.slots += l.grid;
         }
     }
-    kad_slots_sum_kernel<<<N, 256, 0, st>>>(static_cast<const double*>(ws.slots.p), off_d, sums_d);
+    kad_slots_sum_kernel<<<N, 256, 0, cx.st>>>(static_cast<const double*>(ws.slots.p), off_d, sums_d);
     FAD_HIP_TRY(hipGetLastError());
     return FAD_OK;
 }
 
+// fad_kad runs XX, YY and XY; fad_kad_individual XX alone, so its Kxx comes from the same launches, slots and sum as fad_kad's.
+template <int N>
+static int kad_sum_passes(const Ctx& cx, const PassArgs (&passes)[N], double* sums_d) {
+    return sum_passes(cx, passes, sums_d, [&](const PassArgs& p, const kad::Launch& l) {
+        return with_dtype_kernel(cx.dtype, cx.kernel, [&](auto dt, auto kf) {
+            kad_pass_kernel<dt, MODE_SUM, kf><<<(unsigned)l.grid, kThreads, kLdsSum, cx.st>>>(p);
+        });
+    });
+}
+
 // c = log2(e) / sigma^2 (1 / sigma^2 for iq and imq, whose epilogue takes t = c d^2 / 2 itself) as the kernels' float32: the one place a
-// bandwidth becomes a kernel constant, for resolve_sigma and fad_kad_sweep alike
+// bandwidth becomes a kernel constant, for resolve_sigma and resolve_sigmas alike
 enum SigmaCheck { SIGMA_OK = 0, SIGMA_NOT_POSITIVE = 1, SIGMA_OUTSIDE_F32 = 2 };
 static SigmaCheck sigma_constant(double sigma, int kernel, float* c) {
     if (!(sigma > 0) || !std::isfinite(sigma)) return SIGMA_NOT_POSITIVE;
@@ -2066,11 +2168,10 @@ static SigmaCheck sigma_constant(double sigma, int kernel, float* c) {
 }
 
 // sigma = `bandwidth`, or the median pairwise distance of x when it is 0, and its c (sigma_constant)
-static int resolve_sigma(const Packed& x, double bandwidth, int kernel, int dtype, int device, hipStream_t st, KadWorkspace& ws, const char* who,
-                         double* sigma, float* c) {
+static int resolve_sigma(const Ctx& cx, const Packed& x, double bandwidth, const char* who, double* sigma, float* c) {
     *sigma = bandwidth;
-    if (!(*sigma > 0)) FAD_TRY(median_of_packed(x, dtype, device, st, ws, sigma));
-    switch (sigma_constant(*sigma, kernel, c)) {
+    if (!(*sigma > 0)) FAD_TRY(median_of_packed(cx, x, sigma));
+    switch (sigma_constant(*sigma, cx.kernel, c)) {
         case SIGMA_NOT_POSITIVE:
             return set_error(FAD_ERR_INVALID, "%s: bandwidth %g (the median pairwise distance of the baseline when none is given) must be > 0"
                              " -- are all baseline rows identical?", who, *sigma);
@@ -2080,13 +2181,43 @@ static int resolve_sigma(const Packed& x, double bandwidth, int kernel, int dtyp
     }
 }
 
+// A sweep's list of bandwidths, or of factors of the median (relative): every entry finite and > 0.  Checked before the device is opened.
+static int check_bandwidths(const double* bandwidths, int n_bw, int relative, const char* who, bool pooled) {
+    for (int b = 0; b < n_bw; ++b)
+        if (!(bandwidths[b] > 0) || !std::isfinite(bandwidths[b]))
+            return set_error(FAD_ERR_INVALID, "%s: %s %d is %g; every one must be finite and > 0 (the %s is the factor 1)", who,
+                             relative ? "factor" : "bandwidth", b, bandwidths[b], pooled ? "pooled median" : "median");
+    return FAD_OK;
+}
+
+// sigma[b] = bandwidths[b], or bandwidths[b] times the median pairwise distance of x (found once) when relative, and c[b] as
+// sigma_constant forms it.  x is the baseline for fad_kad_sweep and the pooled rows for fad_kad_permutation_sweep.
+static int resolve_sigmas(const Ctx& cx, const Packed& x, const double* bandwidths, int n_bw, int relative, const char* who, bool pooled,
+                          double* sigma, float* c) {
+    double median = 1.0;
+    if (relative) {
+        FAD_TRY(median_of_packed(cx, x, &median));
+        if (!(median > 0) || !std::isfinite(median))
+            return set_error(FAD_ERR_INVALID, "%s: the median pairwise distance of %s is %g; it must be > 0 -- are all %srows identical?", who,
+                             pooled ? "the pooled rows" : "the baseline", median, pooled ? "" : "baseline ");
+    }
+    for (int b = 0; b < n_bw; ++b) {
+        sigma[b] = relative ? bandwidths[b] * median : bandwidths[b];
+        if (sigma_constant(sigma[b], cx.kernel, &c[b]) != SIGMA_OK)
+            return set_error(FAD_ERR_INVALID, "%s: bandwidth %d (%g) is outside the float32 range of the kernel", who, b, sigma[b]);
+    }
+    return FAD_OK;
+}
+
 // The three sum passes for a group of g <= NB bandwidths (c[0 .. g), padded with c[g - 1]; the padded sums are dropped):
 // sums[3 * b + q] = pass q's sum under c[b], read back.  Slots: pass q takes NB * G_q of them, G_q its launches' grids together,
 // bandwidth b's at [NB * (G_0 + .. + G_{q-1}) + b * G_q, + G_q) -- within that range in fad_kad_k's order, launch after launch.  A
 // launch's epilogue weighs NB single ones (kad_tiles.h), so a launch of 8 bandwidths is no longer than one of fad_kad_k.
 template <int NB>
-static int sweep_passes(const PassArgs (&passes)[3], const float* c, int g, int dtype, int kernel, int device, hipStream_t st,
-                        KadWorkspace& ws, double* sums) {
+static int sweep_passes(const Ctx& cx, const PassArgs (&passes)[3], const float* c, int g, double* sums) {
+    KadWorkspace& ws = *cx.ws;
+    const hipStream_t st = cx.st;
+    const int dtype = cx.dtype;
     std::vector<kad::Launch> launches[3];
     int64_t G[3], off[3 * NB + 1];
     int64_t base = 0;
@@ -2094,7 +2225,7 @@ static int sweep_passes(const PassArgs (&passes)[3], const float* c, int g, int 
         const PassArgs& p = passes[q];
         const int64_t total = p.tri ? kad::tri_tiles(p.tiles_j) : kad::blocks(p.n_a) * p.tiles_j;
         const int64_t per = kad::tiles_per_launch_for(p.pitch / (int64_t)dtype_size(dtype), dtype == FAD_F32, kad::kSumEpilogue * NB);
-        launches[q] = kad::launches(total, per, grid_cap(device));
+        launches[q] = kad::launches(total, per, grid_cap(cx.device));
         G[q] = 0;
         for (const kad::Launch& l : launches[q]) G[q] += l.grid;
         for (int b = 0; b < NB; ++b) off[q * NB + b] = base + b * G[q];
@@ -2116,7 +2247,7 @@ static int sweep_passes(const PassArgs (&passes)[3], const float* c, int g, int 
         a.p.slots = static_cast<double*>(ws.slots.p) + off[q * NB];
         for (const kad::Launch& l : launches[q]) {
             a.p.u0 = l.u0; a.p.cnt = l.cnt;
-            FAD_TRY(with_dtype_kernel(dtype, kernel, [&](auto dt, auto kf) {
+            FAD_TRY(with_dtype_kernel(dtype, cx.kernel, [&](auto dt, auto kf) {
                 kad_sweep_kernel<dt, kf, NB><<<(unsigned)l.grid, kThreads, lds_sweep<NB>(), st>>>(a);
             }));
             a.p.slots += l.grid;
@@ -2132,13 +2263,38 @@ static int sweep_passes(const PassArgs (&passes)[3], const float* c, int g, int 
     return FAD_OK;
 }
 
-static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+// The three sum passes of KAD for the g <= kSweepGroup bandwidths c[0 .. g), read back: sums[3 * b + q] = pass q's sum under c[b].
+// XX and YY over their triangles, XY over the rectangle with the larger set as the row operand.  One bandwidth runs fad_kad's own
+// kernel, places and order (so fad_kad_sweep at a single bandwidth is fad_kad_k); 2 .. 4 and 5 .. 8 the sweep kernels of 4 and 8.
+static int kad_three_passes(const Ctx& cx, const Packed& px, const Packed& py, const float* c, int g, double* sums) {
+    const bool x_rows = px.n != py.n ? px.n > py.n : px.norm_sum >= py.norm_sum;
+    const PassArgs passes[3] = {pass_args(px, px, true, c[0]), pass_args(py, py, true, c[0]),
+                                pass_args(x_rows ? px : py, x_rows ? py : px, false, c[0])};
+    if (g > 4) return sweep_passes<8>(cx, passes, c, g, sums);
+    if (g > 1) return sweep_passes<4>(cx, passes, c, g, sums);
+    double* sums_d = static_cast<double*>(cx.ws->small.p) + 16;
+    FAD_TRY(kad_sum_passes(cx, passes, sums_d));
+    FAD_HIP_TRY(hipMemcpyAsync(sums, sums_d, 3 * sizeof(double), hipMemcpyDeviceToHost, cx.st));
+    FAD_HIP_TRY(hipStreamSynchronize(cx.st));
+    return FAD_OK;
+}
+
+// The means and the estimate from the kernel sums over ordered pairs: sxx over the n (n - 1) pairs of x, syy likewise, sxy over n m
+static void fill_result(fad_kad_result_t* r, double sxx, double syy, double sxy, int64_t n, int64_t m, double sigma) {
+    r->kxx_mean = sxx / ((double)n * (double)(n - 1));
+    r->kyy_mean = syy / ((double)m * (double)(m - 1));
+    r->kxy_mean = sxy / ((double)n * (double)m);
+    r->mmd2 = r->kxx_mean + r->kyy_mean - 2.0 * r->kxy_mean;
+    r->bandwidth = sigma;
+    r->n = n;
+    r->m = m;
+}
 
 // A PRDC pass over the rectangle of `rows` x `cols` (fad_prdc): units of rr row blocks, NR row ranges, per-launch units
 struct PrdcPlan { int64_t TI, TJ, rr, NR, per_launch; };
-static PrdcPlan prdc_plan(const Packed& rows, const Packed& cols, int dtype, int64_t epilogue) {
+static PrdcPlan prdc_plan(const Ctx& cx, const Packed& rows, const Packed& cols, int64_t epilogue) {
     PrdcPlan q;
-    const int64_t per = kad::tiles_per_launch_for(rows.pitch / (int64_t)dtype_size(dtype), dtype == FAD_F32, epilogue);
+    const int64_t per = kad::tiles_per_launch_for(rows.pitch / (int64_t)dtype_size(cx.dtype), cx.dtype == FAD_F32, epilogue);
     q.TI = kad::blocks(rows.n); q.TJ = kad::blocks(cols.n);
     q.rr = kad::prdc_rows_per_unit(q.TI, q.TJ, per);
     q.NR = kad::cross_ranges(q.TI, q.rr);
@@ -2147,58 +2303,52 @@ static PrdcPlan prdc_plan(const Packed& rows, const Packed& cols, int dtype, int
 }
 
 // r2[j] (TJ * 128 entries, 0 on the padding rows) = the k-th smallest d^2 from row j of x to the other rows of x
-static int radius_pass(const Packed& x, int k, int dtype, int device, hipStream_t st, float* lists, float* r2) {
-    const PrdcPlan q = prdc_plan(x, x, dtype, kad::kTopkEpilogue);
+static int radius_pass(const Ctx& cx, const Packed& x, int k, float* lists, float* r2) {
+    const PrdcPlan q = prdc_plan(cx, x, x, kad::kTopkEpilogue);
     PrdcArgs p{};
     p.a = p.b = x.img; p.ha = p.hb = x.h; p.pitch = x.pitch; p.nchunks = x.nchunks; p.k = k;
     p.TI = q.TI; p.TJ = q.TJ; p.rr = q.rr; p.lists = lists; p.list_pitch = q.TJ * kTile;
-    for (const kad::Launch& l : kad::launches(q.NR * q.TJ, q.per_launch, grid_cap(device))) {
+    for (const kad::Launch& l : kad::launches(q.NR * q.TJ, q.per_launch, grid_cap(cx.device))) {
         p.u0 = l.u0; p.cnt = l.cnt;
-        FAD_TRY(with_dtype(dtype, [&](auto dt) { prdc_radius_kernel<dt><<<(unsigned)l.grid, kThreads, kLdsRadius, st>>>(p); }));
+        FAD_TRY(with_dtype(cx.dtype, [&](auto dt) { prdc_radius_kernel<dt><<<(unsigned)l.grid, kThreads, kLdsRadius, cx.st>>>(p); }));
     }
-    prdc_radius_reduce_kernel<<<(unsigned)cdiv(p.list_pitch, 256), 256, 0, st>>>(lists, q.NR, p.list_pitch, k, x.n, r2);
+    prdc_radius_reduce_kernel<<<(unsigned)cdiv(p.list_pitch, 256), 256, 0, cx.st>>>(lists, q.NR, p.list_pitch, k, x.n, r2);
     FAD_HIP_TRY(hipGetLastError());
     return FAD_OK;
 }
 
-// index / dist2 [m x k] (device) = the k nearest rows of x to every row of y, ascending in (d^2, i); `lists` holds NR * TJ * 128 * k keys
-static int nearest_pass(const Packed& x, const Packed& y, int k, int dtype, int device, hipStream_t st, uint64_t* lists, int32_t* index,
-                        float* dist2) {
-    const PrdcPlan q = prdc_plan(x, y, dtype, kad::kNearestEpilogue);
+// f(std::integral_constant<int, KB>{}) for the list length the nearest kernels are instantiated at that holds k
+template <typename F>
+static void with_kb(int k, F&& f) {
+    if (k == 1) f(std::integral_constant<int, 1>{});
+    else if (k <= 4) f(std::integral_constant<int, 4>{});
+    else if (k <= 8) f(std::integral_constant<int, 8>{});
+    else f(std::integral_constant<int, kMaxK>{});
+}
+
+// index / dist2 [y.n x k] (device) = the k nearest rows of x to every row of y, ascending in (d^2, i); `lists` holds NR * TJ * 128 * k
+// keys.  self: y is x (fad_nn_test's pooled rows) and the k nearest OTHER rows are wanted -- the same pass with the self pair masked.
+static int nearest_pass(const Ctx& cx, const Packed& x, const Packed& y, bool self, int k, uint64_t* lists, int32_t* index, float* dist2) {
+    const PrdcPlan q = prdc_plan(cx, x, y, kad::kNearestEpilogue);
     PrdcArgs p{};
     p.a = x.img; p.ha = x.h; p.b = y.img; p.hb = y.h; p.pitch = x.pitch; p.nchunks = x.nchunks; p.k = k;
     p.TI = q.TI; p.TJ = q.TJ; p.rr = q.rr; p.list_pitch = q.TJ * kTile;
-    for (const kad::Launch& l : kad::launches(q.NR * q.TJ, q.per_launch, grid_cap(device))) {
+    for (const kad::Launch& l : kad::launches(q.NR * q.TJ, q.per_launch, grid_cap(cx.device))) {
         p.u0 = l.u0; p.cnt = l.cnt;
-        FAD_TRY(with_dtype(dtype, [&](auto dt) {
-            if (k == 1) nearest_cross_kernel<dt, 1><<<(unsigned)l.grid, kThreads, lds_nearest<1>(), st>>>(p, lists);
-            else if (k <= 4) nearest_cross_kernel<dt, 4><<<(unsigned)l.grid, kThreads, lds_nearest<4>(), st>>>(p, lists);
-            else if (k <= 8) nearest_cross_kernel<dt, 8><<<(unsigned)l.grid, kThreads, lds_nearest<8>(), st>>>(p, lists);
-            else nearest_cross_kernel<dt, kMaxK><<<(unsigned)l.grid, kThreads, lds_nearest<kMaxK>(), st>>>(p, lists);
-        }));
+        auto launch = [&](auto self_tag) {
+            return with_dtype(cx.dtype, [&](auto dt) {
+                with_kb(k, [&](auto kb) {
+                    constexpr int DT = decltype(dt)::value, KB = decltype(kb)::value;
+                    if constexpr (decltype(self_tag)::value)
+                        nearest_self_kernel<DT, KB><<<(unsigned)l.grid, kThreads, lds_nearest<KB>(), cx.st>>>(p, lists);
+                    else
+                        nearest_cross_kernel<DT, KB><<<(unsigned)l.grid, kThreads, lds_nearest<KB>(), cx.st>>>(p, lists);
+                });
+            });
+        };
+        FAD_TRY(self ? launch(std::true_type{}) : launch(std::false_type{}));
     }
-    nearest_reduce_kernel<<<(unsigned)cdiv(y.n, 256), 256, 0, st>>>(lists, q.NR, p.list_pitch, k, y.n, index, dist2);
-    FAD_HIP_TRY(hipGetLastError());
-    return FAD_OK;
-}
-
-// index / dist2 [N x k] (device) = the k nearest OTHER rows of z to every row of z, ascending in (d^2, i): nearest_pass over Z x Z with
-// the self pair masked; `lists` holds NR * TZ * 128 * k keys
-static int nearest_self_pass(const Packed& z, int k, int dtype, int device, hipStream_t st, uint64_t* lists, int32_t* index, float* dist2) {
-    const PrdcPlan q = prdc_plan(z, z, dtype, kad::kNearestEpilogue);
-    PrdcArgs p{};
-    p.a = p.b = z.img; p.ha = p.hb = z.h; p.pitch = z.pitch; p.nchunks = z.nchunks; p.k = k;
-    p.TI = q.TI; p.TJ = q.TJ; p.rr = q.rr; p.list_pitch = q.TJ * kTile;
-    for (const kad::Launch& l : kad::launches(q.NR * q.TJ, q.per_launch, grid_cap(device))) {
-        p.u0 = l.u0; p.cnt = l.cnt;
-        FAD_TRY(with_dtype(dtype, [&](auto dt) {
-            if (k == 1) nearest_self_kernel<dt, 1><<<(unsigned)l.grid, kThreads, lds_nearest<1>(), st>>>(p, lists);
-            else if (k <= 4) nearest_self_kernel<dt, 4><<<(unsigned)l.grid, kThreads, lds_nearest<4>(), st>>>(p, lists);
-            else if (k <= 8) nearest_self_kernel<dt, 8><<<(unsigned)l.grid, kThreads, lds_nearest<8>(), st>>>(p, lists);
-            else nearest_self_kernel<dt, kMaxK><<<(unsigned)l.grid, kThreads, lds_nearest<kMaxK>(), st>>>(p, lists);
-        }));
-    }
-    nearest_reduce_kernel<<<(unsigned)cdiv(z.n, 256), 256, 0, st>>>(lists, q.NR, p.list_pitch, k, z.n, index, dist2);
+    nearest_reduce_kernel<<<(unsigned)cdiv(y.n, 256), 256, 0, cx.st>>>(lists, q.NR, p.list_pitch, k, y.n, index, dist2);
     FAD_HIP_TRY(hipGetLastError());
     return FAD_OK;
 }
@@ -2238,47 +2388,26 @@ static int perm_check_labels(int64_t n, int64_t m, const uint32_t* labels, int64
 
 // Z's image and h, the labellings (the observed one first) and their row and column words, all on the device
 struct PermPrep {
-    char* zimg; float* zh;
-    int64_t N, TZ, z_pad, nwz, dp, pitch, NL, W;
+    Packed z;                                                                          // the pooled rows, N of them
+    int64_t n, m, N, TZ, z_pad, nwz, dp, NL, W;
     uint32_t* lab; uint32_t* rows_d; uint32_t* cols_d;
-    double norm_sum;
 };
 
-static int perm_prepare(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype, int on_device,
-                        const uint32_t* labels, int64_t n_perm, int labels_on_device, hipStream_t st, KadWorkspace& ws, PermPrep* out) {
+static int perm_prepare(const Ctx& cx, const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int on_device,
+                        const uint32_t* labels, int64_t n_perm, int labels_on_device, PermPrep* out) {
+    KadWorkspace& ws = *cx.ws;
+    const hipStream_t st = cx.st;
     const int64_t N = n + m, nwl = cdiv(N, 32);
-    // Z = [X; Y] in one image, contiguously: kad_pack_kernel at row 0 (n rows, no padding) and at row n (Y, then Z's padding rows)
-    const size_t es = dtype_size(dtype);
-    const int64_t TZ = kad::blocks(N), z_pad = TZ * kTile, nwz = z_pad / 32, dp = depth_elems(d, dtype), pitch = dp * (int64_t)es;
+    const int64_t TZ = kad::blocks(N), z_pad = TZ * kTile, nwz = z_pad / 32;
     const int64_t NL = n_perm + 1, W = kad::perm_words(NL);                            // labellings with the observed one; their words
-    FAD_TRY(ws.img[0].reserve((size_t)(z_pad * pitch)));
-    FAD_TRY(ws.h[0].reserve((size_t)z_pad * sizeof(float)));
-    FAD_TRY(ws.small.reserve(4096 * sizeof(double) + 2 * kHistBins * sizeof(unsigned long long)));
-    if (!on_device) FAD_TRY(ws.raw[0].reserve((size_t)(N * d) * es));
-    char* zimg = static_cast<char*>(ws.img[0].p);
-    float* zh = static_cast<float*>(ws.h[0].p);
-    for (int s = 0; s < 2; ++s) {
-        const void* src = s ? y : x;
-        int64_t rn = s ? m : n, ld = s ? ldy : ldx;
-        const int64_t r0 = s ? n : 0, r_pad = s ? z_pad - n : n;
-        if (!on_device) {
-            char* raw = static_cast<char*>(ws.raw[0].p) + (size_t)(r0 * d) * es;
-            FAD_HIP_TRY(hipMemcpy2DAsync(raw, (size_t)d * es, src, (size_t)ld * es, (size_t)d * es, (size_t)rn, hipMemcpyHostToDevice, st));
-            src = raw;
-            ld = d;
-        }
-        const dim3 grid((unsigned)cdiv(r_pad, 4));
-        char* img = zimg + r0 * pitch;
-        switch (dtype) {
-            case FAD_F16: kad_pack_kernel<_Float16><<<grid, 256, 0, st>>>(static_cast<const _Float16*>(src), rn, ld, d, reinterpret_cast<_Float16*>(img), dp, r_pad, zh + r0); break;
-            case FAD_BF16: kad_pack_kernel<__bf16><<<grid, 256, 0, st>>>(static_cast<const __bf16*>(src), rn, ld, d, reinterpret_cast<__bf16*>(img), dp, r_pad, zh + r0); break;
-            default: kad_pack_kernel<float><<<grid, 256, 0, st>>>(static_cast<const float*>(src), rn, ld, d, reinterpret_cast<float*>(img), dp, r_pad, zh + r0); break;
-        }
-        FAD_HIP_TRY(hipGetLastError());
-    }
+    // Z = [X; Y] in one image, contiguously: kad_pack_kernel at row 0 (n rows, no padding) and at row n (Y, then Z's padding rows)
+    const RowSet sets[2] = {{x, n, ldx, 0, n}, {y, m, ldy, n, z_pad - n}};
+    Packed z;
+    FAD_TRY(pack_sets(cx, sets, 2, d, on_device, z_pad, false, &z));
+    z.n = N;
     double* info_d = static_cast<double*>(ws.small.p) + 1024;                          // norm sum, non-finite rows, bad labellings
     unsigned long long* bad_d = reinterpret_cast<unsigned long long*>(info_d + 2);
-    kad_norm_info_kernel<<<1, 256, 0, st>>>(zh, N, info_d);
+    kad_norm_info_kernel<<<1, 256, 0, st>>>(z.h, N, info_d);
     FAD_HIP_TRY(hipGetLastError());
 
     // the labellings: the observed one (Z's first n rows), then the caller's, at a row pitch of nwz words (Z's padding rows are 0)
@@ -2314,7 +2443,172 @@ static int perm_prepare(const void* x, int64_t n, int64_t ldx, const void* y, in
     kad_perm_colbits_kernel<<<(unsigned)cdiv(W * cdiv(nwz, 2), 4), 256, 0, st>>>(lab, NL, nwz, W, cols_d);
     FAD_HIP_TRY(hipGetLastError());
 
-    *out = PermPrep{zimg, zh, N, TZ, z_pad, nwz, dp, pitch, NL, W, lab, rows_d, cols_d, info[0]};
+    z.norm_sum = info[0];
+    *out = PermPrep{z, n, m, N, TZ, z_pad, nwz, depth_elems(d, cx.dtype), NL, W, lab, rows_d, cols_d};
+    return FAD_OK;
+}
+
+// The Z x Z column pass of the row sums: kad_unc_cols_kernel's walk over one pooled image whose sets start at the row blocks `blk`
+// (kad_unc_tiles.h).  The plan adds its two tables to the entry's carve; once the carve is reserved, col_pass_args uploads them and
+// gives the pass's arguments but for c, u0 and cnt: column slots in ws.unc_slots (reserved by the entry), one tile wide per unit.
+struct ColPlan {
+    int64_t rr, U;
+    std::vector<kad::Unit> units;
+    std::vector<int64_t> seg_start;
+    Region<kad::Unit> units_r;
+    Region<int64_t> seg_r;
+};
+static ColPlan col_plan(const Ctx& cx, const std::vector<int64_t>& blk, int64_t dp, Carve* cv) {
+    ColPlan q;
+    q.rr = kad::unc_rows_per_unit(kad::unc_tiles(blk), kad::tiles_per_launch_for(dp, cx.dtype == FAD_F32, kad::kUncEpilogue));
+    kad::unc_units(blk, q.rr, &q.units, &q.seg_start);
+    q.U = (int64_t)q.units.size();
+    q.units_r = cv->add<kad::Unit>(q.U);
+    q.seg_r = cv->add<int64_t>((int64_t)q.seg_start.size());
+    return q;
+}
+static int col_pass_args(const Ctx& cx, const ColPlan& q, const Carve& cv, const Packed& z, ColArgs* p) {
+    FAD_HIP_TRY(hipMemcpyAsync(cv.ptr(q.units_r), q.units.data(), (size_t)q.U * sizeof(kad::Unit), hipMemcpyHostToDevice, cx.st));
+    FAD_HIP_TRY(hipMemcpyAsync(cv.ptr(q.seg_r), q.seg_start.data(), q.seg_start.size() * sizeof(int64_t), hipMemcpyHostToDevice, cx.st));
+    *p = ColArgs{};
+    p->a = p->b = z.img; p->ha = p->hb = z.h; p->pitch = z.pitch; p->nchunks = z.nchunks;
+    p->units = cv.ptr(q.units_r); p->slots = static_cast<double*>(cx.ws->unc_slots.p); p->slot_pitch = kTile;
+    return FAD_OK;
+}
+
+// The permutation test of the prepared rows under B bandwidths (sigma_b as c[b]): t [B][NL], labelling 0 the observed one, and the
+// observed kernel sums obs [B][3], both read back.  fad_kad_permutation_sweep's body, and with B = 1 fad_kad_permutation_test_k's:
+// one bandwidth is one run of kad_perm_kernel over perm_groups(W) word groups, the single test's groups, slots and launches
+// (tests/native_cpu/kad_perm_sweep_cover.cpp).  fixed_shift: the shift of every bandwidth, in place of its own T / (N (N - 1)).
+static int perm_run(const Ctx& cx, const PermPrep& pp, int B, const float* c, const float* fixed_shift, std::vector<double>* t, double* obs) {
+    KadWorkspace& ws = *cx.ws;
+    const hipStream_t st = cx.st;
+    const int dtype = cx.dtype, kernel = cx.kernel;
+    const int64_t N = pp.N, TZ = pp.TZ, z_pad = pp.z_pad, nwz = pp.nwz, dp = pp.dp, NL = pp.NL;
+    const bool f32 = dtype == FAD_F32;
+
+    // the r pass's units do not depend on B: a unit's slot is one workgroup's, so r_b has the single call's bits at any size
+    Carve cv;
+    const ColPlan cp = col_plan(cx, kad::unc_blocks(N, nullptr, 0), dp, &cv);
+    const int64_t rr = cp.rr, U = cp.U;
+
+    // the walks of the permutation pass; per bandwidth its word groups as kad_perm_stats_kernel reads them: walk i holds its bandwidths'
+    // slots one after the other, [nb][walk slots][32 nw]
+    const std::vector<kad::PermSweepWalk> walks = kad::perm_sweep_walks(B, NL);
+    std::vector<int64_t> wslots;
+    const std::vector<kad::PermSweepLaunch> pl = kad::perm_sweep_launches(TZ, walks, dp, f32, grid_cap(cx.device), &wslots);
+    int64_t ngmax = 1, nslot_doubles = 0;
+    for (const kad::PermSweepWalk& w : walks) ngmax = std::max(ngmax, w.wgs);
+    std::vector<PermGroup> groups((size_t)(B * ngmax));
+    std::vector<int> ngs((size_t)B, 0);
+    std::vector<int64_t> walk_off(walks.size());
+    for (size_t i = 0; i < walks.size(); ++i) {
+        const kad::PermSweepWalk& w = walks[i];
+        walk_off[i] = nslot_doubles;
+        const int64_t per_bw = wslots[i] * 32 * w.nw;
+        for (int b = 0; b < w.nb; ++b) {
+            groups[(size_t)((w.b0 + b) * ngmax + w.wg)] = PermGroup{w.w0, w.nw, nslot_doubles + b * per_bw, wslots[i]};
+            ngs[(size_t)(w.b0 + b)] = (int)w.wgs;
+        }
+        nslot_doubles += w.nb * per_bw;
+    }
+
+    // units | seg_start | r [B][z_pad] | T [B] | groups [B][ngmax] | t [B][NL] | observed sums [B][3] | permutation slots
+    const auto r_r = cv.add<double>(B * z_pad), tot_r = cv.add<double>(B);
+    const auto groups_r = cv.add<PermGroup>((int64_t)groups.size());
+    const auto t_r = cv.add<double>(B * NL), obs_r = cv.add<double>(3 * B), pslots_r = cv.add<double>(nslot_doubles);
+    FAD_TRY(cv.reserve(ws.perm));
+    const int rg = std::min(B, kad::kPermSweepNB);                                     // bandwidths per r pass at most
+    FAD_TRY(ws.unc_slots.reserve((size_t)(rg * U * kTile) * sizeof(double)));
+    int64_t* seg_d = cv.ptr(cp.seg_r);
+    double* r_d = cv.ptr(r_r);
+    double* tot_d = cv.ptr(tot_r);
+    PermGroup* groups_d = cv.ptr(groups_r);
+    double* t_d = cv.ptr(t_r);
+    double* obs_d = cv.ptr(obs_r);
+    double* pslots = cv.ptr(pslots_r);
+    ColArgs ca;
+    FAD_TRY(col_pass_args(cx, cp, cv, pp.z, &ca));
+    FAD_HIP_TRY(hipMemcpyAsync(groups_d, groups.data(), groups.size() * sizeof(PermGroup), hipMemcpyHostToDevice, st));
+
+    // r_b = K_b'1 and T_b = 1'r_b, up to kPermSweepNB bandwidths per walk over Z x Z; a launch of NB bandwidths weighs NB epilogues
+    for (int b0 = 0; b0 < B; b0 += kad::kPermSweepNB) {
+        const int nb = std::min(kad::kPermSweepNB, B - b0), knb = kad::perm_sweep_kernel_nb(nb);
+        const int64_t per = std::max<int64_t>(1, kad::tiles_per_launch_for(dp, f32, kad::kUncEpilogue * knb) / rr);
+        for (const kad::Launch& l : kad::launches(U, knb == 1 ? kad::unc_units_per_launch(rr, dp, f32) : per, grid_cap(cx.device))) {
+            ca.u0 = l.u0; ca.cnt = l.cnt; ca.c = c[b0];
+            auto sweep = [&](auto nbc) {
+                constexpr int NB = decltype(nbc)::value;
+                ColSweepArgs<NB> q;
+                q.p = ca; q.nb = nb; q.bstride = U * kTile;
+                for (int b = 0; b < NB; ++b) q.c[b] = c[b0 + std::min(b, nb - 1)];
+                return with_dtype_kernel(dtype, kernel, [&](auto dt, auto kf) {
+                    kad_unc_cols_sweep_kernel<dt, kf, NB><<<(unsigned)l.grid, kThreads, lds_unc_sweep<NB>(), st>>>(q);
+                });
+            };
+            if (knb == 1) {
+                FAD_TRY(with_dtype_kernel(dtype, kernel, [&](auto dt, auto kf) {
+                    kad_unc_cols_kernel<dt, kf><<<(unsigned)l.grid, kThreads, kLdsUnc, st>>>(ca);
+                }));
+            } else if (knb == 2) {
+                FAD_TRY(sweep(std::integral_constant<int, 2>{}));
+            } else {
+                FAD_TRY(sweep(std::integral_constant<int, 4>{}));
+            }
+        }
+        for (int b = 0; b < nb; ++b) {
+            kad_perm_rows_kernel<<<(unsigned)cdiv(z_pad, 256), 256, 0, st>>>(ca.slots + b * U * kTile, seg_d, N, z_pad, r_d + (b0 + b) * z_pad);
+            FAD_HIP_TRY(hipGetLastError());
+            kad_perm_total_kernel<<<1, 256, 0, st>>>(r_d + (b0 + b) * z_pad, N, tot_d + b0 + b);
+            FAD_HIP_TRY(hipGetLastError());
+        }
+    }
+    double T[FAD_KAD_PERM_MAX_BANDWIDTHS];
+    FAD_HIP_TRY(hipMemcpyAsync(T, tot_d, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
+    FAD_HIP_TRY(hipStreamSynchronize(st));
+    // the shift of bandwidth b: the mean off-diagonal kernel value of Z under sigma_b, unless the caller fixes it.  Any constant gives
+    // the same t; it sets how much of each kernel value f16 keeps.
+    float c0[FAD_KAD_PERM_MAX_BANDWIDTHS];
+    for (int b = 0; b < B; ++b) c0[b] = fixed_shift ? *fixed_shift : (float)(T[b] / ((double)N * (double)(N - 1)));
+
+    FAD_HIP_TRY(hipMemsetAsync(pslots, 0, (size_t)nslot_doubles * sizeof(double), st));
+    PermArgs pa{};
+    pa.z = pp.z.img; pa.h = pp.z.h; pa.pitch = pp.z.pitch; pa.nchunks = pp.z.nchunks; pa.TZ = TZ; pa.nwz = nwz; pa.z_pad = z_pad;
+    for (const kad::PermSweepLaunch& l : pl) {
+        const kad::PermSweepWalk& w = walks[(size_t)l.walk];
+        pa.nw = (int)w.nw; pa.u0 = l.u0; pa.cnt = l.cnt;
+        pa.rowbits = pp.rows_d + w.w0 * z_pad;
+        pa.colbits = pp.cols_d + w.w0 * z_pad;
+        pa.slots = pslots + walk_off[(size_t)l.walk];
+        pa.c = c[w.b0]; pa.c0 = c0[w.b0];
+        auto sweep = [&](auto nbc) {
+            constexpr int NB = decltype(nbc)::value;
+            PermSweepArgs<NB> q;
+            q.p = pa; q.nb = w.nb; q.bstride = wslots[(size_t)l.walk] * 32 * w.nw;
+            for (int b = 0; b < NB; ++b) { q.c[b] = c[w.b0 + std::min(b, w.nb - 1)]; q.c0[b] = c0[w.b0 + std::min(b, w.nb - 1)]; }
+            return with_dtype_kernel(dtype, kernel, [&](auto dt, auto kf) {
+                kad_perm_sweep_kernel<dt, kf, NB><<<(unsigned)l.grid, kThreads, kLdsPerm, st>>>(q);
+            });
+        };
+        if (w.kernel_nb == 1) {                // one bandwidth: fad_kad_permutation_test_k's own kernel and cut
+            FAD_TRY(with_dtype_kernel(dtype, kernel, [&](auto dt, auto kf) {
+                kad_perm_kernel<dt, kf><<<(unsigned)l.grid, kThreads, kLdsPerm, st>>>(pa);
+            }));
+        } else if (w.kernel_nb == 2) {
+            FAD_TRY(sweep(std::integral_constant<int, 2>{}));
+        } else {
+            FAD_TRY(sweep(std::integral_constant<int, 4>{}));
+        }
+    }
+    for (int b = 0; b < B; ++b) {
+        kad_perm_stats_kernel<<<(unsigned)NL, 256, 0, st>>>(pslots, groups_d + b * ngmax, ngs[(size_t)b], pp.lab, nwz, r_d + b * z_pad, tot_d + b,
+                                                            (double)c0[b], pp.n, pp.m, t_d + b * NL, obs_d + 3 * b);
+        FAD_HIP_TRY(hipGetLastError());
+    }
+    t->resize((size_t)(B * NL));
+    FAD_HIP_TRY(hipMemcpyAsync(t->data(), t_d, t->size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    FAD_HIP_TRY(hipMemcpyAsync(obs, obs_d, (size_t)(3 * B) * sizeof(double), hipMemcpyDeviceToHost, st));
+    FAD_HIP_TRY(hipStreamSynchronize(st));
     return FAD_OK;
 }
 
@@ -2334,15 +2628,18 @@ static int kid_params(int degree, double gamma, double coef0, int64_t d, const c
 
 // n_img images of s rows each (img_rows with the padding) of the rows of x, through `index` (device) or, index NULL, x's own rows:
 // slot's image and markers.  Host rows are staged whole, once, in ws.raw[slot] (*staged keeps the device copy for the next group).
-static int kid_pack(int slot, const void* x, int64_t n, int64_t ld, int64_t d, int dtype, int on_device, const int32_t* index, int64_t s,
-                    int64_t img_rows, int64_t n_img, hipStream_t st, KadWorkspace& ws, const void** staged, Packed* out) {
-    const size_t es = dtype_size(dtype);
-    const int64_t dp = depth_elems(d, dtype);
+static int kid_pack(const Ctx& cx, int slot, const void* x, int64_t n, int64_t ld, int64_t d, int on_device, const int32_t* index, int64_t s,
+                    int64_t img_rows, int64_t n_img, const void** staged, Packed* out) {
+    KadWorkspace& ws = *cx.ws;
+    const hipStream_t st = cx.st;
+    const size_t es = dtype_size(cx.dtype);
+    const int64_t dp = depth_elems(d, cx.dtype);
     if (!on_device) {
         if (!*staged) {
             FAD_TRY(ws.raw[slot].reserve((size_t)(n * d) * es));
-            FAD_HIP_TRY(hipMemcpy2DAsync(ws.raw[slot].p, (size_t)d * es, x, (size_t)ld * es, (size_t)d * es, (size_t)n, hipMemcpyHostToDevice, st));
-            *staged = ws.raw[slot].p;
+            *staged = x;
+            int64_t ld_staged = ld;
+            FAD_TRY(stage_rows(cx, slot, 0, on_device, staged, n, &ld_staged, d));
         }
         x = *staged;
         ld = d;
@@ -2352,7 +2649,7 @@ static int kid_pack(int slot, const void* x, int64_t n, int64_t ld, int64_t d, i
     FAD_TRY(ws.h[slot].reserve((size_t)rows * sizeof(float)));
     float* h = static_cast<float*>(ws.h[slot].p);
     const dim3 grid((unsigned)cdiv(rows, 4));
-    switch (dtype) {
+    switch (cx.dtype) {
         case FAD_F16: kid_pack_kernel<_Float16><<<grid, 256, 0, st>>>(static_cast<const _Float16*>(x), ld, d, index, s, img_rows, n_img, static_cast<_Float16*>(ws.img[slot].p), dp, h); break;
         case FAD_BF16: kid_pack_kernel<__bf16><<<grid, 256, 0, st>>>(static_cast<const __bf16*>(x), ld, d, index, s, img_rows, n_img, static_cast<__bf16*>(ws.img[slot].p), dp, h); break;
         default: kid_pack_kernel<float><<<grid, 256, 0, st>>>(static_cast<const float*>(x), ld, d, index, s, img_rows, n_img, static_cast<float*>(ws.img[slot].p), dp, h); break;
@@ -2380,14 +2677,11 @@ int fad_kad_median_distance(const void* x, int64_t n, int64_t ld, int64_t d, int
     begin_entry();
     if (!sigma) return set_error(FAD_ERR_INVALID, "fad_kad_median_distance: NULL output");
     FAD_TRY(check_rows(x, n, ld, d, dtype, "fad_kad_median_distance"));
-    FAD_TRY(check_device(device));
-    DeviceGuard g(device);
-    if (!g.ok) return set_error(FAD_ERR_HIP, "hipSetDevice(%d) failed", device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    KadWorkspace& ws = workspace(device);
+    Ctx cx;
+    FAD_TRY(cx.open(dtype, FAD_KAD_GAUSSIAN, device, stream));
     Packed px;
-    FAD_TRY(pack_set(0, x, n, ld, d, dtype, on_device, st, ws, &px));
-    return median_of_packed(px, dtype, device, st, ws, sigma);
+    FAD_TRY(pack_set(cx, 0, x, n, ld, d, on_device, &px));
+    return median_of_packed(cx, px, sigma);
 }
 
 int fad_kad(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype, int on_device,
@@ -2405,36 +2699,17 @@ int fad_kad_k(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, i
     FAD_TRY(check_rows(y, m, ldy, d, dtype, "fad_kad (y)"));
     if (std::isnan(bandwidth) || std::isinf(bandwidth))
         return set_error(FAD_ERR_INVALID, "fad_kad: bandwidth %g is not finite", bandwidth);
-    FAD_TRY(check_device(device));
-    DeviceGuard g(device);
-    if (!g.ok) return set_error(FAD_ERR_HIP, "hipSetDevice(%d) failed", device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    KadWorkspace& ws = workspace(device);
+    Ctx cx;
+    FAD_TRY(cx.open(dtype, kernel, device, stream));
 
     Packed px, py;
-    FAD_TRY(pack_set(0, x, n, ldx, d, dtype, on_device, st, ws, &px));
-    FAD_TRY(pack_set(1, y, m, ldy, d, dtype, on_device, st, ws, &py));
-    double sigma;
+    FAD_TRY(pack_set(cx, 0, x, n, ldx, d, on_device, &px));
+    FAD_TRY(pack_set(cx, 1, y, m, ldy, d, on_device, &py));
+    double sigma, sums[3];
     float c;
-    FAD_TRY(resolve_sigma(px, bandwidth, kernel, dtype, device, st, ws, "fad_kad", &sigma, &c));
-
-    // passes: XX and YY over their triangles, XY over the rectangle with the larger set as the row operand
-    const bool x_rows = n != m ? n > m : px.norm_sum >= py.norm_sum;
-    const PassArgs passes[3] = {pass_args(px, px, true, c), pass_args(py, py, true, c),
-                                pass_args(x_rows ? px : py, x_rows ? py : px, false, c)};
-    double* sums_d = static_cast<double*>(ws.small.p) + 16;
-    FAD_TRY(sum_passes(passes, dtype, kernel, device, st, ws, sums_d));
-    double sums[3];
-    FAD_HIP_TRY(hipMemcpyAsync(sums, sums_d, sizeof(sums), hipMemcpyDeviceToHost, st));
-    FAD_HIP_TRY(hipStreamSynchronize(st));
-
-    out->kxx_mean = 2.0 * sums[0] / ((double)n * (double)(n - 1));
-    out->kyy_mean = 2.0 * sums[1] / ((double)m * (double)(m - 1));
-    out->kxy_mean = sums[2] / ((double)n * (double)m);
-    out->mmd2 = out->kxx_mean + out->kyy_mean - 2.0 * out->kxy_mean;
-    out->bandwidth = sigma;
-    out->n = n;
-    out->m = m;
+    FAD_TRY(resolve_sigma(cx, px, bandwidth, "fad_kad", &sigma, &c));
+    FAD_TRY(kad_three_passes(cx, px, py, &c, 1, sums));
+    fill_result(out, 2.0 * sums[0], 2.0 * sums[1], sums[2], n, m, sigma);
     return FAD_OK;
 }
 
@@ -2450,63 +2725,20 @@ int fad_kad_sweep(const void* x, int64_t n, int64_t ldx, const void* y, int64_t 
     FAD_TRY(check_kernel(kernel, "fad_kad_sweep"));
     FAD_TRY(check_rows(x, n, ldx, d, dtype, "fad_kad_sweep (x)"));
     FAD_TRY(check_rows(y, m, ldy, d, dtype, "fad_kad_sweep (y)"));
-    for (int b = 0; b < n_bw; ++b)
-        if (!(bandwidths[b] > 0) || !std::isfinite(bandwidths[b]))
-            return set_error(FAD_ERR_INVALID, "fad_kad_sweep: %s %d is %g; every one must be finite and > 0 (the median is the factor 1)",
-                             relative ? "factor" : "bandwidth", b, bandwidths[b]);
-    FAD_TRY(check_device(device));
-    DeviceGuard g(device);
-    if (!g.ok) return set_error(FAD_ERR_HIP, "hipSetDevice(%d) failed", device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    KadWorkspace& ws = workspace(device);
+    FAD_TRY(check_bandwidths(bandwidths, n_bw, relative, "fad_kad_sweep", false));
+    Ctx cx;
+    FAD_TRY(cx.open(dtype, kernel, device, stream));
 
     Packed px, py;
-    FAD_TRY(pack_set(0, x, n, ldx, d, dtype, on_device, st, ws, &px));
-    FAD_TRY(pack_set(1, y, m, ldy, d, dtype, on_device, st, ws, &py));
-    double median = 1.0;
-    if (relative) {
-        FAD_TRY(median_of_packed(px, dtype, device, st, ws, &median));
-        if (!(median > 0) || !std::isfinite(median))
-            return set_error(FAD_ERR_INVALID, "fad_kad_sweep: the median pairwise distance of the baseline is %g; it must be > 0"
-                             " -- are all baseline rows identical?", median);
-    }
-    double sigma[FAD_KAD_MAX_BANDWIDTHS];
+    FAD_TRY(pack_set(cx, 0, x, n, ldx, d, on_device, &px));
+    FAD_TRY(pack_set(cx, 1, y, m, ldy, d, on_device, &py));
+    double sigma[FAD_KAD_MAX_BANDWIDTHS], sums[3 * FAD_KAD_MAX_BANDWIDTHS];
     float c[FAD_KAD_MAX_BANDWIDTHS];
-    for (int b = 0; b < n_bw; ++b) {
-        sigma[b] = relative ? bandwidths[b] * median : bandwidths[b];
-        if (sigma_constant(sigma[b], kernel, &c[b]) != SIGMA_OK)
-            return set_error(FAD_ERR_INVALID, "fad_kad_sweep: bandwidth %d (%g) is outside the float32 range of the kernel", b, sigma[b]);
-    }
-
-    // passes as fad_kad_k's: XX and YY over their triangles, XY over the rectangle with the larger set as the row operand
-    const bool x_rows = n != m ? n > m : px.norm_sum >= py.norm_sum;
-    double sums[3 * FAD_KAD_MAX_BANDWIDTHS];
-    for (int b0 = 0; b0 < n_bw; b0 += kSweepGroup) {
-        const int gb = std::min(kSweepGroup, n_bw - b0);
-        const PassArgs passes[3] = {pass_args(px, px, true, c[b0]), pass_args(py, py, true, c[b0]),
-                                    pass_args(x_rows ? px : py, x_rows ? py : px, false, c[b0])};
-        if (gb == 1) {                         // fad_kad_k's own kernel, places and order
-            double* sums_d = static_cast<double*>(ws.small.p) + 16;
-            FAD_TRY(sum_passes(passes, dtype, kernel, device, st, ws, sums_d));
-            FAD_HIP_TRY(hipMemcpyAsync(sums + 3 * b0, sums_d, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
-            FAD_HIP_TRY(hipStreamSynchronize(st));
-        } else if (gb <= 4) {
-            FAD_TRY(sweep_passes<4>(passes, c + b0, gb, dtype, kernel, device, st, ws, sums + 3 * b0));
-        } else {
-            FAD_TRY(sweep_passes<8>(passes, c + b0, gb, dtype, kernel, device, st, ws, sums + 3 * b0));
-        }
-    }
-
-    for (int b = 0; b < n_bw; ++b) {           // only now: a refusal above leaves `out` as it was
-        fad_kad_result_t& r = out[b];
-        r.kxx_mean = 2.0 * sums[3 * b] / ((double)n * (double)(n - 1));
-        r.kyy_mean = 2.0 * sums[3 * b + 1] / ((double)m * (double)(m - 1));
-        r.kxy_mean = sums[3 * b + 2] / ((double)n * (double)m);
-        r.mmd2 = r.kxx_mean + r.kyy_mean - 2.0 * r.kxy_mean;
-        r.bandwidth = sigma[b];
-        r.n = n;
-        r.m = m;
-    }
+    FAD_TRY(resolve_sigmas(cx, px, bandwidths, n_bw, relative, "fad_kad_sweep", false, sigma, c));
+    for (int b0 = 0; b0 < n_bw; b0 += kSweepGroup)
+        FAD_TRY(kad_three_passes(cx, px, py, c + b0, std::min(kSweepGroup, n_bw - b0), sums + 3 * b0));
+    for (int b = 0; b < n_bw; ++b)             // only now: a refusal above leaves `out` as it was
+        fill_result(&out[b], 2.0 * sums[3 * b], 2.0 * sums[3 * b + 1], sums[3 * b + 2], n, m, sigma[b]);
     return FAD_OK;
 }
 
@@ -2540,26 +2772,25 @@ int fad_kad_individual_k(const void* x, int64_t n, int64_t ldx, const void* rows
         if (offsets[s + 1] < offsets[s]) return set_error(FAD_ERR_INVALID, "fad_kad_individual: offsets decrease at song %lld", (long long)s);
     if (std::isnan(bandwidth) || std::isinf(bandwidth))
         return set_error(FAD_ERR_INVALID, "fad_kad_individual: bandwidth %g is not finite", bandwidth);
-    FAD_TRY(check_device(device));
-    DeviceGuard g(device);
-    if (!g.ok) return set_error(FAD_ERR_HIP, "hipSetDevice(%d) failed", device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    KadWorkspace& ws = workspace(device);
+    Ctx cx;
+    FAD_TRY(cx.open(dtype, kernel, device, stream));
+    KadWorkspace& ws = *cx.ws;
+    const hipStream_t st = cx.st;
 
     // the baseline: sigma and Kxx exactly as fad_kad finds them (the same launches, slots and fixed-order sum)
     Packed px;
-    FAD_TRY(pack_set(0, x, n, ldx, d, dtype, on_device, st, ws, &px));
+    FAD_TRY(pack_set(cx, 0, x, n, ldx, d, on_device, &px));
     double sigma;
     float c;
-    FAD_TRY(resolve_sigma(px, bandwidth, kernel, dtype, device, st, ws, "fad_kad_individual", &sigma, &c));
+    FAD_TRY(resolve_sigma(cx, px, bandwidth, "fad_kad_individual", &sigma, &c));
     const PassArgs xx[1] = {pass_args(px, px, true, c)};
     double* sxx_d = static_cast<double*>(ws.small.p) + 16;
-    FAD_TRY(sum_passes(xx, dtype, kernel, device, st, ws, sxx_d));
+    FAD_TRY(kad_sum_passes(cx, xx, sxx_d));
 
     // the songs: cross pass (X x Y) and band pass (pairs inside each song), per-column slots, one reduction per song
     if (n_rows > 0 && n_songs > 0) {
         Packed py;
-        FAD_TRY(pack_image(1, rows, n_rows, ldy, d, dtype, on_device, st, ws, &py));
+        FAD_TRY(pack_image(cx, 1, rows, n_rows, ldy, d, on_device, &py));
         const bool f32 = dtype == FAD_F32;
         const int64_t depth = px.pitch / (int64_t)dtype_size(dtype), TI = kad::blocks(n), TJ = kad::blocks(n_rows), m_pad = TJ * kTile;
         const int64_t rr = kad::cross_rows_per_unit(TI, TJ, kad::tiles_per_launch(depth, f32)), NR = kad::cross_ranges(TI, rr);
@@ -2569,26 +2800,22 @@ int fad_kad_individual_k(const void* x, int64_t n, int64_t ldx, const void* rows
         const int64_t U = (int64_t)bunits.size();
 
         // song tables and outputs, one buffer: offsets | band_start | band units | row_end | kyy | kxy | status
-        size_t at[8];
-        at[0] = 0;
-        at[1] = at[0] + align256((size_t)(n_songs + 1) * sizeof(int64_t));
-        at[2] = at[1] + align256((size_t)(TJ + 1) * sizeof(int64_t));
-        at[3] = at[2] + align256((size_t)U * sizeof(kad::Unit));
-        at[4] = at[3] + align256((size_t)m_pad * sizeof(int));
-        at[5] = at[4] + align256((size_t)n_songs * sizeof(double));
-        at[6] = at[5] + align256((size_t)n_songs * sizeof(double));
-        at[7] = at[6] + align256((size_t)n_songs * sizeof(int));
-        FAD_TRY(ws.songs.reserve(at[7]));
+        Carve cv;
+        const auto off_r = cv.add<int64_t>(n_songs + 1), bstart_r = cv.add<int64_t>(TJ + 1);
+        const auto bunits_r = cv.add<kad::Unit>(U);
+        const auto row_end_r = cv.add<int>(m_pad);
+        const auto kyy_r = cv.add<double>(n_songs), kxy_r = cv.add<double>(n_songs);
+        const auto status_r = cv.add<int>(n_songs);
+        FAD_TRY(cv.reserve(ws.songs));
         FAD_TRY(ws.cross.reserve((size_t)(NR * m_pad) * sizeof(double)));
         FAD_TRY(ws.band.reserve((size_t)(U * kTile) * sizeof(double)));
-        char* sb = static_cast<char*>(ws.songs.p);
-        int64_t* off_d = reinterpret_cast<int64_t*>(sb + at[0]);
-        int64_t* bstart_d = reinterpret_cast<int64_t*>(sb + at[1]);
-        kad::Unit* bunits_d = reinterpret_cast<kad::Unit*>(sb + at[2]);
-        int* row_end_d = reinterpret_cast<int*>(sb + at[3]);
-        double* kyy_d = reinterpret_cast<double*>(sb + at[4]);
-        double* kxy_d = reinterpret_cast<double*>(sb + at[5]);
-        int* status_d = reinterpret_cast<int*>(sb + at[6]);
+        int64_t* off_d = cv.ptr(off_r);
+        int64_t* bstart_d = cv.ptr(bstart_r);
+        kad::Unit* bunits_d = cv.ptr(bunits_r);
+        int* row_end_d = cv.ptr(row_end_r);
+        double* kyy_d = cv.ptr(kyy_r);
+        double* kxy_d = cv.ptr(kxy_r);
+        int* status_d = cv.ptr(status_r);
         FAD_HIP_TRY(hipMemcpyAsync(off_d, offsets, (size_t)(n_songs + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
         FAD_HIP_TRY(hipMemcpyAsync(bstart_d, bstart.data(), bstart.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
         FAD_HIP_TRY(hipMemcpyAsync(bunits_d, bunits.data(), bunits.size() * sizeof(kad::Unit), hipMemcpyHostToDevice, st));
@@ -2661,11 +2888,10 @@ int fad_kad_uncertainty_k(const void* x, int64_t n, int64_t ldx, const void* con
     for (int s = 0; s < n_sets; ++s) FAD_TRY(check_rows(ys[s], ms[s], ldys[s], d, dtype, "fad_kad_uncertainty (a set)"));
     if (std::isnan(bandwidth) || std::isinf(bandwidth))
         return set_error(FAD_ERR_INVALID, "fad_kad_uncertainty: bandwidth %g is not finite", bandwidth);
-    FAD_TRY(check_device(device));
-    DeviceGuard g(device);
-    if (!g.ok) return set_error(FAD_ERR_HIP, "hipSetDevice(%d) failed", device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    KadWorkspace& ws = workspace(device);
+    Ctx cx;
+    FAD_TRY(cx.open(dtype, kernel, device, stream));
+    KadWorkspace& ws = *cx.ws;
+    const hipStream_t st = cx.st;
     const int S = n_sets;
 
     // Z: X, then every set from a tile boundary, in one image (kad_unc_tiles.h)
@@ -2677,38 +2903,12 @@ int fad_kad_uncertainty_k(const void* x, int64_t n, int64_t ldx, const void* con
     for (int s = 0; s < S; ++s) { q.blk[s] = blk[(size_t)s]; q.m[s] = ms[s]; q.yoff[s + 1] = q.yoff[s] + ms[s]; }
     q.blk[S] = blk[(size_t)S];
     const int64_t TZ = q.blk[S], z_pad = TZ * kTile, M = q.yoff[S];
-    const size_t es = dtype_size(dtype);
-    const int64_t dp = depth_elems(d, dtype), pitch = dp * (int64_t)es;
-    FAD_TRY(ws.img[0].reserve((size_t)(z_pad * pitch)));
-    FAD_TRY(ws.h[0].reserve((size_t)z_pad * sizeof(float)));
-    FAD_TRY(ws.small.reserve(4096 * sizeof(double) + 2 * kHistBins * sizeof(unsigned long long)));
-    if (!on_device) FAD_TRY(ws.raw[0].reserve((size_t)((n + M) * d) * es));
-    char* zimg = static_cast<char*>(ws.img[0].p);
-    float* zh = static_cast<float*>(ws.h[0].p);
+    std::vector<RowSet> sets;
+    sets.push_back(RowSet{x, n, ldx, 0, kad::blocks(n) * kTile});
+    for (int s = 0; s < S; ++s) sets.push_back(RowSet{ys[s], ms[s], ldys[s], q.blk[s] * kTile, kad::blocks(ms[s]) * kTile});
+    Packed px;
+    FAD_TRY(pack_sets(cx, sets.data(), S + 1, d, on_device, z_pad, true, &px));
     double* info_d = static_cast<double*>(ws.small.p) + 1024;                          // [2 (S + 1)]: norm sum, non-finite rows
-    int64_t staged = 0;
-    for (int s = -1; s < S; ++s) {                                                     // s = -1: X
-        const void* src = s < 0 ? x : ys[s];
-        int64_t rn = s < 0 ? n : ms[s], ld = s < 0 ? ldx : ldys[s];
-        const int64_t r0 = (s < 0 ? 0 : q.blk[s]) * kTile, r_pad = kad::blocks(rn) * kTile;
-        if (!on_device) {
-            char* raw = static_cast<char*>(ws.raw[0].p) + (size_t)(staged * d) * es;
-            FAD_HIP_TRY(hipMemcpy2DAsync(raw, (size_t)d * es, src, (size_t)ld * es, (size_t)d * es, (size_t)rn, hipMemcpyHostToDevice, st));
-            src = raw;
-            ld = d;
-            staged += rn;
-        }
-        const dim3 grid((unsigned)cdiv(r_pad, 4));
-        char* img = zimg + r0 * pitch;
-        switch (dtype) {
-            case FAD_F16: kad_pack_kernel<_Float16><<<grid, 256, 0, st>>>(static_cast<const _Float16*>(src), rn, ld, d, reinterpret_cast<_Float16*>(img), dp, r_pad, zh + r0); break;
-            case FAD_BF16: kad_pack_kernel<__bf16><<<grid, 256, 0, st>>>(static_cast<const __bf16*>(src), rn, ld, d, reinterpret_cast<__bf16*>(img), dp, r_pad, zh + r0); break;
-            default: kad_pack_kernel<float><<<grid, 256, 0, st>>>(static_cast<const float*>(src), rn, ld, d, reinterpret_cast<float*>(img), dp, r_pad, zh + r0); break;
-        }
-        FAD_HIP_TRY(hipGetLastError());
-        kad_norm_info_kernel<<<1, 256, 0, st>>>(zh + r0, rn, info_d + 2 * (s + 1));
-        FAD_HIP_TRY(hipGetLastError());
-    }
     std::vector<double> info((size_t)(2 * (S + 1)));
     FAD_HIP_TRY(hipMemcpyAsync(info.data(), info_d, info.size() * sizeof(double), hipMemcpyDeviceToHost, st));
     FAD_HIP_TRY(hipStreamSynchronize(st));
@@ -2717,60 +2917,44 @@ int fad_kad_uncertainty_k(const void* x, int64_t n, int64_t ldx, const void* con
             return set_error(FAD_ERR_NOT_FINITE, "KAD: %lld of %lld rows of %s have a NaN/Inf norm", (long long)info[(size_t)(2 * (s + 1) + 1)],
                              (long long)(s < 0 ? n : ms[s]), s < 0 ? "the baseline" : "an evaluation set");
 
-    const Packed px{zimg, zh, n, pitch, (int)(pitch / kChunk), info[0]};
+    px.n = n;                                  // the baseline is the image's first rows
+    px.norm_sum = info[0];
     double sigma;
     float c;
-    FAD_TRY(resolve_sigma(px, bandwidth, kernel, dtype, device, st, ws, "fad_kad_uncertainty", &sigma, &c));
+    FAD_TRY(resolve_sigma(cx, px, bandwidth, "fad_kad_uncertainty", &sigma, &c));
 
     // the pass: units, slots and per-row tables
     const bool f32 = dtype == FAD_F32;
-    const int64_t rr = kad::unc_rows_per_unit(kad::unc_tiles(blk), kad::tiles_per_launch_for(dp, f32, kad::kUncEpilogue));
-    std::vector<kad::Unit> units;
-    std::vector<int64_t> seg_start;
-    kad::unc_units(blk, rr, &units, &seg_start);
-    const int64_t U = (int64_t)units.size();
+    const int64_t dp = depth_elems(d, dtype);
+    Carve cv;
+    const ColPlan cp = col_plan(cx, blk, dp, &cv);
     const int64_t W = std::min<int64_t>(256, cdiv(n, kUncCovRows)), P = (int64_t)S * S;
 
     // units | seg_start | a [S n] | b [M] | rxx [n] | ryy [M] | ryx [M] | stats [5 S + 1] | cov partials [W P] | cov sums [P]
-    size_t at[11];
-    at[0] = 0;
-    at[1] = at[0] + align256((size_t)U * sizeof(kad::Unit));
-    at[2] = at[1] + align256(seg_start.size() * sizeof(int64_t));
-    at[3] = at[2] + align256((size_t)(S * n) * sizeof(double));
-    at[4] = at[3] + align256((size_t)M * sizeof(double));
-    at[5] = at[4] + align256((size_t)n * sizeof(double));
-    at[6] = at[5] + align256((size_t)M * sizeof(double));
-    at[7] = at[6] + align256((size_t)M * sizeof(double));
-    at[8] = at[7] + align256((size_t)(5 * S + 1) * sizeof(double));
-    at[9] = at[8] + align256((size_t)(W * P) * sizeof(double));
-    at[10] = at[9] + align256((size_t)P * sizeof(double));
-    FAD_TRY(ws.unc.reserve(at[10]));
-    FAD_TRY(ws.unc_slots.reserve((size_t)(U * kTile) * sizeof(double)));
-    char* ub = static_cast<char*>(ws.unc.p);
-    kad::Unit* units_d = reinterpret_cast<kad::Unit*>(ub + at[0]);
-    int64_t* seg_d = reinterpret_cast<int64_t*>(ub + at[1]);
-    double* a_d = reinterpret_cast<double*>(ub + at[2]);
-    double* b_d = reinterpret_cast<double*>(ub + at[3]);
-    double* rxx_d = reinterpret_cast<double*>(ub + at[4]);
-    double* ryy_d = reinterpret_cast<double*>(ub + at[5]);
-    double* ryx_d = reinterpret_cast<double*>(ub + at[6]);
-    double* stats_d = reinterpret_cast<double*>(ub + at[7]);
-    double* part_d = reinterpret_cast<double*>(ub + at[8]);
-    double* covs_d = reinterpret_cast<double*>(ub + at[9]);
-    double* slots = static_cast<double*>(ws.unc_slots.p);
-    FAD_HIP_TRY(hipMemcpyAsync(units_d, units.data(), (size_t)U * sizeof(kad::Unit), hipMemcpyHostToDevice, st));
-    FAD_HIP_TRY(hipMemcpyAsync(seg_d, seg_start.data(), seg_start.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    const auto a_r = cv.add<double>(S * n), b_r = cv.add<double>(M), rxx_r = cv.add<double>(n), ryy_r = cv.add<double>(M);
+    const auto ryx_r = cv.add<double>(M), stats_r = cv.add<double>(5 * S + 1), part_r = cv.add<double>(W * P), covs_r = cv.add<double>(P);
+    FAD_TRY(cv.reserve(ws.unc));
+    FAD_TRY(ws.unc_slots.reserve((size_t)(cp.U * kTile) * sizeof(double)));
+    int64_t* seg_d = cv.ptr(cp.seg_r);
+    double* a_d = cv.ptr(a_r);
+    double* b_d = cv.ptr(b_r);
+    double* rxx_d = cv.ptr(rxx_r);
+    double* ryy_d = cv.ptr(ryy_r);
+    double* ryx_d = cv.ptr(ryx_r);
+    double* stats_d = cv.ptr(stats_r);
+    double* part_d = cv.ptr(part_r);
+    double* covs_d = cv.ptr(covs_r);
 
-    ColArgs p{};
-    p.a = p.b = zimg; p.ha = p.hb = zh; p.pitch = pitch; p.nchunks = px.nchunks; p.c = c;
-    p.units = units_d; p.slots = slots; p.slot_pitch = kTile;
-    for (const kad::Launch& l : kad::launches(U, kad::unc_units_per_launch(rr, dp, f32), grid_cap(device))) {
+    ColArgs p;
+    FAD_TRY(col_pass_args(cx, cp, cv, px, &p));
+    p.c = c;
+    for (const kad::Launch& l : kad::launches(cp.U, kad::unc_units_per_launch(cp.rr, dp, f32), grid_cap(device))) {
         p.u0 = l.u0; p.cnt = l.cnt;
         FAD_TRY(with_dtype_kernel(dtype, kernel, [&](auto dt, auto kf) {
             kad_unc_cols_kernel<dt, kf><<<(unsigned)l.grid, kThreads, kLdsUnc, st>>>(p);
         }));
     }
-    kad_unc_rows_kernel<<<(unsigned)cdiv(z_pad, 256), 256, 0, st>>>(slots, seg_d, q, a_d, b_d, rxx_d, ryy_d, ryx_d);
+    kad_unc_rows_kernel<<<(unsigned)cdiv(z_pad, 256), 256, 0, st>>>(p.slots, seg_d, q, a_d, b_d, rxx_d, ryy_d, ryx_d);
     FAD_HIP_TRY(hipGetLastError());
     kad_unc_sets_kernel<<<(unsigned)(S + 1), 256, 0, st>>>(a_d, b_d, rxx_d, ryy_d, ryx_d, q, stats_d);
     FAD_HIP_TRY(hipGetLastError());
@@ -2786,18 +2970,13 @@ int fad_kad_uncertainty_k(const void* x, int64_t n, int64_t ldx, const void* con
     if (proj_y) FAD_HIP_TRY(hipMemcpyAsync(proj_y, b_d, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, st));
     FAD_HIP_TRY(hipStreamSynchronize(st));
 
-    const double nd = (double)n, kxx = stats[(size_t)(5 * S)] / (nd * (nd - 1.0)), cx = 4.0 / (nd * (nd - 1.0));
+    const double nd = (double)n, cov_x = 4.0 / (nd * (nd - 1.0));
     for (int s = 0; s < S; ++s) {
         const double* t = stats.data() + 5 * s;
         const double md = (double)ms[s];
-        out[s].mmd2 = t[0] + t[1];
-        out[s].kxx_mean = kxx;
-        out[s].kyy_mean = t[3] / (md * (md - 1.0));
-        out[s].kxy_mean = t[4] / (nd * md);
-        out[s].bandwidth = sigma;
-        out[s].n = n;
-        out[s].m = ms[s];
-        for (int u = 0; u < S; ++u) cov[s * S + u] = cx * covs[(size_t)(s * S + u)];
+        fill_result(&out[s], stats[(size_t)(5 * S)], t[3], t[4], n, ms[s], sigma);
+        out[s].mmd2 = t[0] + t[1];             // as kad_unc_sets_kernel forms it, not from the means
+        for (int u = 0; u < S; ++u) cov[s * S + u] = cov_x * covs[(size_t)(s * S + u)];
         cov[s * S + s] += 4.0 / (md * (md - 1.0)) * t[2];
     }
     return FAD_OK;
@@ -2818,46 +2997,41 @@ int fad_prdc(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, in
                          (long long)m);
     if (n > INT32_MAX - kTile || m > INT32_MAX - kTile)
         return set_error(FAD_ERR_INVALID, "fad_prdc: %lld and %lld rows (at most %d per set)", (long long)n, (long long)m, INT32_MAX - kTile);
-    FAD_TRY(check_device(device));
-    DeviceGuard g(device);
-    if (!g.ok) return set_error(FAD_ERR_HIP, "hipSetDevice(%d) failed", device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    KadWorkspace& ws = workspace(device);
+    Ctx cx;
+    FAD_TRY(cx.open(dtype, FAD_KAD_GAUSSIAN, device, stream));
+    KadWorkspace& ws = *cx.ws;
+    const hipStream_t st = cx.st;
 
     Packed px, py;
-    FAD_TRY(pack_set(0, x, n, ldx, d, dtype, on_device, st, ws, &px));
-    FAD_TRY(pack_set(1, y, m, ldy, d, dtype, on_device, st, ws, &py));
-    const PrdcPlan qx = prdc_plan(px, px, dtype, kad::kTopkEpilogue), qy = prdc_plan(py, py, dtype, kad::kTopkEpilogue);
-    const PrdcPlan qc = prdc_plan(px, py, dtype, kad::kFlagEpilogue);
+    FAD_TRY(pack_set(cx, 0, x, n, ldx, d, on_device, &px));
+    FAD_TRY(pack_set(cx, 1, y, m, ldy, d, on_device, &py));
+    const PrdcPlan qx = prdc_plan(cx, px, px, kad::kTopkEpilogue), qy = prdc_plan(cx, py, py, kad::kTopkEpilogue);
+    const PrdcPlan qc = prdc_plan(cx, px, py, kad::kFlagEpilogue);
     const int64_t n_pad = qx.TJ * kTile, m_pad = qy.TJ * kTile;
 
     // radii x | radii y | flags | balls | totals | count slots
-    size_t at[7];
-    at[0] = 0;
-    at[1] = at[0] + align256((size_t)n_pad * sizeof(float));
-    at[2] = at[1] + align256((size_t)m_pad * sizeof(float));
-    at[3] = at[2] + align256((size_t)n_pad * sizeof(int));
-    at[4] = at[3] + align256((size_t)m_pad * sizeof(int));
-    at[5] = at[4] + align256(4 * sizeof(unsigned long long));
-    at[6] = at[5] + align256((size_t)(qc.NR * m_pad) * sizeof(int));
-    FAD_TRY(ws.prdc.reserve(at[6]));
+    Carve cv;
+    const auto r2x_r = cv.add<float>(n_pad), r2y_r = cv.add<float>(m_pad);
+    const auto flags_r = cv.add<int>(n_pad), balls_r = cv.add<int>(m_pad);
+    const auto totals_r = cv.add<unsigned long long>(4);
+    const auto counts_r = cv.add<int>(qc.NR * m_pad);
+    FAD_TRY(cv.reserve(ws.prdc));
     FAD_TRY(ws.lists.reserve((size_t)std::max(qx.NR * n_pad, qy.NR * m_pad) * (size_t)k * sizeof(float)));
-    char* pb = static_cast<char*>(ws.prdc.p);
-    float* r2x = reinterpret_cast<float*>(pb + at[0]);
-    float* r2y = reinterpret_cast<float*>(pb + at[1]);
-    int* flags = reinterpret_cast<int*>(pb + at[2]);
-    int* balls = reinterpret_cast<int*>(pb + at[3]);
-    unsigned long long* totals = reinterpret_cast<unsigned long long*>(pb + at[4]);
+    float* r2x = cv.ptr(r2x_r);
+    float* r2y = cv.ptr(r2y_r);
+    int* flags = cv.ptr(flags_r);
+    int* balls = cv.ptr(balls_r);
+    unsigned long long* totals = cv.ptr(totals_r);
     float* lists = static_cast<float*>(ws.lists.p);
 
-    FAD_TRY(radius_pass(px, k, dtype, device, st, lists, r2x));
-    FAD_TRY(radius_pass(py, k, dtype, device, st, lists, r2y));
+    FAD_TRY(radius_pass(cx, px, k, lists, r2x));
+    FAD_TRY(radius_pass(cx, py, k, lists, r2y));
     FAD_HIP_TRY(hipMemsetAsync(flags, 0, (size_t)n_pad * sizeof(int), st));
 
     PrdcArgs p{};
     p.a = px.img; p.ha = px.h; p.b = py.img; p.hb = py.h; p.pitch = px.pitch; p.nchunks = px.nchunks; p.k = k;
     p.TI = qc.TI; p.TJ = qc.TJ; p.rr = qc.rr; p.ra = r2x; p.rb = r2y;
-    p.counts = reinterpret_cast<int*>(pb + at[5]); p.count_pitch = m_pad; p.flags = flags;
+    p.counts = cv.ptr(counts_r); p.count_pitch = m_pad; p.flags = flags;
     for (const kad::Launch& l : kad::launches(qc.NR * qc.TJ, qc.per_launch, grid_cap(device))) {
         p.u0 = l.u0; p.cnt = l.cnt;
         FAD_TRY(with_dtype(dtype, [&](auto dt) { prdc_cross_kernel<dt><<<(unsigned)l.grid, kThreads, kLdsCross, st>>>(p); }));
@@ -2902,39 +3076,34 @@ int fad_nearest(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m,
                          authenticity ? " with authenticity" : "", authenticity ? std::max(k, 2) : k, (long long)n, (long long)m);
     if (n > INT32_MAX - kTile || m > INT32_MAX - kTile)
         return set_error(FAD_ERR_INVALID, "fad_nearest: %lld and %lld rows (at most %d per set)", (long long)n, (long long)m, INT32_MAX - kTile);
-    FAD_TRY(check_device(device));
-    DeviceGuard g(device);
-    if (!g.ok) return set_error(FAD_ERR_HIP, "hipSetDevice(%d) failed", device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    KadWorkspace& ws = workspace(device);
+    Ctx cx;
+    FAD_TRY(cx.open(dtype, FAD_KAD_GAUSSIAN, device, stream));
+    KadWorkspace& ws = *cx.ws;
+    const hipStream_t st = cx.st;
 
     Packed px, py;
-    FAD_TRY(pack_set(0, x, n, ldx, d, dtype, on_device, st, ws, &px));
-    FAD_TRY(pack_set(1, y, m, ldy, d, dtype, on_device, st, ws, &py));
-    const PrdcPlan qc = prdc_plan(px, py, dtype, kad::kNearestEpilogue), qx = prdc_plan(px, px, dtype, kad::kTopkEpilogue);
+    FAD_TRY(pack_set(cx, 0, x, n, ldx, d, on_device, &px));
+    FAD_TRY(pack_set(cx, 1, y, m, ldy, d, on_device, &py));
+    const PrdcPlan qc = prdc_plan(cx, px, py, kad::kNearestEpilogue), qx = prdc_plan(cx, px, px, kad::kTopkEpilogue);
     const int64_t n_pad = qx.TJ * kTile, m_pad = qc.TJ * kTile;
 
     // index | dist2 | radii x | nn radii | copied
-    size_t at[6];
-    at[0] = 0;
-    at[1] = at[0] + align256((size_t)(m * k) * sizeof(int32_t));
-    at[2] = at[1] + align256((size_t)(m * k) * sizeof(float));
-    at[3] = at[2] + align256((size_t)n_pad * sizeof(float));
-    at[4] = at[3] + align256((size_t)m * sizeof(float));
-    at[5] = at[4] + align256(sizeof(unsigned long long));
-    FAD_TRY(ws.near.reserve(at[5]));
+    Carve cv;
+    const auto index_r = cv.add<int32_t>(m * k);
+    const auto dist2_r = cv.add<float>(m * k), r2x_r = cv.add<float>(n_pad), nn_r2_r = cv.add<float>(m);
+    const auto copied_r = cv.add<unsigned long long>(1);
+    FAD_TRY(cv.reserve(ws.near));
     // the radius pass's float lists, then (stream-ordered) the cross pass's keys in the same buffer
     FAD_TRY(ws.lists.reserve(std::max((size_t)(qc.NR * m_pad * k) * sizeof(uint64_t),
                                       authenticity ? (size_t)(qx.NR * n_pad) * sizeof(float) : (size_t)0)));
-    char* nb = static_cast<char*>(ws.near.p);
-    int32_t* index_d = reinterpret_cast<int32_t*>(nb + at[0]);
-    float* dist2_d = reinterpret_cast<float*>(nb + at[1]);
-    float* r2x = reinterpret_cast<float*>(nb + at[2]);
-    float* nn_r2 = reinterpret_cast<float*>(nb + at[3]);
-    unsigned long long* copied_d = reinterpret_cast<unsigned long long*>(nb + at[4]);
+    int32_t* index_d = cv.ptr(index_r);
+    float* dist2_d = cv.ptr(dist2_r);
+    float* r2x = cv.ptr(r2x_r);
+    float* nn_r2 = cv.ptr(nn_r2_r);
+    unsigned long long* copied_d = cv.ptr(copied_r);
 
-    if (authenticity) FAD_TRY(radius_pass(px, 1, dtype, device, st, static_cast<float*>(ws.lists.p), r2x));
-    FAD_TRY(nearest_pass(px, py, k, dtype, device, st, static_cast<uint64_t*>(ws.lists.p), index_d, dist2_d));
+    if (authenticity) FAD_TRY(radius_pass(cx, px, 1, static_cast<float*>(ws.lists.p), r2x));
+    FAD_TRY(nearest_pass(cx, px, py, false, k, static_cast<uint64_t*>(ws.lists.p), index_d, dist2_d));
     unsigned long long copied = 0;
     if (authenticity) {
         FAD_HIP_TRY(hipMemsetAsync(copied_d, 0, sizeof(unsigned long long), st));
@@ -2967,33 +3136,30 @@ int fad_nn_test(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m,
     if (k > n + m - 1)
         return set_error(FAD_ERR_INVALID, "fad_nn_test: k = %d needs at least k + 1 pooled rows, got %lld", k, (long long)(n + m));
     FAD_TRY(perm_check_labels(n, m, labels, n_perm, labels_on_device));
-    FAD_TRY(check_device(device));
-    DeviceGuard g(device);
-    if (!g.ok) return set_error(FAD_ERR_HIP, "hipSetDevice(%d) failed", device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    KadWorkspace& ws = workspace(device);
+    Ctx cx;
+    FAD_TRY(cx.open(dtype, FAD_KAD_GAUSSIAN, device, stream));
+    KadWorkspace& ws = *cx.ws;
+    const hipStream_t st = cx.st;
 
     PermPrep pp;
-    FAD_TRY(perm_prepare(x, n, ldx, y, m, ldy, d, dtype, on_device, labels, n_perm, labels_on_device, st, ws, &pp));
+    FAD_TRY(perm_prepare(cx, x, n, ldx, y, m, ldy, d, on_device, labels, n_perm, labels_on_device, &pp));
     const int64_t N = pp.N, z_pad = pp.z_pad, NL = pp.NL, W = pp.W;
-    const Packed pz{pp.zimg, pp.zh, N, pp.pitch, (int)(pp.pitch / kChunk), pp.norm_sum};
-    const PrdcPlan q = prdc_plan(pz, pz, dtype, kad::kNearestEpilogue);
+    const Packed& pz = pp.z;
+    const PrdcPlan q = prdc_plan(cx, pz, pz, kad::kNearestEpilogue);
 
     // index | dist2 | counts [32 W][2]
-    size_t at[4];
-    at[0] = 0;
-    at[1] = at[0] + align256((size_t)(N * k) * sizeof(int32_t));
-    at[2] = at[1] + align256((size_t)(N * k) * sizeof(float));
-    at[3] = at[2] + align256((size_t)(64 * W) * sizeof(unsigned long long));
-    FAD_TRY(ws.near.reserve(at[3]));
+    Carve cv;
+    const auto index_r = cv.add<int32_t>(N * k);
+    const auto dist2_r = cv.add<float>(N * k);
+    const auto counts_r = cv.add<unsigned long long>(64 * W);
+    FAD_TRY(cv.reserve(ws.near));
     FAD_TRY(ws.lists.reserve((size_t)(q.NR * z_pad * k) * sizeof(uint64_t)));
-    char* nb = static_cast<char*>(ws.near.p);
-    int32_t* index_d = reinterpret_cast<int32_t*>(nb + at[0]);
-    float* dist2_d = reinterpret_cast<float*>(nb + at[1]);
-    unsigned long long* counts_d = reinterpret_cast<unsigned long long*>(nb + at[2]);
+    int32_t* index_d = cv.ptr(index_r);
+    float* dist2_d = cv.ptr(dist2_r);
+    unsigned long long* counts_d = cv.ptr(counts_r);
 
     // the graph (it never sees a label), then every labelling's votes on it
-    FAD_TRY(nearest_self_pass(pz, k, dtype, device, st, static_cast<uint64_t*>(ws.lists.p), index_d, dist2_d));
+    FAD_TRY(nearest_pass(cx, pz, pz, true, k, static_cast<uint64_t*>(ws.lists.p), index_d, dist2_d));
     FAD_HIP_TRY(hipMemsetAsync(counts_d, 0, (size_t)(64 * W) * sizeof(unsigned long long), st));
     nnv::nn_vote_kernel<<<dim3((unsigned)cdiv(N, nnv::kVoteRows), (unsigned)W), 256, 0, st>>>(pp.cols_d, z_pad, index_d, k, N, counts_d);
     FAD_HIP_TRY(hipGetLastError());
@@ -3044,124 +3210,25 @@ int fad_kad_permutation_test_k(const void* x, int64_t n, int64_t ldx, const void
     if (std::isnan(bandwidth) || std::isinf(bandwidth))
         return set_error(FAD_ERR_INVALID, "fad_kad_permutation_test: bandwidth %g is not finite", bandwidth);
     FAD_TRY(perm_check_labels(n, m, labels, n_perm, labels_on_device));
-    FAD_TRY(check_device(device));
-    DeviceGuard g(device);
-    if (!g.ok) return set_error(FAD_ERR_HIP, "hipSetDevice(%d) failed", device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    KadWorkspace& ws = workspace(device);
+    Ctx cx;
+    FAD_TRY(cx.open(dtype, kernel, device, stream));
 
     PermPrep pp;
-    FAD_TRY(perm_prepare(x, n, ldx, y, m, ldy, d, dtype, on_device, labels, n_perm, labels_on_device, st, ws, &pp));
-    char* zimg = pp.zimg;
-    float* zh = pp.zh;
-    uint32_t* lab = pp.lab;
-    uint32_t* rows_d = pp.rows_d;
-    uint32_t* cols_d = pp.cols_d;
-    const int64_t N = pp.N, TZ = pp.TZ, z_pad = pp.z_pad, nwz = pp.nwz, dp = pp.dp, pitch = pp.pitch, NL = pp.NL, W = pp.W;
-
+    FAD_TRY(perm_prepare(cx, x, n, ldx, y, m, ldy, d, on_device, labels, n_perm, labels_on_device, &pp));
     // sigma: the given one, or the median pairwise distance of Z (fad_kad_median_distance on the pooled rows, bit for bit)
-    const Packed pz{zimg, zh, N, pitch, (int)(pitch / kChunk), pp.norm_sum};
     double sigma;
     float c;
-    FAD_TRY(resolve_sigma(pz, bandwidth, kernel, dtype, device, st, ws, "fad_kad_permutation_test", &sigma, &c));
-
-    // r = K'1 and T = 1'r: kad_unc_cols_kernel's walk over Z x Z (one set, kad_unc_tiles.h), float32 kernel values
-    const bool f32 = dtype == FAD_F32;
-    const std::vector<int64_t> blk = kad::unc_blocks(N, nullptr, 0);
-    const int64_t rr = kad::unc_rows_per_unit(kad::unc_tiles(blk), kad::tiles_per_launch_for(dp, f32, kad::kUncEpilogue));
-    std::vector<kad::Unit> units;
-    std::vector<int64_t> seg_start;
-    kad::unc_units(blk, rr, &units, &seg_start);
-    const int64_t U = (int64_t)units.size();
-    std::vector<int64_t> gslots;
-    const std::vector<kad::PermLaunch> pl = kad::perm_launches(TZ, NL, dp, f32, grid_cap(device), &gslots);
-    const int ng = (int)gslots.size();
-    std::vector<PermGroup> groups((size_t)ng);
-    int64_t nslot_doubles = 0;
-    for (int q = 0; q < ng; ++q) {
-        const int64_t w0 = kad::perm_group_start(q, ng, W), nw = kad::perm_group_start(q + 1, ng, W) - w0;
-        groups[(size_t)q] = PermGroup{w0, nw, nslot_doubles, gslots[(size_t)q]};
-        nslot_doubles += gslots[(size_t)q] * 32 * nw;
-    }
-
-    // units | seg_start | r [z_pad] | T | groups | t [NL] | observed sums [3] | permutation slots
-    size_t at[9];
-    at[0] = 0;
-    at[1] = at[0] + align256((size_t)U * sizeof(kad::Unit));
-    at[2] = at[1] + align256(seg_start.size() * sizeof(int64_t));
-    at[3] = at[2] + align256((size_t)z_pad * sizeof(double));
-    at[4] = at[3] + align256(sizeof(double));
-    at[5] = at[4] + align256((size_t)ng * sizeof(PermGroup));
-    at[6] = at[5] + align256((size_t)NL * sizeof(double));
-    at[7] = at[6] + align256(3 * sizeof(double));
-    at[8] = at[7] + align256((size_t)nslot_doubles * sizeof(double));
-    FAD_TRY(ws.perm.reserve(at[8]));
-    FAD_TRY(ws.unc_slots.reserve((size_t)(U * kTile) * sizeof(double)));
-    char* pb = static_cast<char*>(ws.perm.p);
-    kad::Unit* units_d = reinterpret_cast<kad::Unit*>(pb + at[0]);
-    int64_t* seg_d = reinterpret_cast<int64_t*>(pb + at[1]);
-    double* r_d = reinterpret_cast<double*>(pb + at[2]);
-    double* tot_d = reinterpret_cast<double*>(pb + at[3]);
-    PermGroup* groups_d = reinterpret_cast<PermGroup*>(pb + at[4]);
-    double* t_d = reinterpret_cast<double*>(pb + at[5]);
-    double* obs_d = reinterpret_cast<double*>(pb + at[6]);
-    double* pslots = reinterpret_cast<double*>(pb + at[7]);
-    FAD_HIP_TRY(hipMemcpyAsync(units_d, units.data(), (size_t)U * sizeof(kad::Unit), hipMemcpyHostToDevice, st));
-    FAD_HIP_TRY(hipMemcpyAsync(seg_d, seg_start.data(), seg_start.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    FAD_HIP_TRY(hipMemcpyAsync(groups_d, groups.data(), (size_t)ng * sizeof(PermGroup), hipMemcpyHostToDevice, st));
-
-    ColArgs ca{};
-    ca.a = ca.b = zimg; ca.ha = ca.hb = zh; ca.pitch = pitch; ca.nchunks = pz.nchunks; ca.c = c;
-    ca.units = units_d; ca.slots = static_cast<double*>(ws.unc_slots.p); ca.slot_pitch = kTile;
-    for (const kad::Launch& l : kad::launches(U, kad::unc_units_per_launch(rr, dp, f32), grid_cap(device))) {
-        ca.u0 = l.u0; ca.cnt = l.cnt;
-        FAD_TRY(with_dtype_kernel(dtype, kernel, [&](auto dt, auto kf) {
-            kad_unc_cols_kernel<dt, kf><<<(unsigned)l.grid, kThreads, kLdsUnc, st>>>(ca);
-        }));
-    }
-    kad_perm_rows_kernel<<<(unsigned)cdiv(z_pad, 256), 256, 0, st>>>(ca.slots, seg_d, N, z_pad, r_d);
-    FAD_HIP_TRY(hipGetLastError());
-    kad_perm_total_kernel<<<1, 256, 0, st>>>(r_d, N, tot_d);
-    FAD_HIP_TRY(hipGetLastError());
-    double T;
-    FAD_HIP_TRY(hipMemcpyAsync(&T, tot_d, sizeof(double), hipMemcpyDeviceToHost, st));
-    FAD_HIP_TRY(hipStreamSynchronize(st));
+    FAD_TRY(resolve_sigma(cx, pp.z, bandwidth, "fad_kad_permutation_test", &sigma, &c));
 
     // the shift: the kernel value at the median distance (t = 1/2: e^-1/2, 2/3 for iq, 1 / sqrt(1.5) for imq) under the default sigma;
-    // the mean off-diagonal kernel value of Z under a given one.  Any constant gives the same t; it sets how much of each kernel value
-    // f16 keeps.
+    // the mean off-diagonal kernel value of Z, perm_run's own, under a given one
     const float at_median = kernel == FAD_KAD_IQ ? 0.66666666666666663f : kernel == FAD_KAD_IMQ ? 0.81649658092772603f : 0.60653065971263342f;
-    const float c0 = bandwidth > 0 ? (float)(T / ((double)N * (double)(N - 1))) : at_median;
-
-    FAD_HIP_TRY(hipMemsetAsync(pslots, 0, (size_t)nslot_doubles * sizeof(double), st));
-    PermArgs pa{};
-    pa.z = zimg; pa.h = zh; pa.pitch = pitch; pa.nchunks = pz.nchunks; pa.c = c; pa.c0 = c0; pa.TZ = TZ; pa.nwz = nwz; pa.z_pad = z_pad;
-    for (const kad::PermLaunch& l : pl) {
-        const PermGroup& gr = groups[(size_t)l.group];
-        pa.nw = (int)l.nw; pa.u0 = l.u0; pa.cnt = l.cnt;
-        pa.rowbits = rows_d + l.w0 * z_pad;
-        pa.colbits = cols_d + l.w0 * z_pad;
-        pa.slots = pslots + gr.slot_off;
-        FAD_TRY(with_dtype_kernel(dtype, kernel, [&](auto dt, auto kf) {
-            kad_perm_kernel<dt, kf><<<(unsigned)l.grid, kThreads, kLdsPerm, st>>>(pa);
-        }));
-    }
-    kad_perm_stats_kernel<<<(unsigned)NL, 256, 0, st>>>(pslots, groups_d, ng, lab, nwz, r_d, tot_d, (double)c0, n, m, t_d, obs_d);
-    FAD_HIP_TRY(hipGetLastError());
-    std::vector<double> t((size_t)NL);
+    std::vector<double> t;
     double obs[3];
-    FAD_HIP_TRY(hipMemcpyAsync(t.data(), t_d, (size_t)NL * sizeof(double), hipMemcpyDeviceToHost, st));
-    FAD_HIP_TRY(hipMemcpyAsync(obs, obs_d, sizeof(obs), hipMemcpyDeviceToHost, st));
-    FAD_HIP_TRY(hipStreamSynchronize(st));
+    FAD_TRY(perm_run(cx, pp, 1, &c, bandwidth > 0 ? nullptr : &at_median, &t, obs));
 
-    const double nd = (double)n, md = (double)m;
-    observed->mmd2 = t[0];
-    observed->kxx_mean = obs[0] / (nd * (nd - 1.0));
-    observed->kyy_mean = obs[1] / (md * (md - 1.0));
-    observed->kxy_mean = obs[2] / (nd * md);
-    observed->bandwidth = sigma;
-    observed->n = n;
-    observed->m = m;
+    fill_result(observed, obs[0], obs[1], obs[2], n, m, sigma);
+    observed->mmd2 = t[0];                     // as kad_perm_stats_kernel forms it, not from the means
     int64_t ge = 0;
     for (int64_t q = 0; q < n_perm; ++q) {
         null_out[q] = t[(size_t)q + 1];
@@ -3203,187 +3270,25 @@ int fad_kad_permutation_sweep(const void* x, int64_t n, int64_t ldx, const void*
         return set_error(FAD_ERR_INVALID, "%s: %d bandwidths, outside 1 .. %d", who, n_bw, FAD_KAD_PERM_MAX_BANDWIDTHS);
     FAD_TRY(check_kernel(kernel, who));
     FAD_TRY(perm_check_args(x, n, ldx, y, m, ldy, d, dtype, labels, n_perm));
-    for (int b = 0; b < n_bw; ++b)
-        if (!(bandwidths[b] > 0) || !std::isfinite(bandwidths[b]))
-            return set_error(FAD_ERR_INVALID, "%s: %s %d is %g; every one must be finite and > 0 (the pooled median is the factor 1)", who,
-                             relative ? "factor" : "bandwidth", b, bandwidths[b]);
+    FAD_TRY(check_bandwidths(bandwidths, n_bw, relative, who, true));
     FAD_TRY(perm_check_labels(n, m, labels, n_perm, labels_on_device));
-    FAD_TRY(check_device(device));
-    DeviceGuard g(device);
-    if (!g.ok) return set_error(FAD_ERR_HIP, "hipSetDevice(%d) failed", device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    KadWorkspace& ws = workspace(device);
+    Ctx cx;
+    FAD_TRY(cx.open(dtype, kernel, device, stream));
 
     PermPrep pp;
-    FAD_TRY(perm_prepare(x, n, ldx, y, m, ldy, d, dtype, on_device, labels, n_perm, labels_on_device, st, ws, &pp));
-    const int64_t N = pp.N, TZ = pp.TZ, z_pad = pp.z_pad, nwz = pp.nwz, dp = pp.dp, pitch = pp.pitch, NL = pp.NL;
-    const Packed pz{pp.zimg, pp.zh, N, pitch, (int)(pitch / kChunk), pp.norm_sum};
-
+    FAD_TRY(perm_prepare(cx, x, n, ldx, y, m, ldy, d, on_device, labels, n_perm, labels_on_device, &pp));
     // sigma_b: the given ones, or factors of the median pairwise distance of Z (found once); c_b as fad_kad_sweep forms it
-    double median = 1.0;
-    if (relative) {
-        FAD_TRY(median_of_packed(pz, dtype, device, st, ws, &median));
-        if (!(median > 0) || !std::isfinite(median))
-            return set_error(FAD_ERR_INVALID, "%s: the median pairwise distance of the pooled rows is %g; it must be > 0 -- are all rows"
-                             " identical?", who, median);
-    }
     const int B = n_bw;
-    double sigma[FAD_KAD_PERM_MAX_BANDWIDTHS];
-    float c[FAD_KAD_PERM_MAX_BANDWIDTHS], c0[FAD_KAD_PERM_MAX_BANDWIDTHS];
-    for (int b = 0; b < B; ++b) {
-        sigma[b] = relative ? bandwidths[b] * median : bandwidths[b];
-        if (sigma_constant(sigma[b], kernel, &c[b]) != SIGMA_OK)
-            return set_error(FAD_ERR_INVALID, "%s: bandwidth %d (%g) is outside the float32 range of the kernel", who, b, sigma[b]);
-    }
+    const int64_t NL = pp.NL;
+    double sigma[FAD_KAD_PERM_MAX_BANDWIDTHS], obs[3 * FAD_KAD_PERM_MAX_BANDWIDTHS];
+    float c[FAD_KAD_PERM_MAX_BANDWIDTHS];
+    FAD_TRY(resolve_sigmas(cx, pp.z, bandwidths, B, relative, who, true, sigma, c));
+    std::vector<double> t;
+    FAD_TRY(perm_run(cx, pp, B, c, nullptr, &t, obs));
 
-    // the r pass's units are fad_kad_permutation_test_k's: a unit's slot is one workgroup's, so r_b has the single call's bits at any size
-    const bool f32 = dtype == FAD_F32;
-    const std::vector<int64_t> blk = kad::unc_blocks(N, nullptr, 0);
-    const int64_t rr = kad::unc_rows_per_unit(kad::unc_tiles(blk), kad::tiles_per_launch_for(dp, f32, kad::kUncEpilogue));
-    std::vector<kad::Unit> units;
-    std::vector<int64_t> seg_start;
-    kad::unc_units(blk, rr, &units, &seg_start);
-    const int64_t U = (int64_t)units.size();
-
-    // the walks of the permutation pass; per bandwidth its word groups as kad_perm_stats_kernel reads them: walk i holds its bandwidths'
-    // slots one after the other, [nb][walk slots][32 nw]
-    const std::vector<kad::PermSweepWalk> walks = kad::perm_sweep_walks(B, NL);
-    std::vector<int64_t> wslots;
-    const std::vector<kad::PermSweepLaunch> pl = kad::perm_sweep_launches(TZ, walks, dp, f32, grid_cap(device), &wslots);
-    int64_t ngmax = 1, nslot_doubles = 0;
-    for (const kad::PermSweepWalk& w : walks) ngmax = std::max(ngmax, w.wgs);
-    std::vector<PermGroup> groups((size_t)(B * ngmax));
-    std::vector<int> ngs((size_t)B, 0);
-    std::vector<int64_t> walk_off(walks.size());
-    for (size_t i = 0; i < walks.size(); ++i) {
-        const kad::PermSweepWalk& w = walks[i];
-        walk_off[i] = nslot_doubles;
-        const int64_t per_bw = wslots[i] * 32 * w.nw;
-        for (int b = 0; b < w.nb; ++b) {
-            groups[(size_t)((w.b0 + b) * ngmax + w.wg)] = PermGroup{w.w0, w.nw, nslot_doubles + b * per_bw, wslots[i]};
-            ngs[(size_t)(w.b0 + b)] = (int)w.wgs;
-        }
-        nslot_doubles += w.nb * per_bw;
-    }
-
-    // units | seg_start | r [B][z_pad] | T [B] | groups [B][ngmax] | t [B][NL] | observed sums [B][3] | permutation slots
-    size_t at[9];
-    at[0] = 0;
-    at[1] = at[0] + align256((size_t)U * sizeof(kad::Unit));
-    at[2] = at[1] + align256(seg_start.size() * sizeof(int64_t));
-    at[3] = at[2] + align256((size_t)(B * z_pad) * sizeof(double));
-    at[4] = at[3] + align256((size_t)B * sizeof(double));
-    at[5] = at[4] + align256(groups.size() * sizeof(PermGroup));
-    at[6] = at[5] + align256((size_t)(B * NL) * sizeof(double));
-    at[7] = at[6] + align256((size_t)(3 * B) * sizeof(double));
-    at[8] = at[7] + align256((size_t)nslot_doubles * sizeof(double));
-    FAD_TRY(ws.perm.reserve(at[8]));
-    const int rg = std::min(B, kad::kPermSweepNB);                                     // bandwidths per r pass at most
-    FAD_TRY(ws.unc_slots.reserve((size_t)(rg * U * kTile) * sizeof(double)));
-    char* pb = static_cast<char*>(ws.perm.p);
-    kad::Unit* units_d = reinterpret_cast<kad::Unit*>(pb + at[0]);
-    int64_t* seg_d = reinterpret_cast<int64_t*>(pb + at[1]);
-    double* r_d = reinterpret_cast<double*>(pb + at[2]);
-    double* tot_d = reinterpret_cast<double*>(pb + at[3]);
-    PermGroup* groups_d = reinterpret_cast<PermGroup*>(pb + at[4]);
-    double* t_d = reinterpret_cast<double*>(pb + at[5]);
-    double* obs_d = reinterpret_cast<double*>(pb + at[6]);
-    double* pslots = reinterpret_cast<double*>(pb + at[7]);
-    FAD_HIP_TRY(hipMemcpyAsync(units_d, units.data(), (size_t)U * sizeof(kad::Unit), hipMemcpyHostToDevice, st));
-    FAD_HIP_TRY(hipMemcpyAsync(seg_d, seg_start.data(), seg_start.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    FAD_HIP_TRY(hipMemcpyAsync(groups_d, groups.data(), groups.size() * sizeof(PermGroup), hipMemcpyHostToDevice, st));
-
-    // r_b = K_b'1 and T_b = 1'r_b, up to kPermSweepNB bandwidths per walk over Z x Z; a launch of NB bandwidths weighs NB epilogues
-    ColArgs ca{};
-    ca.a = ca.b = pp.zimg; ca.ha = ca.hb = pp.zh; ca.pitch = pitch; ca.nchunks = pz.nchunks;
-    ca.units = units_d; ca.slots = static_cast<double*>(ws.unc_slots.p); ca.slot_pitch = kTile;
-    for (int b0 = 0; b0 < B; b0 += kad::kPermSweepNB) {
-        const int nb = std::min(kad::kPermSweepNB, B - b0), knb = kad::perm_sweep_kernel_nb(nb);
-        const int64_t per = std::max<int64_t>(1, kad::tiles_per_launch_for(dp, f32, kad::kUncEpilogue * knb) / rr);
-        for (const kad::Launch& l : kad::launches(U, knb == 1 ? kad::unc_units_per_launch(rr, dp, f32) : per, grid_cap(device))) {
-            ca.u0 = l.u0; ca.cnt = l.cnt; ca.c = c[b0];
-            auto sweep = [&](auto nbc) {
-                constexpr int NB = decltype(nbc)::value;
-                ColSweepArgs<NB> q;
-                q.p = ca; q.nb = nb; q.bstride = U * kTile;
-                for (int b = 0; b < NB; ++b) q.c[b] = c[b0 + std::min(b, nb - 1)];
-                return with_dtype_kernel(dtype, kernel, [&](auto dt, auto kf) {
-                    kad_unc_cols_sweep_kernel<dt, kf, NB><<<(unsigned)l.grid, kThreads, lds_unc_sweep<NB>(), st>>>(q);
-                });
-            };
-            if (knb == 1) {
-                FAD_TRY(with_dtype_kernel(dtype, kernel, [&](auto dt, auto kf) {
-                    kad_unc_cols_kernel<dt, kf><<<(unsigned)l.grid, kThreads, kLdsUnc, st>>>(ca);
-                }));
-            } else if (knb == 2) {
-                FAD_TRY(sweep(std::integral_constant<int, 2>{}));
-            } else {
-                FAD_TRY(sweep(std::integral_constant<int, 4>{}));
-            }
-        }
-        for (int b = 0; b < nb; ++b) {
-            kad_perm_rows_kernel<<<(unsigned)cdiv(z_pad, 256), 256, 0, st>>>(ca.slots + b * U * kTile, seg_d, N, z_pad, r_d + (b0 + b) * z_pad);
-            FAD_HIP_TRY(hipGetLastError());
-            kad_perm_total_kernel<<<1, 256, 0, st>>>(r_d + (b0 + b) * z_pad, N, tot_d + b0 + b);
-            FAD_HIP_TRY(hipGetLastError());
-        }
-    }
-    double T[FAD_KAD_PERM_MAX_BANDWIDTHS];
-    FAD_HIP_TRY(hipMemcpyAsync(T, tot_d, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
-    FAD_HIP_TRY(hipStreamSynchronize(st));
-    // the shift of bandwidth b: the mean off-diagonal kernel value of Z under sigma_b, as the single call's under a given sigma
-    for (int b = 0; b < B; ++b) c0[b] = (float)(T[b] / ((double)N * (double)(N - 1)));
-
-    FAD_HIP_TRY(hipMemsetAsync(pslots, 0, (size_t)nslot_doubles * sizeof(double), st));
-    PermArgs pa{};
-    pa.z = pp.zimg; pa.h = pp.zh; pa.pitch = pitch; pa.nchunks = pz.nchunks; pa.TZ = TZ; pa.nwz = nwz; pa.z_pad = z_pad;
-    for (const kad::PermSweepLaunch& l : pl) {
-        const kad::PermSweepWalk& w = walks[(size_t)l.walk];
-        pa.nw = (int)w.nw; pa.u0 = l.u0; pa.cnt = l.cnt;
-        pa.rowbits = pp.rows_d + w.w0 * z_pad;
-        pa.colbits = pp.cols_d + w.w0 * z_pad;
-        pa.slots = pslots + walk_off[(size_t)l.walk];
-        pa.c = c[w.b0]; pa.c0 = c0[w.b0];
-        auto sweep = [&](auto nbc) {
-            constexpr int NB = decltype(nbc)::value;
-            PermSweepArgs<NB> q;
-            q.p = pa; q.nb = w.nb; q.bstride = wslots[(size_t)l.walk] * 32 * w.nw;
-            for (int b = 0; b < NB; ++b) { q.c[b] = c[w.b0 + std::min(b, w.nb - 1)]; q.c0[b] = c0[w.b0 + std::min(b, w.nb - 1)]; }
-            return with_dtype_kernel(dtype, kernel, [&](auto dt, auto kf) {
-                kad_perm_sweep_kernel<dt, kf, NB><<<(unsigned)l.grid, kThreads, kLdsPerm, st>>>(q);
-            });
-        };
-        if (w.kernel_nb == 1) {                // one bandwidth: fad_kad_permutation_test_k's own kernel and cut
-            FAD_TRY(with_dtype_kernel(dtype, kernel, [&](auto dt, auto kf) {
-                kad_perm_kernel<dt, kf><<<(unsigned)l.grid, kThreads, kLdsPerm, st>>>(pa);
-            }));
-        } else if (w.kernel_nb == 2) {
-            FAD_TRY(sweep(std::integral_constant<int, 2>{}));
-        } else {
-            FAD_TRY(sweep(std::integral_constant<int, 4>{}));
-        }
-    }
-    for (int b = 0; b < B; ++b) {
-        kad_perm_stats_kernel<<<(unsigned)NL, 256, 0, st>>>(pslots, groups_d + b * ngmax, ngs[(size_t)b], pp.lab, nwz, r_d + b * z_pad, tot_d + b,
-                                                            (double)c0[b], n, m, t_d + b * NL, obs_d + 3 * b);
-        FAD_HIP_TRY(hipGetLastError());
-    }
-    std::vector<double> t((size_t)(B * NL));
-    double obs[3 * FAD_KAD_PERM_MAX_BANDWIDTHS];
-    FAD_HIP_TRY(hipMemcpyAsync(t.data(), t_d, t.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    FAD_HIP_TRY(hipMemcpyAsync(obs, obs_d, (size_t)(3 * B) * sizeof(double), hipMemcpyDeviceToHost, st));
-    FAD_HIP_TRY(hipStreamSynchronize(st));
-
-    const double nd = (double)n, md = (double)m;
     for (int b = 0; b < B; ++b) {              // only now: a refusal above leaves the outputs as they were
-        fad_kad_result_t& r = observed[b];
-        r.mmd2 = t[(size_t)(b * NL)];
-        r.kxx_mean = obs[3 * b] / (nd * (nd - 1.0));
-        r.kyy_mean = obs[3 * b + 1] / (md * (md - 1.0));
-        r.kxy_mean = obs[3 * b + 2] / (nd * md);
-        r.bandwidth = sigma[b];
-        r.n = n;
-        r.m = m;
+        fill_result(&observed[b], obs[3 * b], obs[3 * b + 1], obs[3 * b + 2], n, m, sigma[b]);
+        observed[b].mmd2 = t[(size_t)(b * NL)];                                        // as kad_perm_stats_kernel forms it
         for (int64_t q = 0; q < n_perm; ++q) null_out[b * n_perm + q] = t[(size_t)(b * NL + q + 1)];
     }
     kad::perm_aggregate(t.data(), B, NL, p_values, p_aggregated);
@@ -3399,47 +3304,27 @@ int fad_kid(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int
     FAD_TRY(check_rows(y, m, ldy, d, dtype, "fad_kid (y)"));
     KidParams k;
     FAD_TRY(kid_params(degree, gamma, coef0, d, "fad_kid", &k));
-    FAD_TRY(check_device(device));
-    DeviceGuard g(device);
-    if (!g.ok) return set_error(FAD_ERR_HIP, "hipSetDevice(%d) failed", device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    KadWorkspace& ws = workspace(device);
-    FAD_TRY(ws.small.reserve(4096 * sizeof(double) + 2 * kHistBins * sizeof(unsigned long long)));
+    Ctx cx;
+    FAD_TRY(cx.open(dtype, FAD_KAD_GAUSSIAN, device, stream));
+    FAD_TRY(reserve_small(*cx.ws));
 
     Packed px, py;
     const void* staged[2] = {nullptr, nullptr};
-    FAD_TRY(kid_pack(0, x, n, ldx, d, dtype, on_device, nullptr, n, kad::blocks(n) * kTile, 1, st, ws, &staged[0], &px));
-    FAD_TRY(kid_pack(1, y, m, ldy, d, dtype, on_device, nullptr, m, kad::blocks(m) * kTile, 1, st, ws, &staged[1], &py));
+    FAD_TRY(kid_pack(cx, 0, x, n, ldx, d, on_device, nullptr, n, kad::blocks(n) * kTile, 1, &staged[0], &px));
+    FAD_TRY(kid_pack(cx, 1, y, m, ldy, d, on_device, nullptr, m, kad::blocks(m) * kTile, 1, &staged[1], &py));
 
-    // passes as fad_kad's: XX and YY over their triangles, XY over the rectangle with the larger set as the row operand; slots as
-    // sum_passes lays them out, summed by kad_slots_sum_kernel
+    // passes as fad_kad's: XX and YY over their triangles, XY over the rectangle with the larger set as the row operand; launches, slots
+    // and sum are sum_passes' own, with kid_pass_kernel in kad_pass_kernel's place
     const bool x_rows = n >= m;
     const PassArgs passes[3] = {pass_args(px, px, true, 0.f), pass_args(py, py, true, 0.f), pass_args(x_rows ? px : py, x_rows ? py : px, false, 0.f)};
-    std::vector<kad::Launch> launches[3];
-    int64_t off[4] = {0};
-    for (int q = 0; q < 3; ++q) {
-        launches[q] = pass_launches(passes[q], dtype, false, device);
-        off[q + 1] = off[q];
-        for (const kad::Launch& l : launches[q]) off[q + 1] += l.grid;
-    }
-    FAD_TRY(ws.slots.reserve((size_t)off[3] * sizeof(double)));
-    int64_t* off_d = reinterpret_cast<int64_t*>(static_cast<double*>(ws.small.p) + 8);
-    double* sums_d = static_cast<double*>(ws.small.p) + 16;
-    FAD_HIP_TRY(hipMemcpyAsync(off_d, off, sizeof(off), hipMemcpyHostToDevice, st));
-    for (int q = 0; q < 3; ++q) {
-        KidArgs a = kid_args(passes[q], k);
-        a.p.slots = static_cast<double*>(ws.slots.p) + off[q];
-        for (const kad::Launch& l : launches[q]) {
-            a.p.u0 = l.u0; a.p.cnt = l.cnt;
-            FAD_TRY(with_dtype(dtype, [&](auto dt) { kid_pass_kernel<dt><<<(unsigned)l.grid, kThreads, kLdsSum, st>>>(a); }));
-            a.p.slots += l.grid;
-        }
-    }
-    kad_slots_sum_kernel<<<3, 256, 0, st>>>(static_cast<const double*>(ws.slots.p), off_d, sums_d);
-    FAD_HIP_TRY(hipGetLastError());
+    double* sums_d = static_cast<double*>(cx.ws->small.p) + 16;
+    FAD_TRY(sum_passes(cx, passes, sums_d, [&](const PassArgs& p, const kad::Launch& l) {
+        const KidArgs a = kid_args(p, k);
+        return with_dtype(dtype, [&](auto dt) { kid_pass_kernel<dt><<<(unsigned)l.grid, kThreads, kLdsSum, cx.st>>>(a); });
+    }));
     double sums[3];
-    FAD_HIP_TRY(hipMemcpyAsync(sums, sums_d, sizeof(sums), hipMemcpyDeviceToHost, st));
-    FAD_HIP_TRY(hipStreamSynchronize(st));
+    FAD_HIP_TRY(hipMemcpyAsync(sums, sums_d, sizeof(sums), hipMemcpyDeviceToHost, cx.st));
+    FAD_HIP_TRY(hipStreamSynchronize(cx.st));
     for (int q = 0; q < 3; ++q)
         if (!std::isfinite(sums[q]))
             return set_error(FAD_ERR_NOT_FINITE, "fad_kid: the kernel sum of %s is not finite (NaN/Inf rows, or (gamma a.b + coef0)^%d beyond float32)",
@@ -3476,11 +3361,10 @@ int fad_kid_subsets(const void* x, int64_t n, int64_t ldx, const void* y, int64_
                          (long long)std::min(n, m));
     if (n_subsets < 1) return set_error(FAD_ERR_INVALID, "fad_kid_subsets: %lld subsets (at least 1)", (long long)n_subsets);
     if (n > INT32_MAX || m > INT32_MAX) return set_error(FAD_ERR_INVALID, "fad_kid_subsets: the index is 32-bit, at most %d rows per set", INT32_MAX);
-    FAD_TRY(check_device(device));
-    DeviceGuard g(device);
-    if (!g.ok) return set_error(FAD_ERR_HIP, "hipSetDevice(%d) failed", device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    KadWorkspace& ws = workspace(device);
+    Ctx cx;
+    FAD_TRY(cx.open(dtype, FAD_KAD_GAUSSIAN, device, stream));
+    KadWorkspace& ws = *cx.ws;
+    const hipStream_t st = cx.st;
 
     // the index lists on the device, checked there before any row is read through them
     const int64_t count = n_subsets * s;
@@ -3518,8 +3402,8 @@ int fad_kid_subsets(const void* x, int64_t n, int64_t ldx, const void* y, int64_
     const void* staged[2] = {nullptr, nullptr};
     for (const kid::Group& grp : kid::plan(n_subsets, s, row_bytes, kid::kImageBudget)) {
         Packed px, py;
-        FAD_TRY(kid_pack(0, x, n, ldx, d, dtype, on_device, ix + grp.q0 * s, s, img_rows, grp.count, st, ws, &staged[0], &px));
-        FAD_TRY(kid_pack(1, y, m, ldy, d, dtype, on_device, iy + grp.q0 * s, s, img_rows, grp.count, st, ws, &staged[1], &py));
+        FAD_TRY(kid_pack(cx, 0, x, n, ldx, d, on_device, ix + grp.q0 * s, s, img_rows, grp.count, &staged[0], &px));
+        FAD_TRY(kid_pack(cx, 1, y, m, ldy, d, on_device, iy + grp.q0 * s, s, img_rows, grp.count, &staged[1], &py));
         // ws.slots: the group's units, one float64 each, then the unit table the pass reads
         const int64_t total = grp.count * U;
         FAD_TRY(ws.slots.reserve((size_t)total * (sizeof(double) + sizeof(KidUnitRow))));

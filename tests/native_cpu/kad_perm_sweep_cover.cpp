@@ -4,7 +4,8 @@
 // bandwidths; every launch stays under tiles_per_launch_for(.., perm_epilogue(kernel_nb * nw)); a walk's slots are as many as its widest
 // launch's workgroups; the walks are as few as any uniform cut into runs of 1, 2 or 4 bandwidths gives, the smaller run at a tie (one walk per bandwidth
 // when the labellings fill kPermWords words); and a
-// walk of one bandwidth is cut exactly as kad_perm_tiles.h cuts the single test.
+// walk of one bandwidth is cut exactly as kad_perm_tiles.h cuts the single test (check_single: the same groups, slots and launches, which
+// is what lets the single test run through the sweep's host driver).
 #include "../../fadtk_amd/csrc/kad_perm_sweep_tiles.h"
 
 #include <cstdio>
@@ -88,6 +89,41 @@ static void check(int64_t N, int n_bw, int64_t labellings, int64_t depth, bool f
     printf("%s: N %lld B %d labellings %lld NB %d walks %zu launches %zu\n", label, (long long)N, n_bw, (long long)labellings, NB, walks.size(), ls.size());
 }
 
+// One bandwidth through the sweep's plan is the single test's plan, exactly: fad_kad_permutation_test_k runs the sweep's driver with one
+// bandwidth (kad.hip perm_run), so perm_sweep_walks(1, NL) with perm_sweep_launches must give perm_launches' groups (their number, w0
+// and nw), the slots of each group and the sequence of (group, u0, cnt, grid).
+static void check_single(int64_t TZ, int64_t NL, int64_t depth, bool f32, int64_t cap) {
+    char label[128];
+    snprintf(label, sizeof(label), "single: TZ %lld NL %lld depth %lld f32 %d cap %lld budget %lld", (long long)TZ, (long long)NL, (long long)depth,
+             (int)f32, (long long)cap, (long long)launch_budget());
+    std::vector<int64_t> gslots, wslots;
+    const std::vector<PermLaunch> single = perm_launches(TZ, NL, depth, f32, cap, &gslots);
+    const std::vector<PermSweepWalk> walks = perm_sweep_walks(1, NL);
+    const std::vector<PermSweepLaunch> ls = perm_sweep_launches(TZ, walks, depth, f32, cap, &wslots);
+    const int64_t W = perm_words(NL), ng = perm_groups(W);
+    CHECK((int64_t)walks.size() == ng && (int64_t)gslots.size() == ng, "%s: %zu walks, %zu groups, perm_groups %lld", label, walks.size(),
+          gslots.size(), (long long)ng);
+    for (size_t g = 0; g < walks.size() && g < gslots.size(); ++g) {
+        const PermSweepWalk& w = walks[g];
+        const int64_t w0 = perm_group_start((int64_t)g, ng, W), nw = perm_group_start((int64_t)g + 1, ng, W) - w0;
+        CHECK(w.b0 == 0 && w.nb == 1 && w.kernel_nb == 1 && w.wg == (int64_t)g && w.wgs == ng, "%s: walk %zu is not word group %zu of one bandwidth",
+              label, g, g);
+        CHECK(w.w0 == w0 && w.nw == nw, "%s: walk %zu words [%lld, +%lld), group [%lld, +%lld)", label, g, (long long)w.w0, (long long)w.nw,
+              (long long)w0, (long long)nw);
+        CHECK(wslots[g] == gslots[g], "%s: walk %zu has %lld slots, the group %lld", label, g, (long long)wslots[g], (long long)gslots[g]);
+    }
+    CHECK(single.size() == ls.size(), "%s: %zu launches, the single test %zu", label, ls.size(), single.size());
+    for (size_t i = 0; i < single.size() && i < ls.size(); ++i) {
+        const PermLaunch& a = single[i];
+        const PermSweepLaunch& b = ls[i];
+        CHECK(a.group == b.walk && a.u0 == b.u0 && a.cnt == b.cnt && a.grid == b.grid, "%s: launch %zu is (%lld, %lld, %lld, %lld), the single test's "
+              "(%lld, %lld, %lld, %lld)", label, i, (long long)b.walk, (long long)b.u0, (long long)b.cnt, (long long)b.grid, (long long)a.group,
+              (long long)a.u0, (long long)a.cnt, (long long)a.grid);
+        if (b.walk >= 0 && b.walk < (int64_t)walks.size())
+            CHECK(a.w0 == walks[(size_t)b.walk].w0 && a.nw == walks[(size_t)b.walk].nw, "%s: launch %zu takes other words than the single test's", label, i);
+    }
+}
+
 int main() {
     for (int B = 1; B <= kPermSweepMax; ++B)
         for (int64_t P : {1, 31, 32, 199, 255, 256, 300, 511, 512, 999, 1023, 1024, 2048})
@@ -112,6 +148,20 @@ int main() {
         check(2700, 3, 34, 24, true, 512, "cut test f32, B = 3, P = 33");
         check(2700, 5, 301, 80, false, 512, "cut test, B = 5, P = 300");
     }
+    fad::kad::set_launch_budget(0);
+    // the single test through the sweep's plan, under the default budget and under one at which the largest case (820 tiles) takes 13 launches
+    int64_t most = 0;
+    for (int64_t budget : {(int64_t)0, (int64_t)1}) {
+        fad::kad::set_launch_budget(budget);
+        for (int64_t NL : {2, 32, 33, 1024, 1025, 2049, 65537})
+            for (int64_t TZ : {1, 2, 3, 9, 40})
+                for (int64_t depth : {16, 512, 2048})
+                    for (bool f32 : {false, true})
+                        for (int64_t cap : {8, 504}) check_single(TZ, NL, depth, f32, cap);
+        const std::vector<PermSweepWalk> one = perm_sweep_walks(1, 2);
+        most = (int64_t)perm_sweep_launches(40, one, 2048, true, 504).size();
+    }
+    CHECK(most > 1, "the small budget does not cut the largest case into several launches (%lld)", (long long)most);
     fad::kad::set_launch_budget(0);
     if (fails) { printf("%d failures\n", fails); return 1; }
     printf("OK\n");
