@@ -61,6 +61,8 @@ struct fad_moments {
     hipEvent_t rs_pending = nullptr;       // ... the library's event behind the handle's last detached walk: settle() makes a reader's stream wait for it
     hipEvent_t rs_reader = nullptr;        // ... and the handle's own event behind its last ASYNCHRONOUS reader (moments_mark_read): the next detached walk,
     bool rs_reader_set = false;            //     which rewrites the running sums on the side stream, waits for it
+    hipEvent_t rs_caller = nullptr;        // ... and the handle's own event behind its last walk on the CALLER's stream (unaligned rows, bfloat16, float32):
+    bool rs_caller_set = false;            //     the next detached walk continues that walk's carry, so it waits for it as well
     bool staged_input = false;             // update_any is feeding host rows through the staging area: no detached walk over those
     int tile256 = 1;                       // 0: FAD_MOMENTS_TILE256=0 (read at creation) keeps D >= 512 on the 128 x 128 kernel
     // the segment tables of the last fused update_segmented call, kept on the host: a caller feeding groups of the SAME file sizes
@@ -451,6 +453,9 @@ static int running_sums(int count, fad_moments* const* hs, const void* const* ro
             //  caller's stream before the handle was reset would otherwise see the NEXT rows' sums)
             for (int i = 0; i < count; ++i)
                 if (n[i] > 0 && hs[i]->rs_reader_set) { FAD_HIP_TRY(hipStreamWaitEvent(side, hs[i]->rs_reader, 0)); hs[i]->rs_reader_set = false; }
+            // (... and a walk of the same handle on the caller's stream that may not have left its sums yet: this walk starts from them)
+            for (int i = 0; i < count; ++i)
+                if (n[i] > 0 && hs[i]->rs_caller_set) { FAD_HIP_TRY(hipStreamWaitEvent(side, hs[i]->rs_caller, 0)); hs[i]->rs_caller_set = false; }
             run_st = side;
         } else if (side) {
             if (!h0->rs_fork) {
@@ -484,6 +489,17 @@ static int running_sums(int count, fad_moments* const* hs, const void* const* ro
         else hipLaunchKernelGGL((moments_running_colsum<float, false>), grid, dim3(256), kRunLds, st, L);
     }
     FAD_HIP_TRY(hipGetLastError());
+    if (!(dtype == FAD_F16 && wide)) {
+        // a detached walk waits for nothing on the caller's stream -- but it continues THIS walk's carry if the handle's next rows are
+        // aligned float16: it waits for the event behind this walk (rs_caller)
+        for (int i = 0; i < count; ++i) {
+            fad_moments* h = hs[i];
+            if (n[i] <= 0 || !h->ref_mean || !h->runsum_covers) continue;
+            if (!h->rs_caller) FAD_HIP_TRY(hipEventCreateWithFlags(&h->rs_caller, hipEventDisableTiming));
+            FAD_HIP_TRY(hipEventRecord(h->rs_caller, st));
+            h->rs_caller_set = true;
+        }
+    }
     return FAD_OK;
 }
 
@@ -885,6 +901,7 @@ int fad_moments_destroy(fad_moments_t* h) {
     if (h->rs_join) (void)hipEventDestroy(h->rs_join);
     if (h->ev) { for (int i = 0; i < fad_moments::kRing * 3; ++i) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]); delete[] h->ev; }
     if (h->rs_reader) (void)hipEventDestroy(h->rs_reader);
+    if (h->rs_caller) (void)hipEventDestroy(h->rs_caller);
     delete h;
     return FAD_OK;
 }
