@@ -37,6 +37,9 @@ def __getattr__(name):
     if name in ("KernelDistance", "calc_kernel_distance", "calc_kernel_distance_full"):      # lazy, as KAD's
         from . import kid
         return getattr(kid, name)
+    if name in ("SinkhornDivergence", "calc_sinkhorn_divergence"):      # lazy, as KAD's
+        from . import sinkhorn
+        return getattr(sinkhorn, name)
     if name == "cache_embedding_files":
         from .fad_batch import cache_embedding_files
         return cache_embedding_files

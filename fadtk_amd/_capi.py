@@ -91,6 +91,19 @@ class FadKidResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class FadSinkhornResult(C.Structure):
+    _fields_ = [("divergence", C.c_double), ("ot_xy", C.c_double), ("ot_xx", C.c_double), ("ot_yy", C.c_double),
+                ("epsilon", C.c_double), ("marginal_error", C.c_double), ("marginal_error_xx", C.c_double),
+                ("marginal_error_yy", C.c_double), ("n", C.c_int64), ("m", C.c_int64), ("iterations", C.c_int)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class FadSinkhornDetail(C.Structure):
+    _fields_ = [("f", C.c_void_p), ("g", C.c_void_p), ("pot_x", C.c_void_p), ("pot_y", C.c_void_p)]
+
+
 _P = C.c_void_p
 _I64 = C.c_int64
 # name -> (restype, argtypes)     -- one entry per declaration in include/fad_hip.h
@@ -176,6 +189,8 @@ SIGNATURES = {
                           C.c_int, _P]),
     "fad_kid_subsets": (C.c_int, [_P, _I64, _I64, _P, _I64, _I64, _I64, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _P, _P, _I64, _I64,
                                   C.c_int, _P, _P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, _P]),
+    "fad_sinkhorn": (C.c_int, [_P, _I64, _I64, _P, _I64, _I64, _I64, C.c_int, C.c_int, C.c_double, C.c_int, C.POINTER(FadSinkhornResult),
+                               C.POINTER(FadSinkhornDetail), C.c_int, _P]),
 }
 
 _lib = None

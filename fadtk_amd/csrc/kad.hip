@@ -2,7 +2,8 @@
 // of one set (the default bandwidth).  DESIGN.md 4.6.  Per-song KAD (4.7), the k-NN precision / recall / density / coverage (4.8),
 // KAD's standard errors (4.9), its permutation test (4.10), the nearest baseline rows with authenticity (4.11), KAD at several
 // bandwidths in one pass (4.12), the permutation test at several bandwidths, aggregated (4.13), the leave-one-out k-NN two-sample
-// test on the pooled rows (4.14) and the polynomial-kernel distance of the KID protocol (4.15) run on the same main loop.
+// test on the pooled rows (4.14), the polynomial-kernel distance of the KID protocol (4.15) and the Sinkhorn divergence (4.16) run on
+// the same main loop.
 //
 // Every pass is one GEMM-shaped walk over 128 x 128 tiles of a pair space (kad_tiles.h) whose n x m matrix is never stored:
 //   - pack:   each set is copied once into a zero-padded [n_pad x dp] image of its own dtype (dp: D rounded up to 128 bytes, n_pad:
@@ -571,6 +572,154 @@ __global__ void __launch_bounds__(256) kad_song_reduce_kernel(const double* __re
             kyy[s] = 2.0 * ry[0] / (md * (md - 1.0));
         }
     }
+}
+
+// ------------------------------------------------------------------------------------------ Sinkhorn divergence
+// One Sinkhorn half-step is the cross pass above with a soft-min epilogue: for every column j, LSE_i((p_i + S'_ij) / eps) over the rows
+// i, S' = a.b + h_a + h_b = -C.  The row potential rides in the row operand's h vector (ha[i] = h_a[i] + p_i, still -inf on padding
+// rows), so the main loop is tile_mfma's, unchanged, and the accumulators end at v = p_i - C_ij.  No clamp of C at 0: no root is taken.
+// A column's state is the pair (M, S) = (max v, sum of exp2((v - M) c)), c = log2(e) / eps: M stays in the units of v, so it enters the
+// new potential unscaled, and the exponent is formed from the difference to the maximum, never from v / eps itself.  A state with
+// nothing in it is (-inf, 0); merges take the reference 0 in place of a maximum of -inf, so -inf - (-inf) is never formed and a
+// padding row adds exp2(-inf) = 0 exactly.
+struct SoftminArgs {
+    const char* a; const char* b;              // row operand (reduced over), column operand
+    const float* ha; const float* hb;          // ha: h + potential of the rows; hb: h of the columns
+    int64_t pitch;
+    int nchunks;
+    float c;                                   // log2(e) / eps
+    int64_t u0, cnt;                           // the launch's units [u0, u0 + cnt)
+    int64_t TI, TJ, rr;                        // the cross unit map
+    float2* slots; int64_t slot_pitch;         // slots[R * slot_pitch + j] = (M, S) of column j over row range R
+};
+
+__device__ __forceinline__ float lse_ref(float m) { return m == -INFINITY ? 0.f : m; }
+
+// (M, S) <- (M, S) merged with (m2, s2), in this order
+__device__ __forceinline__ void lse_merge(float& M, float& S, float m2, float s2, float c) {
+    const float nm = fmaxf(M, m2), ref = lse_ref(nm);
+    S = S * __builtin_amdgcn_exp2f((M - ref) * c) + s2 * __builtin_amdgcn_exp2f((m2 - ref) * c);
+    M = nm;
+}
+
+// the wave's 64 rows of a tile merged into the states of the lane's two columns: the maximum of the lane's 32 values of a column, their
+// sum against it, one merge into the running state
+__device__ __forceinline__ void col_softmin(const f32x16 (&acc)[2][2], float c, float (&M)[2], float (&S)[2]) {
+#pragma unroll
+    for (int bj = 0; bj < 2; ++bj) {
+        float tm = -INFINITY;
+#pragma unroll
+        for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+            for (int g = 0; g < 16; ++g) tm = fmaxf(tm, acc[bi][bj][g]);
+        const float ref = lse_ref(tm);
+        float ts = 0.f;
+#pragma unroll
+        for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+            for (int g = 0; g < 16; ++g) ts += __builtin_amdgcn_exp2f((acc[bi][bj][g] - ref) * c);
+        lse_merge(M[bj], S[bj], tm, ts, c);
+    }
+}
+
+template <int DT>
+__global__ void __launch_bounds__(kThreads, 2) sinkhorn_cols_kernel(SoftminArgs p) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    float2* lx = reinterpret_cast<float2*>(lds + 2 * kOpBytes + 2 * kTile * 4);       // the wm = 1 waves' column states of a unit
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
+    const int cbase = wn * 64;
+    const int64_t G = gridDim.x, nslots = kad::launch_slots(p.cnt);
+
+    for (int64_t L = blockIdx.x; L < nslots; L += G) {
+        bool live;
+        const int64_t v = kad::slot_tile(L, p.cnt, &live);
+        if (!live) continue;                                                          // uniform over the workgroup
+        const int64_t u = p.u0 + v;
+        const kad::Unit un = kad::cross_unit(u, p.TI, p.TJ, p.rr);
+        float M[2] = {-INFINITY, -INFINITY}, S[2] = {0.f, 0.f};
+
+        for (int64_t I = un.I0; I < un.I1; ++I) {
+            f32x16 acc[2][2];
+            tile_mfma<DT>(p.a, p.b, p.ha, p.hb, p.pitch, p.nchunks, I, un.J, lds, [](int) {}, acc);
+            col_softmin(acc, p.c, M, S);
+        }
+
+        // a column: the lower lane half merged with the upper, then the wm = 0 wave with the wm = 1 wave, in this order
+#pragma unroll
+        for (int bj = 0; bj < 2; ++bj) {
+            const float om = __shfl_xor(M[bj], 32, 64), os = __shfl_xor(S[bj], 32, 64);
+            const bool lo = lane < 32;
+            float m1 = lo ? M[bj] : om, s1 = lo ? S[bj] : os;
+            lse_merge(m1, s1, lo ? om : M[bj], lo ? os : S[bj], p.c);
+            M[bj] = m1; S[bj] = s1;
+        }
+        if (wm == 1 && lane < 32) {
+#pragma unroll
+            for (int bj = 0; bj < 2; ++bj) lx[cbase + bj * 32 + lane] = make_float2(M[bj], S[bj]);
+        }
+        __syncthreads();
+        if (wm == 0 && lane < 32) {
+            float2* slot = p.slots + (u / p.TJ) * p.slot_pitch + un.J * kTile;
+#pragma unroll
+            for (int bj = 0; bj < 2; ++bj) {
+                const float2 o = lx[cbase + bj * 32 + lane];
+                lse_merge(M[bj], S[bj], o.x, o.y, p.c);
+                slot[cbase + bj * 32 + lane] = make_float2(M[bj], S[bj]);
+            }
+        }
+    }
+}
+
+constexpr size_t kLdsSoftmin = 2 * kOpBytes + 2 * kTile * 4 + kTile * sizeof(float2);
+
+// One thread per column: the nr row ranges' states merged in unit order, in float64, into the new potential
+//   pot[j] = -(M + eps ln S) + eps log(rows)      (= -eps (LSE_i((p_i - C_ij) / eps) - log rows))
+// kept in float64 for the outputs, and hp[j] = h[j] + (float)pot[j] for the next half-step, where these columns are the rows (-inf on
+// the padding columns; hp NULL: the diagnostic step, whose potential is not adopted).
+__global__ void __launch_bounds__(256) sinkhorn_reduce_kernel(const float2* __restrict__ slots, int64_t nr, int64_t pitch,
+                                                              const float* __restrict__ h, int64_t n_cols, int64_t n_pad, double c,
+                                                              double eps, double eps_log_rows, double* __restrict__ pot,
+                                                              float* __restrict__ hp) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= n_pad) return;
+    if (j >= n_cols) {
+        pot[j] = 0.0;
+        if (hp) hp[j] = -INFINITY;
+        return;
+    }
+    double M = -INFINITY, S = 0.0;
+    for (int64_t R = 0; R < nr; ++R) {
+        const float2 v = slots[R * pitch + j];
+        const double m2 = (double)v.x, nm = fmax(M, m2);
+        if (nm == -INFINITY) continue;                                                // nothing in either state yet
+        S = S * exp2((M - nm) * c) + (double)v.y * exp2((m2 - nm) * c);
+        M = nm;
+    }
+    const double f = -(M + eps * log(S)) + eps_log_rows;
+    pot[j] = f;
+    if (hp) hp[j] = h[j] + (float)f;
+}
+
+// One problem's sums, each in a fixed order: out[0] = sum f, out[1] = sum g, out[2] = sum_i |exp((f_i - f'_i) / eps) - 1|
+__global__ void __launch_bounds__(256) sinkhorn_finish_kernel(const double* __restrict__ f, const double* __restrict__ g,
+                                                              const double* __restrict__ f2, int64_t n, int64_t m, double inv_eps,
+                                                              double* __restrict__ out) {
+    __shared__ double red[3][256];
+    double sf = 0.0, sg = 0.0, se = 0.0;
+    for (int64_t i = threadIdx.x; i < n; i += 256) {
+        sf += f[i];
+        se += fabs(expm1((f[i] - f2[i]) * inv_eps));
+    }
+    for (int64_t j = threadIdx.x; j < m; j += 256) sg += g[j];
+    red[0][threadIdx.x] = sf; red[1][threadIdx.x] = sg; red[2][threadIdx.x] = se;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w)
+            for (int q = 0; q < 3; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x < 3) out[threadIdx.x] = red[threadIdx.x][0];
 }
 
 // ---------------------------------------------------------------------------------------- KAD standard errors
@@ -1855,11 +2004,12 @@ struct KadWorkspace {
     DevBuf perm_lab, perm_rows, perm_cols, perm;     // fad_kad_permutation_test: labellings, row and column words; slots and tables
     DevBuf near;                                     // fad_nearest: index, dist2, radii, nn radii, copied count; fad_nn_test: index, dist2, counts
     DevBuf kid_index, kid;                           // fad_kid_subsets: the two index lists; the bad-index count, sums and results
+    DevBuf sink_slots, sink;                         // fad_sinkhorn: the column states of a half-step; potentials and sums
     void release_all() {
         for (int i = 0; i < 2; ++i) { raw[i].release(); img[i].release(); h[i].release(); }
         slots.release(); small.release(); cross.release(); band.release(); songs.release(); lists.release(); prdc.release();
         unc_slots.release(); unc.release(); perm_lab.release(); perm_rows.release(); perm_cols.release(); perm.release();
-        near.release(); kid_index.release(); kid.release();
+        near.release(); kid_index.release(); kid.release(); sink_slots.release(); sink.release();
     }
 };
 
@@ -2665,6 +2815,45 @@ static KidArgs kid_args(const PassArgs& p, const KidParams& k) {
     return q;
 }
 
+// ------------------------------------------------------------------------------------------ Sinkhorn divergence
+// One direction of one problem: the rows of `rows` reduced into every column of `cols`.  Planned once (one call of kad::launches, so one
+// pass of fad_kad_last_plan's tally) and run at every iteration.
+struct SoftminPlan {
+    const Packed* rows; const Packed* cols;
+    int64_t TI, TJ, rr, NR;
+    std::vector<kad::Launch> launches;
+};
+
+static SoftminPlan softmin_plan(const Ctx& cx, const Packed& rows, const Packed& cols) {
+    SoftminPlan q;
+    q.rows = &rows; q.cols = &cols;
+    q.TI = kad::blocks(rows.n); q.TJ = kad::blocks(cols.n);
+    const int64_t per_launch = kad::tiles_per_launch_for(rows.pitch / (int64_t)dtype_size(cx.dtype), cx.dtype == FAD_F32, kad::kSoftminEpilogue);
+    q.rr = kad::cross_rows_per_unit(q.TI, q.TJ, per_launch);
+    q.NR = kad::cross_ranges(q.TI, q.rr);
+    q.launches = kad::launches(q.NR * q.TJ, std::max<int64_t>(1, per_launch / q.rr), grid_cap(cx.device));
+    return q;
+}
+
+// One half-step: pot[j] = -eps (LSE_i((p_i - C_ij) / eps) - log rows) for the columns j, hp_rows = h + p of the rows; hp_out (or NULL)
+// gets h + pot of the columns.  Enqueued only.
+static int softmin_pass(const Ctx& cx, const SoftminPlan& q, const float* hp_rows, float c, double eps, double* pot, float* hp_out) {
+    const int64_t cols_pad = q.TJ * kTile;
+    SoftminArgs p{};
+    p.a = q.rows->img; p.b = q.cols->img; p.ha = hp_rows; p.hb = q.cols->h;
+    p.pitch = q.rows->pitch; p.nchunks = q.rows->nchunks; p.c = c;
+    p.TI = q.TI; p.TJ = q.TJ; p.rr = q.rr;
+    p.slots = static_cast<float2*>(cx.ws->sink_slots.p); p.slot_pitch = cols_pad;
+    for (const kad::Launch& l : q.launches) {
+        p.u0 = l.u0; p.cnt = l.cnt;
+        FAD_TRY(with_dtype(cx.dtype, [&](auto dt) { sinkhorn_cols_kernel<dt><<<(unsigned)l.grid, kThreads, kLdsSoftmin, cx.st>>>(p); }));
+    }
+    sinkhorn_reduce_kernel<<<(unsigned)cdiv(cols_pad, 256), 256, 0, cx.st>>>(p.slots, q.NR, cols_pad, q.cols->h, q.cols->n, cols_pad, (double)c,
+                                                                             eps, eps * std::log((double)q.rows->n), pot, hp_out);
+    FAD_HIP_TRY(hipGetLastError());
+    return FAD_OK;
+}
+
 }  // namespace
 
 }  // namespace fad
@@ -3436,6 +3625,119 @@ int fad_kid_subsets(const void* x, int64_t n, int64_t ldx, const void* y, int64_
         for (int64_t q = 0; q < 3 * n_subsets; ++q) terms[q] = r[n_subsets + q];
     *mean = r[4 * n_subsets];
     *std_out = r[4 * n_subsets + 1];
+    return FAD_OK;
+}
+
+int fad_sinkhorn(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype, int on_device,
+                 double epsilon, int iterations, fad_sinkhorn_result_t* out, fad_sinkhorn_detail_t* detail, int device, void* stream) {
+    using namespace fad;
+    begin_entry();
+    const char* who = "fad_sinkhorn";
+    if (!out) return set_error(FAD_ERR_INVALID, "%s: NULL output", who);
+    if (!x || !y) return set_error(FAD_ERR_INVALID, "%s: NULL rows", who);
+    if (dtype == FAD_F64) return set_error(FAD_ERR_INVALID, "%s: float64 rows are not supported; cast to float32 (or float16 / bfloat16)", who);
+    if (dtype != FAD_F16 && dtype != FAD_BF16 && dtype != FAD_F32) return set_error(FAD_ERR_INVALID, "%s: unknown dtype %d", who, dtype);
+    if (d < 1 || d > 2048) return set_error(FAD_ERR_INVALID, "%s: D = %lld is outside 1 .. 2048", who, (long long)d);
+    if (ldx < d || ldy < d) return set_error(FAD_ERR_INVALID, "%s: row pitch %lld / %lld < D = %lld", who, (long long)ldx, (long long)ldy, (long long)d);
+    if (n < 1 || m < 1) return set_error(FAD_ERR_TOO_FEW_ROWS, "%s: needs at least 1 row per set, got %lld and %lld", who, (long long)n, (long long)m);
+    if (n > INT32_MAX - kTile || m > INT32_MAX - kTile)
+        return set_error(FAD_ERR_INVALID, "%s: %lld and %lld rows (at most %d per set)", who, (long long)n, (long long)m, INT32_MAX - kTile);
+    if (iterations < 1 || iterations > 100000) return set_error(FAD_ERR_INVALID, "%s: %d iterations, outside 1 .. 100000", who, iterations);
+    if (std::isnan(epsilon) || std::isinf(epsilon)) return set_error(FAD_ERR_INVALID, "%s: epsilon %g is not finite", who, epsilon);
+    const bool by_median = !(epsilon > 0);
+    if (by_median && n < 2)
+        return set_error(FAD_ERR_TOO_FEW_ROWS, "%s: the default epsilon is taken from the median pairwise distance of x, which needs 2 rows", who);
+    Ctx cx;
+    FAD_TRY(cx.open(dtype, FAD_KAD_GAUSSIAN, device, stream));
+    KadWorkspace& ws = *cx.ws;
+    const hipStream_t st = cx.st;
+
+    // each set packed once: the two images serve every iteration of all three problems
+    Packed px, py;
+    FAD_TRY(pack_set(cx, 0, x, n, ldx, d, on_device, &px));
+    FAD_TRY(pack_set(cx, 1, y, m, ldy, d, on_device, &py));
+    double eps = epsilon;
+    if (by_median) {
+        double median;
+        FAD_TRY(median_of_packed(cx, px, &median));
+        if (!(median > 0))
+            return set_error(FAD_ERR_INVALID, "%s: the median pairwise distance of x is %g, so there is no default epsilon -- are all rows of x "
+                             "identical?", who, median);
+        eps = (FAD_SINKHORN_BLUR_FACTOR * median) * (FAD_SINKHORN_BLUR_FACTOR * median);
+    }
+    const double cd = 1.4426950408889634 / eps;
+    const float c = (float)cd;
+    if (!(eps > 0) || !std::isfinite(eps) || !std::isfinite(c) || c == 0.f)
+        return set_error(FAD_ERR_INVALID, "%s: epsilon %g is outside the float32 range of the kernel", who, eps);
+
+    // problems: (x, y), (x, x), (y, y).  Per problem f, g and f' in float64 and h + f, h + g in float32; then 9 sums.
+    const Packed* A[3] = {&px, &px, &py};
+    const Packed* B[3] = {&py, &px, &py};
+    Carve cv;
+    Region<double> f_r[3], g_r[3], f2_r[3];
+    Region<float> hpf_r[3], hpg_r[3];
+    int64_t slots = 0;
+    for (int q = 0; q < 3; ++q) {
+        const int64_t a_pad = kad::blocks(A[q]->n) * kTile, b_pad = kad::blocks(B[q]->n) * kTile;
+        f_r[q] = cv.add<double>(a_pad); g_r[q] = cv.add<double>(b_pad); f2_r[q] = cv.add<double>(a_pad);
+        hpf_r[q] = cv.add<float>(a_pad); hpg_r[q] = cv.add<float>(b_pad);
+    }
+    const auto sums_r = cv.add<double>(9);
+    FAD_TRY(cv.reserve(ws.sink));
+    SoftminPlan plan_f[3], plan_g[3];
+    for (int q = 0; q < 3; ++q) {
+        plan_f[q] = softmin_plan(cx, *B[q], *A[q]);            // f: over the rows of B, for every row of A
+        plan_g[q] = softmin_plan(cx, *A[q], *B[q]);
+        slots = std::max({slots, plan_f[q].NR * plan_f[q].TJ * kTile, plan_g[q].NR * plan_g[q].TJ * kTile});
+    }
+    FAD_TRY(ws.sink_slots.reserve((size_t)slots * sizeof(float2)));
+
+    double* sums_d = cv.ptr(sums_r);
+    for (int q = 0; q < 3; ++q) {
+        double* f = cv.ptr(f_r[q]);
+        double* g = cv.ptr(g_r[q]);
+        double* f2 = cv.ptr(f2_r[q]);
+        float* hpf = cv.ptr(hpf_r[q]);
+        float* hpg = cv.ptr(hpg_r[q]);
+        for (int it = 0; it < iterations; ++it) {              // Gauss-Seidel from f = g = 0: g takes the new f
+            FAD_TRY(softmin_pass(cx, plan_f[q], it == 0 ? B[q]->h : hpg, c, eps, f, hpf));
+            FAD_TRY(softmin_pass(cx, plan_g[q], hpf, c, eps, g, hpg));
+        }
+        FAD_TRY(softmin_pass(cx, plan_f[q], hpg, c, eps, f2, nullptr));               // f', for the marginal error only
+        sinkhorn_finish_kernel<<<1, 256, 0, st>>>(f, g, f2, A[q]->n, B[q]->n, 1.0 / eps, sums_d + 3 * q);
+        FAD_HIP_TRY(hipGetLastError());
+    }
+    double sums[9];
+    FAD_HIP_TRY(hipMemcpyAsync(sums, sums_d, sizeof(sums), hipMemcpyDeviceToHost, st));
+    std::vector<double> fx, gx, fy, gy, fv, gv;
+    auto fetch = [&](std::vector<double>* v, Region<double> r, int64_t count) {
+        v->resize((size_t)count);
+        return hipMemcpyAsync(v->data(), cv.ptr(r), (size_t)count * sizeof(double), hipMemcpyDeviceToHost, st);
+    };
+    if (detail && (detail->f || detail->pot_x)) FAD_HIP_TRY(fetch(&fv, f_r[0], n));
+    if (detail && (detail->g || detail->pot_y)) FAD_HIP_TRY(fetch(&gv, g_r[0], m));
+    if (detail && detail->pot_x) { FAD_HIP_TRY(fetch(&fx, f_r[1], n)); FAD_HIP_TRY(fetch(&gx, g_r[1], n)); }
+    if (detail && detail->pot_y) { FAD_HIP_TRY(fetch(&fy, f_r[2], m)); FAD_HIP_TRY(fetch(&gy, g_r[2], m)); }
+    FAD_HIP_TRY(hipStreamSynchronize(st));
+    for (int q = 0; q < 9; ++q)
+        if (!std::isfinite(sums[q])) return set_error(FAD_ERR_NOT_FINITE, "%s: a potential is not finite (epsilon %g)", who, eps);
+
+    double ot[3], err[3];                                      // only now: a refusal above leaves the outputs as they were
+    for (int q = 0; q < 3; ++q) {
+        ot[q] = sums[3 * q] / (double)A[q]->n + sums[3 * q + 1] / (double)B[q]->n;
+        err[q] = sums[3 * q + 2] / (double)A[q]->n;
+    }
+    out->ot_xy = ot[0]; out->ot_xx = ot[1]; out->ot_yy = ot[2];
+    out->divergence = ot[0] - 0.5 * ot[1] - 0.5 * ot[2];
+    out->epsilon = eps;
+    out->marginal_error = err[0]; out->marginal_error_xx = err[1]; out->marginal_error_yy = err[2];
+    out->n = n; out->m = m; out->iterations = iterations;
+    if (detail) {
+        for (int64_t i = 0; detail->f && i < n; ++i) detail->f[i] = fv[(size_t)i];
+        for (int64_t j = 0; detail->g && j < m; ++j) detail->g[j] = gv[(size_t)j];
+        for (int64_t i = 0; detail->pot_x && i < n; ++i) detail->pot_x[i] = fv[(size_t)i] - 0.5 * (fx[(size_t)i] + gx[(size_t)i]);
+        for (int64_t j = 0; detail->pot_y && j < m; ++j) detail->pot_y[j] = gv[(size_t)j] - 0.5 * (fy[(size_t)j] + gy[(size_t)j]);
+    }
     return FAD_OK;
 }
 

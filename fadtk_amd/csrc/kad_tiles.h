@@ -103,12 +103,14 @@ inline std::vector<Launch> launches(int64_t total, int64_t per_launch, int64_t c
 // PRDC's passes weigh their own epilogues: kTopkEpilogue for the radius pass's per-column top-k (a compare and a
 // wave-uniform skip per pair, a 16-step insertion where a value enters), kFlagEpilogue for the cross pass's two threshold tests, counts
 // and ballots per pair.  fad_nearest's cross pass weighs kNearestEpilogue: the top-k of 64-bit keys, a permlane swap
-// per two pairs and a u64 compare per pair, six VALU ops per list entry where a key enters.
+// per two pairs and a u64 compare per pair, six VALU ops per list entry where a key enters.  The Sinkhorn half-step
+// weighs kSoftminEpilogue: a maximum, a subtraction, a multiply and an exponential per pair, against the sums' three instructions.
 // The budget of cost units per launch is a host-side value of the calling thread, 2^30 unless set_launch_budget changed it: kad.hip
 // sets it from FAD_KAD_LAUNCH_BUDGET at the start of every public entry (for tests: a small budget cuts a small pass into several
 // launches), the CPU cover programs set it directly.  The floor of 64 tiles per launch holds at any budget.  Host only, as is
 // everything that derives a launch size from it.
-constexpr int64_t kSumEpilogue = 128, kHistEpilogue = 2048, kTopkEpilogue = 1024, kFlagEpilogue = 512, kNearestEpilogue = 1536;
+constexpr int64_t kSumEpilogue = 128, kHistEpilogue = 2048, kTopkEpilogue = 1024, kFlagEpilogue = 512, kNearestEpilogue = 1536,
+                  kSoftminEpilogue = 192;
 constexpr int64_t kLaunchBudget = (int64_t)1 << 30;
 inline int64_t& launch_budget_value() {
     static thread_local int64_t v = kLaunchBudget;

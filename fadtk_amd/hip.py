@@ -1185,3 +1185,43 @@ def kid_subsets(x, y, index_x, index_y, degree: int = 3, gamma: Optional[float] 
     K.check(lib.fad_kid_subsets(px, n, ldx, py, m, ldy, d, code, on_dev, degree, g, c, pix, piy, S, s, dev_i, mmd2.ctypes.data,
                                 terms.ctypes.data, C.byref(mean), C.byref(std), int(device), K.current_stream_ptr(device)), "fad_kid_subsets")
     return {"mmd2": mmd2[:S], "terms": terms[:S], "mean": float(mean.value), "std": float(std.value), "subsets": S, "subset_size": s}
+
+
+# ------------------------------------------------------------------------ Sinkhorn divergence between the two sets of rows
+SINKHORN_MAX_ITERATIONS = 100000
+
+
+def sinkhorn_params(epsilon=None, iterations=100):
+    """-> (epsilon, iterations) as the C ABI takes them: epsilon None -> 0 (the library's default from x's median distance) else a finite
+    value > 0, iterations an integer in 1 .. 100000.  Anything else is a ValueError, raised before the native library is touched."""
+    e = 0.0 if epsilon is None else float(epsilon)
+    if epsilon is not None and not (e > 0 and np.isfinite(e)):
+        raise ValueError(f"Sinkhorn: epsilon must be finite and > 0 (None: from the median distance of x), got {epsilon}")
+    if isinstance(iterations, bool) or int(iterations) != iterations or not 1 <= int(iterations) <= SINKHORN_MAX_ITERATIONS:
+        raise ValueError(f"Sinkhorn: iterations must be an integer in 1 .. {SINKHORN_MAX_ITERATIONS}, got {iterations!r}")
+    return e, int(iterations)
+
+
+def sinkhorn(x, y, epsilon: Optional[float] = None, iterations: int = 100, device: int = 0, potentials: bool = False) -> dict:
+    """``fad_sinkhorn``: the debiased Sinkhorn divergence between the rows of x (baseline) and y with the cost |a - b|^2 / 2 -> dict of
+    fad_sinkhorn_result (divergence, ot_xy, ot_xx, ot_yy, epsilon as used, marginal_error, marginal_error_xx, marginal_error_yy, n, m,
+    iterations).  ``epsilon=None``: (0.25 x the median pairwise distance of x)^2.  ``potentials=True`` adds the float64 arrays ``f`` [n]
+    and ``g`` [m] (the dual potentials of the x-y problem) and ``pot_x`` [n], ``pot_y`` [m] (the debiased ones: divergence =
+    mean(pot_x) + mean(pot_y)).  Both sets are numpy arrays or both torch CUDA tensors of one dtype (float16 / bfloat16 / float32)."""
+    e, iterations = sinkhorn_params(epsilon, iterations)
+    lib = K.load_library()
+    (px, n, d, ldx, cx, dev_x, kx), (py, m, dy, ldy, cy, dev_y, ky) = _kad_pair(x, y, "y", device)
+    if d != dy:
+        raise ValueError(f"Sinkhorn: x has D = {d}, y has D = {dy}")
+    if cx != cy:
+        raise ValueError("Sinkhorn: x and y must have the same dtype")
+    res = K.FadSinkhornResult()
+    det, arrays = None, {}
+    if potentials:
+        arrays = {"f": np.zeros(n), "g": np.zeros(m), "pot_x": np.zeros(n), "pot_y": np.zeros(m)}
+        det = K.FadSinkhornDetail(*(a.ctypes.data for a in arrays.values()))
+    K.check(lib.fad_sinkhorn(px, n, ldx, py, m, ldy, d, cx, dev_x, e, iterations, C.byref(res), C.byref(det) if det is not None else None,
+                             int(device), K.current_stream_ptr(device)), "fad_sinkhorn")
+    out = res.as_dict()
+    out.update(arrays)
+    return out

@@ -594,6 +594,50 @@ int fad_kid_subsets(const void* x, int64_t n, int64_t ldx, const void* y, int64_
                     double* mmd2 /* [n_subsets] host */, double* terms /* [n_subsets][3]: kxx, kyy, kxy means; may be NULL */,
                     double* mean, double* std /* population, ddof = 0; 0 for one subset */, int device, void* stream);
 
+/* ------------------------------------------------------------------ Sinkhorn divergence between the two sets of rows
+ * Not in the reference.  The debiased entropic transport cost between the empirical measures of x [n x d] and y [m x d] (uniform
+ * weights 1 / n and 1 / m; Genevay et al. 2018, Feydy et al. 2019), cost C_ij = |x_i - y_j|^2 / 2, regularisation epsilon > 0:
+ * non-negative, zero only for equal measures, -> W_2^2 / 2 as epsilon -> 0 and -> |mean x - mean y|^2 / 2 as epsilon -> infinity.
+ * One problem OT_eps(x, y) starts from f = 0 [n], g = 0 [m] and runs `iterations` times, in this order (g takes the new f),
+ *   f_i <- -eps (LSE_j((g_j - C_ij) / eps) - log m)        g_j <- -eps (LSE_i((f_i - C_ij) / eps) - log n)
+ * and its value is mean(f) + mean(g) (after a g step the column marginal holds exactly, so the dual has no correction term).
+ *   divergence = ot_xy - ot_xx / 2 - ot_yy / 2       the self problems run the same iteration on (x, x) and (y, y), i = j included
+ *   marginal_error = mean_i |exp((f_i - f'_i) / eps) - 1|, f' one more f step that is not adopted: the L1 error of the row marginal
+ *                    (marginal_error_xx / _yy: the self problems').  The count is fixed: no early stop; a large value means more
+ *                    iterations or a larger epsilon are needed.
+ *   detail (may be NULL; each array NULL or host float64): f [n] and g [m] of the (x, y) problem, and the debiased potentials
+ *     pot_x[i] = f_i - (f^xx_i + g^xx_i) / 2,  pot_y[j] = g_j - (f^yy_j + g^yy_j) / 2, so that divergence = mean(pot_x) + mean(pot_y):
+ *     the mean of pot_y over a song's rows, times its share of the rows, is what that song adds to the divergence.
+ * epsilon <= 0 takes (FAD_SINKHORN_BLUR_FACTOR x fad_kad_median_distance(x))^2 (needs n >= 2; a median of 0 -> FAD_ERR_INVALID); the
+ * result reports the epsilon used.  Every half-step is one pass of fad_kad_individual's cross kernel over the n x m pair rectangle with
+ * a (max, sum of exponentials) epilogue per column, the row potential added to the rows' -|row|^2 / 2: dot products on the matrix cores
+ * into float32, the cost matrix never stored, both sets packed once for all iterations of the three problems, potentials kept in
+ * float32 between steps and merged in float64, every merge in a fixed order: the same bits on every run, and divergence == 0 exactly
+ * for sets of identical bits.  C is formed in float32 from norms and dot products as KAD's d^2 is, so a potential carries an error of
+ * about 2^-24 (|x|^2 + |y|^2): rows far from the origin lose digits (centre them first).
+ * Rows are float16 / bfloat16 / float32; FAD_F64 -> FAD_ERR_INVALID (cast).  d outside 1 .. 2048, a row pitch < d, iterations outside
+ * 1 .. 100000, an epsilon that is NaN / Inf or outside float32, a NULL out -> FAD_ERR_INVALID; n or m < 1 -> FAD_ERR_TOO_FEW_ROWS; a
+ * NaN/Inf row norm -> FAD_ERR_NOT_FINITE.  Argument errors come before any device call; any refusal leaves every output untouched.
+ * Workspace: the two images; per problem 20 bytes per row of its first set and 12 per row of its second (f, f', g and the two float32
+ * vectors); 8 bytes per column and row range of the largest pass.  Synchronises `stream`. */
+#define FAD_SINKHORN_BLUR_FACTOR 0.25
+typedef struct fad_sinkhorn_result {
+    double divergence, ot_xy, ot_xx, ot_yy;
+    double epsilon;
+    double marginal_error, marginal_error_xx, marginal_error_yy;
+    int64_t n, m;
+    int iterations;
+} fad_sinkhorn_result_t;
+typedef struct fad_sinkhorn_detail {
+    double* f;        /* [n] */
+    double* g;        /* [m] */
+    double* pot_x;    /* [n] */
+    double* pot_y;    /* [m] */
+} fad_sinkhorn_detail_t;
+int fad_sinkhorn(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype, int on_device,
+                 double epsilon, int iterations, fad_sinkhorn_result_t* out, fad_sinkhorn_detail_t* detail /* may be NULL */,
+                 int device, void* stream);
+
 /* ------------------------------------------------------------------ diagnostics (NOT part of the drop-in surface)
  * Nothing in fadtk corresponds to these two calls and no binding of the reference needs them: they exist for bench.py's
  * roofline object (HIP events around the tile kernel on the stream it is launched on) and for the GPU tests that check
@@ -615,8 +659,8 @@ int fad_moments_set_timing(fad_moments_t* h, int enabled);
 int fad_moments_last_timing(fad_moments_t* h, float* ms_main_kernel, float* ms_reduce_kernel,
                             int* kernel_variant);
 
-/* Diagnostic: how the last KAD-family call of this thread (fad_kad*, fad_prdc, fad_nearest, fad_nn_test, fad_kid*) cut its passes into
- * launches.  out = { passes planned, launches planned, fewest launches of one pass, most launches of one pass, most slots one
+/* Diagnostic: how the last KAD-family call of this thread (fad_kad*, fad_prdc, fad_nearest, fad_nn_test, fad_kid*, fad_sinkhorn) cut its passes into
+ * launches (fad_sinkhorn plans each direction of each problem once, 6 passes, and runs that plan at every iteration).  out = { passes planned, launches planned, fewest launches of one pass, most launches of one pass, most slots one
  * workgroup of a launch walks }; all 0 when the call was refused before it planned a pass.  A pass is one walk of a pair space (the
  * median's three histogram rounds share one plan and count once; every word group of a permutation pass is one).  The environment
  * variable FAD_KAD_LAUNCH_BUDGET (cost units per launch, default 2^30, read at the start of every such call; a launch never holds
