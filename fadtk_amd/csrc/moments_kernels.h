@@ -8,6 +8,7 @@
 namespace fad {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -112,6 +113,17 @@ template <int KIND> __device__ __forceinline__ f32x16 mfma_h16(const uint4& a, c
     } else {
         bf16x8 va, vb; __builtin_memcpy(&va, &a, 16); __builtin_memcpy(&vb, &b, 16);
         return __builtin_amdgcn_mfma_f32_32x32x16_bf16(va, vb, c, 0, 0, 0);
+    }
+}
+
+// 16 x 16 x 32: lane l holds column l & 15 and the eight k 8 (l >> 4) .. + 7 of both operands, rows 4 (l >> 4) .. + 3 of column l & 15 of c
+template <int KIND> __device__ __forceinline__ f32x4 mfma16_h16(const uint4& a, const uint4& b, const f32x4& c) {
+    if constexpr (KIND == FAD_F16) {
+        f16x8 va, vb; __builtin_memcpy(&va, &a, 16); __builtin_memcpy(&vb, &b, 16);
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(va, vb, c, 0, 0, 0);
+    } else {
+        bf16x8 va, vb; __builtin_memcpy(&va, &a, 16); __builtin_memcpy(&vb, &b, 16);
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(va, vb, c, 0, 0, 0);
     }
 }
 

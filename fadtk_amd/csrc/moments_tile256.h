@@ -2,29 +2,35 @@
 // (whose small device helpers it uses); the block bookkeeping is in tile256_roles.h.
 //
 // A workgroup of 8 waves owns a CU, streams TWO 256-column slabs of 32 rows per stage (32 KiB, ring of T2_NST stages) and issues
-// 136 MFMAs on them (128 for a plain tile).  Round 6 rewrote the stage loop and the stage layout (rounds 4-5: HISTORY.md):
+// the 136 blocks of 32 x 32 on them (128 for a plain tile), each as four v_mfma_f32_16x16x32 on 16 x 16 sub-blocks -- the one below
+// the diagonal of a diagonal block is not issued.  Round 6 rewrote the stage loop and the stage layout (rounds 4-5: HISTORY.md):
 //
 //   * stage layout [32 rows][slab A 256 columns | slab B 256 columns]: one LDS row = 1 KiB = ONE LDS-DMA piece
 //     (global_load_lds_dwordx4, SGPR base + lane offset).  For a P / Q item the two slabs are adjacent in memory, so a piece is
 //     1 KiB of one frame row, contiguous (scripts/probes/r6_limits.hip: the P + Q pair of an XCD streams 5.45 TB/s with such pieces
-//     against 4.56 with pieces of 4 rows x 256 B).  The XOR swizzle of the 16-byte chunks -- chunk ^ 4 (row & 3) -- is applied on
-//     the SOURCE side (the DMA writes lane-linear): four lane-offset registers, one per row residue;
-//   * fragments: ds_read_b64_tr_b16, two per fragment and 16-row k-step;
-//   * FREE-RUNNING waves, ONE barrier per stage.  Every wave runs the same software pipeline -- while it multiplies the fragments of
-//     one k-step it reads the next k-step's and issues its share of the refill between the MFMAs -- and the two waves of a SIMD are
-//     NOT phase-locked any more (rounds 4-5 ran the two wave quartets half a stage apart, two barriers per stage).  The barrier sits
-//     between the two k-steps of a stage: behind it the next stage is in LDS for everybody and the slot of the stage before may be
+//     against 4.56 with pieces of 4 rows x 256 B).  The XOR swizzle of the 16-byte chunks -- chunk ^ 2 (row & 3) ^ 8 ((row >> 3) & 1),
+//     derived in tile256_layout.h -- is applied on the SOURCE side (the DMA writes lane-linear): four lane-offset registers, one per
+//     piece (the term in row >> 3 is wave-uniform);
+//   * fragments: a fragment of 32 columns is two sub-fragments of 16 columns x 32 rows (the 16x16x32 operand: a lane holds eight
+//     rows of one column); ds_read_b64_tr_b16, two per sub-fragment = four per fragment and stage;
+//   * FREE-RUNNING waves, ONE barrier per stage.  Every wave runs the same software pipeline -- the products of a stage go low x low,
+//     low x high and high x low, high x high halves of the fragments; the high halves are read under the first quarter, the next
+//     stage's low halves under the last, the wave's share of the refill is issued between the MFMAs -- and the two waves of a SIMD
+//     are NOT phase-locked any more (rounds 4-5 ran the two wave quartets half a stage apart, two barriers per stage).  The barrier
+//     sits behind the first quarter: behind it the next stage is in LDS for everybody and the slot of the stage before may be
 //     refilled (see the loop).  What bounds the kernel is the package's power budget: it runs at the 1400 W cap;
 //   * every wave has a compile-time ROLE (tile256_roles.h): the loop it runs updates a fixed set of accumulators (9 blocks = 144
-//     registers, or 8);
+//     registers as 36 f32x4, or 8);
 //   * column sums (and sum x^2 for the shift guard) ride on the two waves per superblock that read fragments 0..3 / 4..7 anyway
 //     (v_dot2c_f32_f16 against (1, 1) resp. against itself);
-//   * epilogue: a wave stores its blocks fragment-major (1 KiB per store instruction) at slot 9 wave + b of the item.
+//   * epilogue: a wave stores its blocks sub-block by sub-block (1 KiB per store instruction) at slot 9 wave + b of the item; the
+//     element map of a slot is in tile256_layout.h, shared with moments_reduce256.
 //
 // SHIFT = the shift guard's second pass (see tile_h16_tr_body): rows enter as the error-free pair x - c = x' + e.
 #pragma once
 #include "moments_kernels.h"
 #include "tile256_roles.h"
+#include "tile256_layout.h"
 
 namespace fad {
 
@@ -35,6 +41,7 @@ constexpr int T2_KB = 32;                   // rows per slab and stage
 constexpr int T2_NST = T2_NST_VALUE;        // ring depth (scripts/probes/tile256_bench.hip builds variants)
 constexpr int T2_ROW = 1024;                // bytes per LDS row of a stage: 256 columns of slab A, then 256 of slab B
 constexpr int T2_STAGE = T2_KB * T2_ROW;    // 32 KiB
+static_assert(T2_KB == t256::STAGE_ROWS && T2_ROW == t256::ROW_BYTES, "tile256_layout.h describes this stage");
 constexpr size_t kT256Lds = (size_t)T2_NST * T2_STAGE;      // 128 KiB
 
 struct T256Set {
@@ -72,7 +79,8 @@ __device__ __forceinline__ uint4 t2_frag(uint32_t lds_byte) {
     return f;
 }
 
-// x - c = x' + e (packed TwoSum, float16); rows past the end of the run (loaded as zeros) stay zero
+// x - c = x' + e (packed TwoSum, float16) on a lane's eight rows of a stage (t256::lane_row0 on); `rows_left` counts the rows of the
+// run from the first of them: rows past the end of the run (loaded as zeros) stay zero
 __device__ __forceinline__ void t2_split2(const uint4& f, uint32_t c2, int64_t rows_left, uint4& xs, uint4& es) {
     typedef _Float16 h2 __attribute__((ext_vector_type(2)));
     uint32_t w[4] = {f.x, f.y, f.z, f.w}, x[4], e[4];
@@ -121,8 +129,8 @@ __device__ __forceinline__ void tile256_wave(
     const int my_rowoff = two_rows ? T2_KB * quartet : 0;                        // rows of a stage this wave's fragments come from
 
     // ---- loads.  Piece p of wave w = LDS row 4 w + p of the stage, fetched by ONE buffer_load_dwordx4 ... lds.  The DMA writes
-    // lane-linear (lane l -> bytes 16 l .. 16 l + 15 of the row), so lane l FETCHES chunk l ^ 4 p of the row (p = row & 3: the
-    // swizzle): chunks 0..31 are slab A's columns, 32..63 slab B's (its frame row 32 further down for a Z item).
+    // lane-linear (lane l -> bytes 16 l .. 16 l + 15 of the row), so lane l FETCHES chunk l ^ swizzle(row) of the row
+    // (t256::dma_chunk): chunks 0..31 are slab A's columns, 32..63 slab B's (its frame row 32 further down for a Z item).
     // The buffer resource covers exactly this split's rows [k_begin, k_end) -- base = row k_begin, num_records = the bytes up to the
     // end of row k_end - 1 -- and the hardware's range check does the edges: a lane whose offset falls behind the last row reads
     // ZEROS (rows of a last, partial stage; whole stages a short split never had), and a lane whose COLUMN is not below d (ragged
@@ -144,7 +152,7 @@ __device__ __forceinline__ void tile256_wave(
     bool lane_in_b[LPS];
 #pragma unroll
     for (int p = 0; p < LPS; ++p) {
-        const int c = lane ^ (p << 2);
+        const int c = t256::dma_chunk(wave, p, lane);
         const bool in_b = c >= 32;
         lane_in_b[p] = in_b;
         const int col = in_b ? colB + (c - 32) * 8 : colA + c * 8;                         // d % 8 == 0: a chunk is in or out as a whole
@@ -179,8 +187,10 @@ __device__ __forceinline__ void tile256_wave(
         if (kb >= NSTG - 1) return;
 #endif
         uint32_t vo;
-        if constexpr (IDX) vo = voff[p] + ((two_rows && lane_in_b[p]) ? r.ro2[p] : r.ro[p]);
-        else vo = voff[p] + r.ro[p];
+        if constexpr (IDX) {                 // either term may be the marker 2^31: the sum must stay out of range, not wrap to 0
+            const uint32_t ro = (two_rows && lane_in_b[p]) ? r.ro2[p] : r.ro[p];
+            vo = ((voff[p] | ro) & 0x80000000u) ? 0x80000000u : voff[p] + ro;
+        } else vo = voff[p] + r.ro[p];
         const uint32_t m0v = wave_lds + (uint32_t)((kb % NSTG) * T2_STAGE + p * T2_ROW);
         // (`nt`, the streaming hint, on these loads: 214 against 218 us per 8-matrix launch in the back-to-back harness at the power cap, nothing in
         //  bench.py's loop -- 11 350-11 670 scores/s against 11 650-11 850 -- FETCH_SIZE + 0.2 %: not used.  `lds` has to be the LAST modifier: the
@@ -198,9 +208,11 @@ __device__ __forceinline__ void tile256_wave(
     };
     const int nwhole = (int)((k_end - k_begin) / rows_per_stage);                        // stages [0, nwhole) have all their rows
 
-    // ---- fragments: byte offset inside a stage of F[i] for k-step 0 (k-step 1: + 16 rows)
+    // ---- fragments.  F[i] is read as two sub-fragments of 16 columns, the operands of the 16x16x32 MFMA (tile256_layout.h): a lane
+    // holds column 16 s + t16 and rows 8 grp .. 8 grp + 7 of the stage.  foff[i] = this lane's address inside a stage for the first
+    // transposed read of sub-fragment 0 of F[i] (the second read: + 4 rows, same swizzle; sub-fragment 1: the next chunk pair, which
+    // the swizzle turns into ^ 32 bytes -- one v_xor_b32 per read instead of six more address registers).
     const int t16 = lane & 15, grp = lane >> 4;
-    const int tr_row = 8 * (grp >> 1) + (t16 >> 2), tr_col = 16 * (grp & 1) + 4 * (t16 & 3);
     auto frag_of = [&](int i, bool& from_a) -> int {        // F[i]: which slab, and the fragment's index in its superblock
         if constexpr (ROLE == t256::XR) {
             from_a = i < 4;
@@ -210,90 +222,154 @@ __device__ __forceinline__ void tile256_wave(
             return RD::frag[i];
         }
     };
-    auto fcol = [&](int i) -> int {                          // global column of this lane's element of F[i] (column sums, shifts)
+    auto fcol = [&](int i, int c32) -> int {                 // global column of column c32 (0..31) of F[i] (column sums, shifts)
         bool from_a; const int f = frag_of(i, from_a);
-        return (from_a ? colA : colB) + 32 * f + li;
+        return (from_a ? colA : colB) + 32 * f + c32;
     };
     uint32_t foff[NF];
+    static_assert((t256::tr_read_byte(5, 0, 16) ^ t256::tr_read_byte(5, 0, 0)) == 32 && (t256::tr_read_byte(62, 1, 48) ^ t256::tr_read_byte(62, 1, 32)) == 32,
+                  "sub-fragment 1 = sub-fragment 0 ^ 32 bytes");
 #pragma unroll
     for (int i = 0; i < NF; ++i) {
         bool from_a; const int f = frag_of(i, from_a);
-        const int col = (from_a ? 0 : t256::SB) + 32 * f + tr_col;               // column inside the 512-column LDS row
-        foff[i] = (uint32_t)(tr_row * T2_ROW + (((col >> 3) ^ ((tr_row & 3) << 2)) << 4) + ((col >> 2) & 1) * 8);
+        foff[i] = (uint32_t)t256::tr_read_byte(lane, 0, (from_a ? 0 : t256::SB) + 32 * f);
     }
-    uint32_t cs[NF];                         // SHIFT: this lane's shift per fragment, packed twice
+    uint32_t cs[NF][2];                      // SHIFT: this lane's shift per sub-fragment, packed twice
 #pragma unroll
-    for (int i = 0; i < NF; ++i) cs[i] = 0u;
+    for (int i = 0; i < NF; ++i) cs[i][0] = cs[i][1] = 0u;
     if constexpr (SHIFT) {
         const uint16_t* cv = s.cvec + (int64_t)split * (L.nsb * t256::SB);
 #pragma unroll
-        for (int i = 0; i < NF; ++i) { const uint32_t h = cv[fcol(i)]; cs[i] = h | (h << 16); }
+        for (int i = 0; i < NF; ++i)
+#pragma unroll
+            for (int sf = 0; sf < 2; ++sf) { const uint32_t h = cv[fcol(i, 16 * sf + t16)]; cs[i][sf] = h | (h << 16); }
     }
-    auto rows_left_at = [&](int kb, int ks) -> int64_t {
-        return k_end - (k_begin + (int64_t)kb * rows_per_stage + my_rowoff + ks * 16 + 8 * kg);
+    auto rows_left_at = [&](int kb) -> int64_t {            // rows of the run from the first of this lane's eight rows of stage kb on
+        return k_end - (k_begin + (int64_t)kb * rows_per_stage + my_rowoff + t256::lane_row0(lane));
     };
 
-    f32x16 acc[NB];
+    // block b = four 16 x 16 sub-blocks (si, sj) at acc[b][2 si + sj]; sub-block (1, 0) of a diagonal block is never issued
+    f32x4 acc[NB][4];
 #pragma unroll
     for (int b = 0; b < NB; ++b)
 #pragma unroll
-        for (int q = 0; q < 16; ++q) acc[b][q] = 0.f;
+        for (int q = 0; q < 4; ++q) acc[b][q] = f32x4{0.f, 0.f, 0.f, 0.f};
     // column sums (and sum x^2 for the guard): every triangle-family wave takes TWO of its fragments -- superblock fragments
     // 0,1 (TRI_LO), 2,3 (RECT_D), 4,5 (RECT_C), 6,7 (TRI_HI) -- so that no wave carries more than 2 x 2 x 9 VALU ops per stage
     constexpr bool CSUM = ROLE != t256::XR;
     constexpr int CS0 = (ROLE == t256::TRI_HI || ROLE == t256::RECT_C) ? 2 : 0;          // F[CS0], F[CS0 + 1]
-    double csum[2] = {0.0, 0.0};
+    double csum[2][2] = {{0.0, 0.0}, {0.0, 0.0}};        // [fragment][sub-fragment]
 
-    uint4 F0[NF], F1[NF];                    // the fragments of k-step 0 / 1 (F1 of stage k is read while F0 is multiplied, F0 of stage k + 1 while F1 is)
-    auto load_half = [&](int kb, int ks, uint4 (&F)[NF]) {
+    // The low / high 16 columns of every fragment, all 32 rows of a stage.  The products of a stage run F0 x F0, then F0 x F1 and
+    // F1 x F0, then F1 x F1: F1 of stage k is read under the first quarter, F0 of stage k + 1 under the last.
+    uint4 F0[NF], F1[NF];
+    auto load_sub = [&](int kb, int sf, uint4 (&F)[NF]) {
 #ifdef T2_ABL_NOREAD                         // ablation (scripts/probes/tile256_bench.hip): no transpose reads
         if (kb > 0) return;
 #endif
-        const uint32_t base = smem_lds + (uint32_t)((kb % NSTG) * T2_STAGE + ks * 16 * T2_ROW);
+        const uint32_t base = smem_lds + (uint32_t)((kb % NSTG) * T2_STAGE);
 #pragma unroll
-        for (int i = 0; i < NF; ++i) F[i] = t2_frag(base + foff[i]);
+        for (int i = 0; i < NF; ++i) F[i] = t2_frag(base + (foff[i] ^ (uint32_t)(sf << 5)));
     };
-    // The MFMAs of one k-step; `refill`: this wave's LDS-DMA pieces 2 ks, 2 ks + 1 of stage kb + NSTG - 1 go BETWEEN them.
-    auto half = [&](int kb, int ks, const uint4 (&F)[NF], auto refill, const StageRows& rr) {
-        constexpr int PH = LPS / 2;          // pieces per k-step: behind MFMA 1, 3
-        if constexpr (SHIFT) {               // x - c = x' + e
-            if (decltype(refill)::value) { piece(kb + NSTG - 1, PH * ks, rr); piece(kb + NSTG - 1, PH * ks + 1, rr); }
-            const bool full = kb < nwhole;
-            uint4 X[NF], R[NF];
+    // this wave's LDS-DMA piece p of stage kb + NSTG - 1 goes BETWEEN the MFMAs
+    auto refill_piece = [&](auto refill, int kb, int p, const StageRows& rr) {
+        if constexpr (decltype(refill)::value) {
+            __builtin_amdgcn_sched_barrier(0); piece(kb + NSTG - 1, p, rr); __builtin_amdgcn_sched_barrier(0);
+        }
+    };
+    constexpr int P_FIRST = SHIFT ? 2 : 1;   // pieces issued in the first quarter (the rest behind the barrier)
+    // The shifted pass holds x' and e of both halves in the middle quarters (96 registers beside the 144 accumulators): it reads a half only
+    // when the quarter before it is through, so that the spills stay in the middle quarters (it runs for flagged sets only).
+    constexpr bool EARLY_READS = !SHIFT;
+    uint4 X0[NF], R0[NF], X1[NF], R1[NF];    // SHIFT: x - c = x' + e of F0 / F1
+    // three terms per sub-block of the shifted pass: (x'_a + e_a)^T (x'_b + e_b) without e^T e
+    auto mma3 = [&](f32x4& c, const uint4& xa, const uint4& ra, const uint4& xb, const uint4& rb) {
+        c = mfma16_h16<KIND>(xa, xb, c);
+        c = mfma16_h16<KIND>(xa, rb, c);
+        c = mfma16_h16<KIND>(ra, xb, c);
+    };
+    auto split_sub = [&](int kb, int sf, const uint4 (&F)[NF], uint4 (&X)[NF], uint4 (&R)[NF]) {
+        const int64_t left = kb < nwhole ? 8 : rows_left_at(kb);
 #pragma unroll
-            for (int i = 0; i < NF; ++i) t2_split2(F[i], cs[i], full ? 8 : rows_left_at(kb, ks), X[i], R[i]);
+        for (int i = 0; i < NF; ++i) t2_split2(F[i], cs[i][sf], left, X[i], R[i]);
+    };
+    // first quarter: sub-blocks (0, 0)
+    auto quarter_first = [&](int kb, auto refill, const StageRows& rr) {
+        if constexpr (SHIFT) {
+            refill_piece(refill, kb, 0, rr); refill_piece(refill, kb, 1, rr);
+            split_sub(kb, 0, F0, X0, R0);
 #pragma unroll
-            for (int b = 0; b < NB; ++b) {
-                acc[b] = mfma_h16<KIND>(X[RD::fa[b]], X[RD::fb[b]], acc[b]);
-                acc[b] = mfma_h16<KIND>(X[RD::fa[b]], R[RD::fb[b]], acc[b]);
-                acc[b] = mfma_h16<KIND>(R[RD::fa[b]], X[RD::fb[b]], acc[b]);
-            }
-            if constexpr (CSUM) {
-#pragma unroll
-                for (int i = 0; i < 2; ++i) csum[i] += (double)sum8<KIND>(X[CS0 + i]) + (double)sum8<KIND>(R[CS0 + i]);
-            }
+            for (int b = 0; b < NB; ++b) mma3(acc[b][0], X0[RD::fa[b]], R0[RD::fa[b]], X0[RD::fb[b]], R0[RD::fb[b]]);
             return;
         }
 #ifdef T2_ABL_NOMMA                          // ablation: no MFMAs (the fragments stay live through a cheap VALU use)
 #pragma unroll
-        for (int i = 0; i < NF; ++i) acc[0][i] += __uint_as_float((F[i].x ^ F[i].y ^ F[i].z ^ F[i].w) & 0x007fffffu);
-        if (decltype(refill)::value) { piece(kb + NSTG - 1, PH * ks, rr); piece(kb + NSTG - 1, PH * ks + 1, rr); }
+        for (int i = 0; i < NF; ++i) acc[0][0][i & 3] += __uint_as_float((F0[i].x ^ F0[i].y ^ F0[i].z ^ F0[i].w) & 0x007fffffu);
+        refill_piece(refill, kb, 0, rr);
         return;
 #endif
 #pragma unroll
         for (int b = 0; b < NB; ++b) {
-            acc[b] = mfma_h16<KIND>(F[RD::fa[b]], F[RD::fb[b]], acc[b]);
-            if (decltype(refill)::value && (b & 1) && (b >> 1) < PH) {
-                __builtin_amdgcn_sched_barrier(0); piece(kb + NSTG - 1, PH * ks + (b >> 1), rr); __builtin_amdgcn_sched_barrier(0);
+            acc[b][0] = mfma16_h16<KIND>(F0[RD::fa[b]], F0[RD::fb[b]], acc[b][0]);
+            if (b == 3) refill_piece(refill, kb, 0, rr);
+        }
+    };
+    // the two middle quarters: sub-blocks (0, 1) and, off the diagonal, (1, 0); the column sums ride here, where F0 and F1 are live
+    auto quarter_mid = [&](int kb, auto refill, const StageRows& rr) {
+        if constexpr (SHIFT) {
+            refill_piece(refill, kb, 2, rr); refill_piece(refill, kb, 3, rr);
+            split_sub(kb, 1, F1, X1, R1);
+#pragma unroll
+            for (int b = 0; b < NB; ++b) {
+                mma3(acc[b][1], X0[RD::fa[b]], R0[RD::fa[b]], X1[RD::fb[b]], R1[RD::fb[b]]);
+                if (t256::sub_block_issued(RD::fa[b] == RD::fb[b], 1, 0)) mma3(acc[b][2], X1[RD::fa[b]], R1[RD::fa[b]], X0[RD::fb[b]], R0[RD::fb[b]]);
             }
-#ifndef T2_OPT_NOCOLSUM
             if constexpr (CSUM) {
-                if (b == 4 || b == 6) {      // the column sums of one fragment each, among the later MFMAs
-                    const int i = (b - 4) >> 1;
-                    csum[i] += (double)sum8<KIND>(F[CS0 + i]);
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    csum[i][0] += (double)sum8<KIND>(X0[CS0 + i]) + (double)sum8<KIND>(R0[CS0 + i]);
+                    csum[i][1] += (double)sum8<KIND>(X1[CS0 + i]) + (double)sum8<KIND>(R1[CS0 + i]);
                 }
             }
+            return;
+        }
+#ifdef T2_ABL_NOMMA
+#pragma unroll
+        for (int i = 0; i < NF; ++i) acc[0][1][i & 3] += __uint_as_float((F1[i].x ^ F1[i].y ^ F1[i].z ^ F1[i].w) & 0x007fffffu);
+        refill_piece(refill, kb, 1, rr); refill_piece(refill, kb, 2, rr);
+        return;
 #endif
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            acc[b][1] = mfma16_h16<KIND>(F0[RD::fa[b]], F1[RD::fb[b]], acc[b][1]);
+            if (t256::sub_block_issued(RD::fa[b] == RD::fb[b], 1, 0)) acc[b][2] = mfma16_h16<KIND>(F1[RD::fa[b]], F0[RD::fb[b]], acc[b][2]);
+            if (b == 1) refill_piece(refill, kb, 1, rr);
+            if (b == 5) refill_piece(refill, kb, 2, rr);
+#ifndef T2_OPT_NOCOLSUM
+            if constexpr (CSUM) {            // the column sums of one sub-fragment each, among the later MFMAs
+                if (b == 2) csum[0][0] += (double)sum8<KIND>(F0[CS0]);
+                if (b == 3) csum[0][1] += (double)sum8<KIND>(F1[CS0]);
+                if (b == 6) csum[1][0] += (double)sum8<KIND>(F0[CS0 + 1]);
+                if (b == 7) csum[1][1] += (double)sum8<KIND>(F1[CS0 + 1]);
+            }
+#endif
+        }
+    };
+    // last quarter: sub-blocks (1, 1)
+    auto quarter_last = [&](int kb, auto refill, const StageRows& rr) {
+        if constexpr (SHIFT) {
+#pragma unroll
+            for (int b = 0; b < NB; ++b) mma3(acc[b][3], X1[RD::fa[b]], R1[RD::fa[b]], X1[RD::fb[b]], R1[RD::fb[b]]);
+            return;
+        }
+#ifdef T2_ABL_NOMMA
+        refill_piece(refill, kb, 3, rr);
+        return;
+#endif
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            acc[b][3] = mfma16_h16<KIND>(F1[RD::fa[b]], F1[RD::fb[b]], acc[b][3]);
+            if (b == 3) refill_piece(refill, kb, 3, rr);
         }
     };
     // this wave's pieces of stage `kb + 1` have landed once at most (stages issued beyond it) x LPS of its loads are outstanding
@@ -303,59 +379,73 @@ __device__ __forceinline__ void tile256_wave(
     };
     static_assert(NSTG <= 8 && NSTG >= 3, "wait_vmcnt_upto counts at most seven stages");
 
-    // ---- the loop.  Barrier B(k + 1) sits between the two k-steps of stage k.  A wave arrives there with (a) its reads of stage k
+    // ---- the loop.  Barrier B(k + 1) sits behind the first quarter of stage k.  A wave arrives there with (a) its reads of stage k
     // complete (F1 came back: lgkmcnt(0)) and (b) its own pieces of stage k + 1 landed (counted vmcnt).  Hence behind B(k + 1): stage
-    // k + 1 may be read by everybody; and the slot of stage k may be refilled -- which is what iteration k + 1 does with the pieces of
-    // stage k + NSTG (same slot), all of them issued behind B(k + 1).
+    // k + 1 may be read by everybody -- F0 under the last quarter of stage k, F1 under the first of stage k + 1; and the slot of stage
+    // k may be refilled -- which is what iteration k + 1 does with the pieces of stage k + NSTG (same slot), all of them issued behind
+    // B(k + 1).
     for (int s0 = 0; s0 < NSTG - 1 && s0 < nkb; ++s0) issue(s0);
     wait_vmcnt_upto<LPS>(((nkb < NSTG - 1) ? nkb : NSTG - 1) - 1);                    // stages issued beyond stage 0
     t2_phase_barrier();
-    load_half(0, 0, F0);
+    load_sub(0, 0, F0);
     const int hot = nkb - (NSTG - 1) > 0 ? nkb - (NSTG - 1) : 0;                      // stages behind which a refill is due
     int kb = 0;
     // (static priority for waves 4..7 and the next k-step's reads spread one per MFMA were measured -- within the +-3 % of the harness,
     //  profiles/r06b_tile256_variants.txt -- and are not in the code)
     for (; kb < hot; ++kb) {                 // no branches: the refill rides between the MFMAs
-        const StageRows rr = rows_of_stage(kb + NSTG - 1);     // (IDX: four scalar loads, in flight while the k-step's reads are issued)
-        load_half(kb, 1, F1);
+        const StageRows rr = rows_of_stage(kb + NSTG - 1);     // (IDX: four scalar loads, in flight while the reads are issued)
+        if constexpr (!EARLY_READS) __builtin_amdgcn_sched_barrier(0); else load_sub(kb, 1, F1);
         __builtin_amdgcn_sched_barrier(0);
-        half(kb, 0, F0, std::true_type{}, rr);
+        quarter_first(kb, std::true_type{}, rr);
         __builtin_amdgcn_sched_barrier(0);
-        // in flight at this point: stages kb + 1 .. kb + NSTG - 2 and half of kb + NSTG - 1; kb + 1 must have landed
-        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(LPS * (NSTG - 3) + LPS / 2) : "memory");
+        if constexpr (!EARLY_READS) load_sub(kb, 1, F1);
+        // in flight at this point: stages kb + 1 .. kb + NSTG - 2 and the first pieces of kb + NSTG - 1; kb + 1 must have landed
+        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(LPS * (NSTG - 3) + P_FIRST) : "memory");
         t2_phase_barrier();
-        load_half(kb + 1, 0, F0);
+        quarter_mid(kb, std::true_type{}, rr);
         __builtin_amdgcn_sched_barrier(0);
-        half(kb, 1, F1, std::true_type{}, rr);
+        if constexpr (EARLY_READS) load_sub(kb + 1, 0, F0);
         __builtin_amdgcn_sched_barrier(0);
+        quarter_last(kb, std::true_type{}, rr);
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (!EARLY_READS) { load_sub(kb + 1, 0, F0); __builtin_amdgcn_sched_barrier(0); }
     }
     const StageRows none = rows_of_stage(0);
     for (; kb < nkb; ++kb) {                 // the last NSTG - 1 stages: nothing left to fetch
-        load_half(kb, 1, F1);
+        if constexpr (EARLY_READS) load_sub(kb, 1, F1);
         __builtin_amdgcn_sched_barrier(0);
-        half(kb, 0, F0, std::false_type{}, none);
+        quarter_first(kb, std::false_type{}, none);
         __builtin_amdgcn_sched_barrier(0);
+        if constexpr (!EARLY_READS) load_sub(kb, 1, F1);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         const bool more = kb + 1 < nkb;
         if (more) {
             wait_next(kb);
             t2_phase_barrier();
-            load_half(kb + 1, 0, F0);
+        }
+        quarter_mid(kb, std::false_type{}, none);
+        __builtin_amdgcn_sched_barrier(0);
+        if (EARLY_READS && more) {
+            load_sub(kb + 1, 0, F0);
             __builtin_amdgcn_sched_barrier(0);
         }
-        half(kb, 1, F1, std::false_type{}, none);
+        quarter_last(kb, std::false_type{}, none);
         __builtin_amdgcn_sched_barrier(0);
+        if (!EARLY_READS && more) {
+            load_sub(kb + 1, 0, F0);
+            __builtin_amdgcn_sched_barrier(0);
+        }
     }
 
-    // ---- epilogue: blocks, fragment major -- float4 (q, lane) of block b = registers 4q..4q+3 = rows 8q + 4 (lane >> 5) + 0..3
-    // of column lane & 31
+    // ---- epilogue: a block's slot is 256 float4 -- float4 64 (2 si + sj) + lane = this lane's accumulator of sub-block (si, sj)
+    // (t256::slot_float4; rows and column: slot_row0, slot_col).  1 KiB per store instruction.
     {
         float4* out = reinterpret_cast<float4*>(s.partials + ((int64_t)split * L.NT + ti) * t256::ITEM_STRIDE) + (size_t)(9 * wave) * 256;
 #pragma unroll
         for (int b = 0; b < NB; ++b)
 #pragma unroll
             for (int q = 0; q < 4; ++q)
-                out[(b * 4 + q) * 64 + lane] = make_float4(acc[b][4 * q], acc[b][4 * q + 1], acc[b][4 * q + 2], acc[b][4 * q + 3]);
+                out[b * 256 + t256::slot_float4(q >> 1, q & 1, lane)] = make_float4(acc[b][q][0], acc[b][q][1], acc[b][q][2], acc[b][q][3]);
     }
 
     // ---- shift guard, first pass: sum x^2 of a column is the DIAGONAL of its 32 x 32 diagonal block -- it sits in the accumulators
@@ -370,14 +460,17 @@ __device__ __forceinline__ void tile256_wave(
             if constexpr (CSUM) {
 #pragma unroll
                 for (int b = 0; b < NB; ++b) {
-                    if (RD::fa[b] != RD::fb[b]) continue;                  // (a diagonal block: element (c, c) is register 4 (c >> 3) + (c & 3) of lane 32 ((c >> 2) & 1) + c)
-                    float v = 0.f;
-#pragma unroll
-                    for (int q = 0; q < 4; ++q)
+                    if (RD::fa[b] != RD::fb[b]) continue;
+                    // a diagonal block: lane diag_lane(c) holds element (c, c) in component diag_comp(c) of sub-block (c >> 4, c >> 4);
+                    // the lanes with grp == t16 >> 2 hold c = t16 and c = 16 + t16
+                    if (t256::diag_lane(t16) == lane) {
+                        float v0 = 0.f, v1 = 0.f;
 #pragma unroll
                         for (int j = 0; j < 4; ++j)
-                            if ((li >> 3) == q && (li & 3) == j) v = acc[b][4 * q + j];
-                    if (kg == ((li >> 2) & 1)) dsq[32 * RD::frag[RD::fa[b]] + li] = v;
+                            if (t256::diag_comp(t16) == j) { v0 = acc[b][0][j]; v1 = acc[b][3][j]; }
+                        dsq[32 * RD::frag[RD::fa[b]] + t16] = v0;
+                        dsq[32 * RD::frag[RD::fa[b]] + 16 + t16] = v1;
+                    }
                 }
             }
             __syncthreads();
@@ -401,8 +494,10 @@ __device__ __forceinline__ void tile256_wave(
         bool hit = false;
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            const int col = fcol(CS0 + i);
-            double sx = csum[i];
+            // lane l ends with the sum of column l & 31: its own sub-fragment's sum over the four 16-lane groups (8 rows each)
+            const int col = fcol(CS0 + i, li);
+            const bool hi16 = (lane & 16) != 0;
+            double sx = (hi16 ? csum[i][1] : csum[i][0]) + __shfl_xor(hi16 ? csum[i][0] : csum[i][1], 16);
             sx += __shfl_xor(sx, 32);
             if (kg == 0) cp[col] = sx;
             if constexpr (!SHIFT) {
@@ -460,8 +555,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(112))) void mom
 }
 
 // ------------------------------------------------------------------------------------------
-// partial blocks -> packed float64 accumulator.  One thread = one float4 (4 adjacent ROWS of one column) of one 32 x 32
-// output block, for every SL-th row-split; the SL partial sums meet in LDS in a fixed order (deterministic).
+// partial blocks -> packed float64 accumulator.  One thread = one float4 (4 adjacent ROWS of one column: tile256_layout.h) of one
+// 32 x 32 output block, for every SL-th row-split; the SL partial sums meet in LDS in a fixed order (deterministic).
 // ------------------------------------------------------------------------------------------
 struct R256Job {
     const float* partials; const double* colpart; const uint16_t* cvec;
@@ -560,7 +655,7 @@ __global__ __launch_bounds__(256) void moments_reduce256(R256Launch R) {
             }
         }
         if (unshift) {                        // + c_a s'_b + s'_a c_b + n c_a c_b, split by split (see reduce_body)
-            const int ga = 32 * bi + 8 * (e >> 6) + 4 * ((e & 63) >> 5), gb = 32 * bj + (e & 31);
+            const int ga = 32 * bi + t256::slot_row0(e), gb = 32 * bj + t256::slot_col(e);
             const bool two_a = (R.two_mask >> (ga / t256::SB)) & 1u, two_b = (R.two_mask >> (gb / t256::SB)) & 1u;
             for (int sp = sl; sp < S; sp += SL) {
                 const double nq = rows_of(sp);
@@ -594,7 +689,7 @@ __global__ __launch_bounds__(256) void moments_reduce256(R256Launch R) {
 #endif
     double* M = j.acc + 1 + R.d;
     const int d = R.d;
-    const int a0 = 32 * bi + 8 * (e >> 6) + 4 * ((e & 63) >> 5), b = 32 * bj + (e & 31);
+    const int a0 = 32 * bi + t256::slot_row0(e), b = 32 * bj + t256::slot_col(e);
     if (b >= d) return;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {

@@ -2,6 +2,8 @@
 // (2 x [100000 x 512] float16, three pairs rotated: every launch streams from HBM), built in several variants by -D flags:
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 [-DT2_OPT_KS_READS] [-DT2_OPT_NOCOLSUM] [-DT2_NST_VALUE=3] -o /tmp/t256b scripts/probes/tile256_bench.hip
 // Prints the average kernel / reduce duration (HIP events) and a checksum of the accumulators.
+// A/B against an earlier kernel (the 32x32x16 arithmetic before the change of MFMA shape, say): build this file in a checkout of that commit -- the
+// stage image and the slot layout changed with the arithmetic, a -D switch would have to carry both -- and run the two binaries in turn (profiles/tile256_shape_ab.txt).
 #include "../../fadtk_amd/csrc/moments_tile256.h"
 #include <cstdio>
 #include <cstdlib>
