@@ -77,6 +77,104 @@ def test_bf16_rounding_is_round_to_nearest_even():
     assert np.array_equal(SR.round_to(a, "bf16"), np.array([1.0, 1.0, 1.015625, 1.0078125, -1.0, 1.0078125], np.float32))
 
 
+# --------------------------------------------------------------------------- the references of the edge tests (no GPU)
+def _rel(got, want):
+    """the worst difference of the compared quantities, relative to the size of the potentials"""
+    scale = max(float(np.abs(want[k]).max()) for k in SR.POTS)
+    keys = SR.POTS + SR.TERMS + ("marginal_error", "marginal_error_xx", "marginal_error_yy")
+    return max(float(np.abs(np.asarray(got[k]) - np.asarray(want[k])).max()) for k in keys) / scale
+
+
+@pytest.mark.parametrize("block", (77, 128))
+def test_blocked_float64_equals_the_dense_reference(block):
+    """neither block size divides 300 or 200: a ragged last block in both directions of all three problems"""
+    x, y = SR.rows(300, 200, 37, "fp32")
+    eps = (0.25 * SR.median_distance(x)) ** 2
+    want = SR.sinkhorn(x, y, eps, 5)
+    got = SR.sinkhorn_blocked(x, y, eps, 5, "cpu", block=block)
+    assert set(got) == set(want) and got["f"].shape == (300,) and got["pot_y"].shape == (200,)
+    assert _rel(got, want) <= 1e-12
+
+
+@pytest.mark.parametrize("dt,L", (("fp16", 2), ("bf16", 2), ("fp32", 2), ("fp32", 30)))
+def test_chain32_is_within_one_unit_of_float64_at_the_default_blur(dt, L):
+    """f, g, F, G, the three OT terms and S -- what the GPU tests compare.  f and g of the self problems are not compared one by one:
+    the diagonal pair dominates there, so f_i - g_i is nearly free and drifts with L while f + g does not."""
+    x, y = SR.rows(129, 127, 128, dt)
+    eps = (0.25 * SR.median_distance(x)) ** 2
+    want, got = SR.sinkhorn(x, y, eps, L), SR.sinkhorn_chain32(x, y, eps, L, dt)
+    r = SR.ratios(got, want, SR.unit(x, y, eps))
+    assert max(r.values()) <= 1.0, r
+    assert 0.0 < max(r.values()), "the emulation is float32: it cannot equal float64"
+    assert abs(got["marginal_error"] - want["marginal_error"]) <= 1e-4 * (1.0 + want["marginal_error"])
+
+
+@pytest.mark.parametrize("dt", SR.DTYPES)
+def test_chain32_gives_exactly_zero_for_identical_sets(dt):
+    x, _ = SR.rows(129, 127, 128, dt)
+    got = SR.sinkhorn_chain32(x, x.copy(), 3.0, 3, dt)
+    assert got["divergence"] == 0.0 and got["ot_xy"] == got["ot_xx"] == got["ot_yy"]
+
+
+def test_chain32_over_several_row_blocks_per_unit(monkeypatch):
+    """The emulation's own unit loop (rr = 2, a ragged last range) against rr = 1 on the same rows: another merge order, the same
+    soft-min within float32."""
+    x, y = SR.rows(300, 200, 37, "fp32")
+    eps = (0.25 * SR.median_distance(x)) ** 2
+    one = SR.sinkhorn_chain32(x, y, eps, 2, "fp32")
+    monkeypatch.setattr(SR, "CROSS_UNITS", 4)                                      # 3 x 2 blocks: rr = 2 for the 3, 1 for the 2
+    assert SR.cross_plan(300, 200)[2:] == (2, 2) and SR.cross_plan(200, 300)[2:] == (1, 2)
+    two = SR.sinkhorn_chain32(x, y, eps, 2, "fp32")
+    r = SR.ratios(two, one, SR.unit(x, y, eps))
+    assert max(r.values()) <= 1.0, r
+
+
+def test_cross_plan_of_the_large_case_walks_two_row_blocks_per_unit():
+    """kad::cross_rows_per_unit: nr = ceil(8192 / TJ) ranges at most, rr = ceil(TI / nr).  rr = 2 needs TI > ceil(8192 / TJ): 92 x 92
+    blocks (n = m >= 11 649) is the smallest square shape.  11 800 x 11 700 is 93 x 92 blocks."""
+    TI, TJ, rr, NR = SR.cross_plan(11800, 11700)
+    assert (TI, TJ, rr, NR) == (93, 92, 2, 47) and TI - (NR - 1) * rr == 1         # the last range is a single block
+    TI, TJ, rr, NR = SR.cross_plan(11700, 11800)
+    assert (TI, TJ, rr, NR) == (92, 93, 2, 46) and TI - (NR - 1) * rr == 2
+    assert SR.cross_plan(11648, 11648)[2] == 1 and SR.cross_plan(11649, 11649)[2] == 2
+    assert SR.cross_plan(11800, 11700, depth=64, f32=True)[2] == 2                 # the default budget does not bind here
+    assert SR.cross_plan(1200, 1100) == (10, 9, 1, 10)                             # the largest shape of test_gpu_sinkhorn.py: never
+    assert SR.cross_plan(1, 300) == (1, 3, 1, 1) and SR.cross_plan(100000, 100000)[2] == 72
+
+
+def test_cross_plan_restates_the_header():
+    """the constants it restates, read from the headers"""
+    import re
+    song = (ROOT / "fadtk_amd" / "csrc" / "kad_song_tiles.h").read_text()
+    tiles = (ROOT / "fadtk_amd" / "csrc" / "kad_tiles.h").read_text()
+    assert int(re.search(r"kCrossUnits = (\d+);", song).group(1)) == SR.CROSS_UNITS
+    assert int(re.search(r"kSoftminEpilogue = (\d+);", tiles).group(1)) == SR.SOFTMIN_EPILOGUE
+    assert "kLaunchBudget = (int64_t)1 << 30;" in tiles and SR.LAUNCH_BUDGET == 1 << 30
+    assert "int64_t rr = (TI + nr - 1) / nr;" in song and "I0 + rr < TI ? I0 + rr : TI" in song
+
+
+def test_a_translated_copy_at_a_large_blur():
+    """y = x + t, t a power of two so that it stays exact: S -> |t|^2 / 2 as the blur grows (the distance of the means), and the two self
+    problems are the same problem.  Translation invariance is what a bug in the offset cases would break."""
+    x, _ = SR.rows(129, 127, 16, "fp32")
+    x = np.round(x * 8.0) / 8.0
+    y = x + np.float32(2.0)
+    assert np.array_equal(y - np.float32(2.0), x)
+    r = SR.sinkhorn(x, y, (1000.0 * SR.median_distance(x)) ** 2, 5)
+    assert abs(r["divergence"] - 0.5 * 16 * 4.0) <= 1e-4 * 32.0
+    assert abs(r["ot_xx"] - r["ot_yy"]) <= 1e-12 * abs(r["ot_xx"])
+    near = SR.sinkhorn(x, y, (0.25 * SR.median_distance(x)) ** 2, 30)              # and at the default blur: the same self problems
+    assert abs(near["ot_xx"] - near["ot_yy"]) <= 1e-12 * abs(near["ot_xx"])
+
+
+def test_edge_rows_round_after_the_addition():
+    x0, y0 = SR.rows(129, 127, 128, "bf16")
+    x, y = SR.edge_rows(129, 127, 128, "bf16", off=16.0, sep=2.0)
+    assert np.array_equal(x, SR.round_to(x0 + np.float32(16), "bf16")) and np.array_equal(y, SR.round_to(y0 + np.float32(18), "bf16"))
+    assert np.array_equal(SR.round_to(x, "bf16"), x) and not np.array_equal(x - np.float32(16), x0)
+    assert np.array_equal(SR.edge_rows(129, 127, 128, "fp16")[0], SR.rows(129, 127, 128, "fp16")[0])       # no offset: rows() itself
+
+
 # ------------------------------------------------------------------------------------------------------------ surface
 def test_prototype_and_structures():
     from fadtk_amd import _capi
