@@ -104,6 +104,18 @@ class FadSinkhornDetail(C.Structure):
     _fields_ = [("f", C.c_void_p), ("g", C.c_void_p), ("pot_x", C.c_void_p), ("pot_y", C.c_void_p)]
 
 
+class FadSlicedResult(C.Structure):
+    _fields_ = [("sw2_squared", C.c_double), ("std_error", C.c_double), ("max_sliced", C.c_double), ("max_index", C.c_int64),
+                ("n", C.c_int64), ("m", C.c_int64), ("projections", C.c_int)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class FadSlicedDetail(C.Structure):
+    _fields_ = [("values", C.c_void_p), ("sorted_x", C.c_void_p), ("sorted_y", C.c_void_p)]
+
+
 _P = C.c_void_p
 _I64 = C.c_int64
 # name -> (restype, argtypes)     -- one entry per declaration in include/fad_hip.h
@@ -189,6 +201,9 @@ SIGNATURES = {
                           C.c_int, _P]),
     "fad_kid_subsets": (C.c_int, [_P, _I64, _I64, _P, _I64, _I64, _I64, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _P, _P, _I64, _I64,
                                   C.c_int, _P, _P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, _P]),
+    "fad_sliced_wasserstein": (C.c_int, [_P, _I64, _I64, _P, _I64, _I64, _I64, C.c_int, C.c_int, _P, C.c_int, C.POINTER(FadSlicedResult),
+                                         C.POINTER(FadSlicedDetail), C.c_int, _P]),
+    "fad_sliced_last_plan": (C.c_int, [C.POINTER(_I64)]),
     "fad_sinkhorn": (C.c_int, [_P, _I64, _I64, _P, _I64, _I64, _I64, C.c_int, C.c_int, C.c_double, C.c_int, C.POINTER(FadSinkhornResult),
                                C.POINTER(FadSinkhornDetail), C.c_int, _P]),
 }

@@ -3,7 +3,7 @@
 // KAD's standard errors (4.9), its permutation test (4.10), the nearest baseline rows with authenticity (4.11), KAD at several
 // bandwidths in one pass (4.12), the permutation test at several bandwidths, aggregated (4.13), the leave-one-out k-NN two-sample
 // test on the pooled rows (4.14), the polynomial-kernel distance of the KID protocol (4.15) and the Sinkhorn divergence (4.16) run on
-// the same main loop.
+// the same main loop; the sliced Wasserstein distance (4.17) takes its projections from it.
 //
 // Every pass is one GEMM-shaped walk over 128 x 128 tiles of a pair space (kad_tiles.h) whose n x m matrix is never stored:
 //   - pack:   each set is copied once into a zero-padded [n_pad x dp] image of its own dtype (dp: D rounded up to 128 bytes, n_pad:
@@ -27,6 +27,7 @@
 #include "kad_perm_sweep_tiles.h"
 #include "kid_tiles.h"
 #include "nn_vote.h"
+#include "sliced_sort.h"
 
 #include <algorithm>
 #include <cmath>
@@ -720,6 +721,97 @@ __global__ void __launch_bounds__(256) sinkhorn_finish_kernel(const double* __re
         __syncthreads();
     }
     if (threadIdx.x < 3) out[threadIdx.x] = red[threadIdx.x][0];
+}
+
+// ------------------------------------------------------------------------------------- sliced Wasserstein distance
+// The projection pass: P[l, i] = theta_l . x_i for the directions of one chunk, direction-major (a direction's n values are contiguous,
+// the segment the sort takes).  tile_mfma with the directions' image as the row operand and the set's image as the column operand, so
+// that a wave's 32 lanes of one accumulator element store 32 consecutive floats; both h vectors are one vector of zeros.  The image of
+// the directions has kTile rows of zeros after the last direction, so a chunk may start at any direction: its tiles read on into the
+// next chunk's rows or into the zeros, and only l < lc and i < n are stored -- no padding row or column reaches the sort.  A value that
+// is not finite sets *flag (every writer stores the same word).
+struct ProjArgs {
+    const char* th; const char* rows;          // the chunk's first direction in the directions' image; the set's image
+    const float* zeros;
+    int64_t pitch;
+    int nchunks;
+    int64_t TI, TJ;                            // direction blocks of the chunk, row blocks of the set
+    int64_t lc, n;
+    float* P; int64_t ppitch;
+    unsigned int* flag;
+};
+
+template <int DT>
+__global__ void __launch_bounds__(kThreads, 2) sliced_project_kernel(ProjArgs p) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
+    const int64_t total = p.TI * p.TJ;
+    bool bad = false;
+    for (int64_t t = blockIdx.x; t < total; t += gridDim.x) {
+        const int64_t I = t / p.TJ, J = t % p.TJ;
+        f32x16 acc[2][2];
+        tile_mfma<DT>(p.th, p.rows, p.zeros, p.zeros, p.pitch, p.nchunks, I, J, lds, [](int) {}, acc);
+#pragma unroll
+        for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+            for (int bj = 0; bj < 2; ++bj) {
+                const int64_t i = J * kTile + wn * 64 + bj * 32 + (lane & 31);
+#pragma unroll
+                for (int g = 0; g < 16; ++g) {
+                    const int64_t l = I * kTile + wm * 64 + bi * 32 + (g & 3) + 8 * (g >> 2) + 4 * (lane >> 5);
+                    const float v = acc[bi][bj][g];
+                    if (l < p.lc && i < p.n) {
+                        p.P[l * p.ppitch + i] = v;
+                        bad |= !(fabsf(v) < INFINITY);
+                    }
+                }
+            }
+    }
+    if (bad) *p.flag = 1u;
+}
+
+constexpr size_t kLdsProject = 2 * kOpBytes + 2 * kTile * 4;
+constexpr int kMatchBlock = 256;
+
+// The quantile match of one chunk: workgroup (direction l, block k) takes the elements i in [256 k, 256 k + 256) of the sorted larger
+// set a [na] and, for each, the elements j0 .. j1 of the sorted smaller set b [nb] whose quantile interval [j nb', (j + 1) nb') meets
+// [i, i + 1) na' (in units of 1 / (na nb)): the overlap w is an exact integer, the term w * (a_i - b_j)^2 is float64 (difference, square
+// and product each rounded once: contraction into a fused multiply-add is switched off), summed over j ascending per element, then by the workgroup's halving tree, one
+// slot per workgroup.
+__global__ void __launch_bounds__(kMatchBlock) sliced_match_kernel(const float* __restrict__ a, int64_t pa, int64_t na,
+                                                                   const float* __restrict__ b, int64_t pb, int64_t nb, int64_t nblk,
+                                                                   double* __restrict__ slots) {
+#pragma clang fp contract(off)
+    __shared__ double red[kMatchBlock];
+    const int64_t l = blockIdx.x / nblk, k = blockIdx.x % nblk, i = k * kMatchBlock + threadIdx.x;
+    double s = 0.0;
+    if (i < na) {
+        const double ai = (double)a[l * pa + i];
+        const int64_t lo = i * nb, hi = lo + nb, j0 = lo / na, j1 = (hi - 1) / na;
+        for (int64_t j = j0; j <= j1 && j < nb; ++j) {
+            const int64_t w = (hi < (j + 1) * na ? hi : (j + 1) * na) - (lo > j * na ? lo : j * na);
+            const double diff = ai - (double)b[l * pb + j];
+            const double sq = diff * diff;
+            const double term = (double)w * sq;
+            s += term;
+        }
+    }
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = kMatchBlock / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) slots[blockIdx.x] = red[0];
+}
+
+// S[l] = the nblk slots of direction l summed in index order, one thread per direction of the chunk
+__global__ void __launch_bounds__(256) sliced_finish_kernel(const double* __restrict__ slots, int64_t nblk, int64_t lc, double* __restrict__ S) {
+    const int64_t l = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (l >= lc) return;
+    double s = 0.0;
+    for (int64_t k = 0; k < nblk; ++k) s += slots[l * nblk + k];
+    S[l] = s;
 }
 
 // ---------------------------------------------------------------------------------------- KAD standard errors
@@ -2005,11 +2097,13 @@ struct KadWorkspace {
     DevBuf near;                                     // fad_nearest: index, dist2, radii, nn radii, copied count; fad_nn_test: index, dist2, counts
     DevBuf kid_index, kid;                           // fad_kid_subsets: the two index lists; the bad-index count, sums and results
     DevBuf sink_slots, sink;                         // fad_sinkhorn: the column states of a half-step; potentials and sums
+    DevBuf sliced_theta, sliced;                     // fad_sliced_wasserstein: the directions' image; projections, sort scratch and sums
     void release_all() {
         for (int i = 0; i < 2; ++i) { raw[i].release(); img[i].release(); h[i].release(); }
         slots.release(); small.release(); cross.release(); band.release(); songs.release(); lists.release(); prdc.release();
         unc_slots.release(); unc.release(); perm_lab.release(); perm_rows.release(); perm_cols.release(); perm.release();
         near.release(); kid_index.release(); kid.release(); sink_slots.release(); sink.release();
+        sliced_theta.release(); sliced.release();
     }
 };
 
@@ -2851,6 +2945,62 @@ static int softmin_pass(const Ctx& cx, const SoftminPlan& q, const float* hp_row
     sinkhorn_reduce_kernel<<<(unsigned)cdiv(cols_pad, 256), 256, 0, cx.st>>>(p.slots, q.NR, cols_pad, q.cols->h, q.cols->n, cols_pad, (double)c,
                                                                              eps, eps * std::log((double)q.rows->n), pot, hp_out);
     FAD_HIP_TRY(hipGetLastError());
+    return FAD_OK;
+}
+
+// ------------------------------------------------------------------------------------- sliced Wasserstein distance
+// A float32 direction entry rounded to the rows' dtype, round to nearest even, as the bits the image holds (16-bit dtypes: in the low
+// half) and as the value they stand for.  Finite in; a float16 / bfloat16 result may be infinite (the caller refuses it through q).
+static uint32_t round_direction(float f, int dtype, double* value) {
+    uint32_t x;
+    memcpy(&x, &f, 4);
+    if (dtype == FAD_F32) { *value = (double)f; return x; }
+    if (dtype == FAD_BF16) {
+        const uint32_t h = (x + 0x7fffu + ((x >> 16) & 1u)) >> 16, back = h << 16;
+        float v;
+        memcpy(&v, &back, 4);
+        *value = (double)v;
+        return h;
+    }
+    const uint32_t sign = (x >> 16) & 0x8000u, mag = x & 0x7fffffffu;
+    uint32_t h;
+    if (mag < 0x38800000u) {                               // below 2^-14: a multiple of 2^-24, rounded by the float32 unit itself
+        float a;
+        memcpy(&a, &mag, 4);
+        h = (uint32_t)std::nearbyint(a * 16777216.0f);     // exact product; nearbyint rounds to even; 1024 is the smallest normal
+    } else {
+        const uint32_t r = (mag + 0xfffu + ((mag >> 13) & 1u)) >> 13;
+        h = r - (112u << 10);
+        if (h > 0x7c00u) h = 0x7c00u;                      // 65520 and above round to infinity
+    }
+    const uint32_t e = h >> 10, man = h & 0x3ffu;
+    float a;
+    if (e == 0) {
+        a = (float)man * 5.9604644775390625e-8f;           // 2^-24
+    } else {
+        const uint32_t back = e == 31 ? 0x7f800000u : ((e + 112u) << 23) | (man << 13);
+        memcpy(&a, &back, 4);
+    }
+    *value = sign ? -(double)a : (double)a;
+    return sign | h;
+}
+
+constexpr int64_t kSlicedWorkspace = (int64_t)1 << 30;     // bytes of chunked buffers by default (FAD_SLICED_WORKSPACE)
+struct SlicedPlan { int64_t chunks, lc, passes, share; };
+static SlicedPlan& sliced_plan_value() {
+    static thread_local SlicedPlan p{0, 0, 0, 0};
+    return p;
+}
+
+// One set's side of a chunk: projections of lc directions from direction l0 on, then the segmented sort.  Enqueued only.
+static int sliced_project_sort(const Ctx& cx, const Packed& set, const char* theta, const float* zeros, int64_t l0, int64_t lc, float* P,
+                               int64_t ppitch, float* tmp, uint32_t* counts, uint32_t* bases, unsigned int* flag) {
+    ProjArgs p{};
+    p.th = theta + l0 * set.pitch; p.rows = set.img; p.zeros = zeros; p.pitch = set.pitch; p.nchunks = set.nchunks;
+    p.TI = kad::blocks(lc); p.TJ = kad::blocks(set.n); p.lc = lc; p.n = set.n; p.P = P; p.ppitch = ppitch; p.flag = flag;
+    const unsigned int grid = (unsigned int)std::min<int64_t>(p.TI * p.TJ, grid_cap(cx.device));
+    FAD_TRY(with_dtype(cx.dtype, [&](auto dt) { sliced_project_kernel<dt><<<grid, kThreads, kLdsProject, cx.st>>>(p); }));
+    FAD_HIP_TRY(ssort::sort_segments(P, tmp, ppitch, set.n, lc, counts, bases, cx.st));
     return FAD_OK;
 }
 
@@ -3738,6 +3888,155 @@ int fad_sinkhorn(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m
         for (int64_t i = 0; detail->pot_x && i < n; ++i) detail->pot_x[i] = fv[(size_t)i] - 0.5 * (fx[(size_t)i] + gx[(size_t)i]);
         for (int64_t j = 0; detail->pot_y && j < m; ++j) detail->pot_y[j] = gv[(size_t)j] - 0.5 * (fy[(size_t)j] + gy[(size_t)j]);
     }
+    return FAD_OK;
+}
+
+int fad_sliced_wasserstein(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype, int on_device,
+                           const float* directions, int projections, fad_sliced_result_t* out, fad_sliced_detail_t* detail, int device,
+                           void* stream) {
+    using namespace fad;
+    begin_entry();
+    sliced_plan_value() = SlicedPlan{0, 0, 0, 0};
+    const char* who = "fad_sliced_wasserstein";
+    if (!out) return set_error(FAD_ERR_INVALID, "%s: NULL output", who);
+    if (!x || !y) return set_error(FAD_ERR_INVALID, "%s: NULL rows", who);
+    if (!directions) return set_error(FAD_ERR_INVALID, "%s: NULL directions", who);
+    if (dtype == FAD_F64) return set_error(FAD_ERR_INVALID, "%s: float64 rows are not supported; cast to float32 (or float16 / bfloat16)", who);
+    if (dtype != FAD_F16 && dtype != FAD_BF16 && dtype != FAD_F32) return set_error(FAD_ERR_INVALID, "%s: unknown dtype %d", who, dtype);
+    if (d < 1 || d > 2048) return set_error(FAD_ERR_INVALID, "%s: D = %lld is outside 1 .. 2048", who, (long long)d);
+    if (ldx < d || ldy < d) return set_error(FAD_ERR_INVALID, "%s: row pitch %lld / %lld < D = %lld", who, (long long)ldx, (long long)ldy, (long long)d);
+    if (projections < 1 || projections > 65536) return set_error(FAD_ERR_INVALID, "%s: %d projections, outside 1 .. 65536", who, projections);
+    if (n < 1 || m < 1) return set_error(FAD_ERR_TOO_FEW_ROWS, "%s: needs at least 1 row per set, got %lld and %lld", who, (long long)n, (long long)m);
+    if (n > INT32_MAX - kTile || m > INT32_MAX - kTile)
+        return set_error(FAD_ERR_INVALID, "%s: %lld and %lld rows (at most %d per set)", who, (long long)n, (long long)m, INT32_MAX - kTile);
+    if (n > (((int64_t)1 << 53) - 1) / m)
+        return set_error(FAD_ERR_INVALID, "%s: n m = %lld x %lld is 2^53 or more: the integer weights would not be exact in float64", who,
+                         (long long)n, (long long)m);
+    const int64_t L = projections;
+    const size_t es = dtype_size(dtype);
+    const int64_t dp = depth_elems(d, dtype), tpitch = dp * (int64_t)es, l_img = (kad::blocks(L) + 1) * kTile;
+
+    // the directions rounded to the rows' dtype into their zero-padded image, and q_l from the rounded values, before any device call
+    std::vector<char> timg((size_t)(l_img * tpitch), 0);
+    std::vector<double> q((size_t)L);
+    for (int64_t l = 0; l < L; ++l) {
+        double ql = 0.0;
+        for (int64_t c = 0; c < d; ++c) {
+            const float f = directions[l * d + c];
+            if (!std::isfinite(f)) return set_error(FAD_ERR_INVALID, "%s: direction %lld has an entry that is not finite", who, (long long)l);
+            double v;
+            const uint32_t bits = round_direction(f, dtype, &v);
+            if (es == 2) {
+                const uint16_t h = (uint16_t)bits;
+                memcpy(&timg[(size_t)(l * tpitch + c * 2)], &h, 2);
+            } else {
+                memcpy(&timg[(size_t)(l * tpitch + c * 4)], &bits, 4);
+            }
+            const double sq = v * v;
+            ql += sq;
+        }
+        if (!(ql > 0) || !std::isfinite(ql))
+            return set_error(FAD_ERR_INVALID, "%s: direction %lld, rounded to the rows' dtype, has the squared length %g", who, (long long)l, ql);
+        q[(size_t)l] = ql;
+    }
+    const char* env = getenv("FAD_SLICED_WORKSPACE");
+    char* end = nullptr;
+    const long long env_v = env && *env ? strtoll(env, &end, 10) : 0;
+    const int64_t budget = end && *end == 0 && env_v > 0 ? (int64_t)env_v : kSlicedWorkspace;
+
+    Ctx cx;
+    FAD_TRY(cx.open(dtype, FAD_KAD_GAUSSIAN, device, stream));
+    KadWorkspace& ws = *cx.ws;
+    const hipStream_t st = cx.st;
+    Packed px, py;                                             // each set packed once, its norms checked finite
+    FAD_TRY(pack_set(cx, 0, x, n, ldx, d, on_device, &px));
+    FAD_TRY(pack_set(cx, 1, y, m, ldy, d, on_device, &py));
+    FAD_TRY(ws.sliced_theta.reserve(timg.size()));
+    FAD_HIP_TRY(hipMemcpyAsync(ws.sliced_theta.p, timg.data(), timg.size(), hipMemcpyHostToDevice, st));
+
+    // the chunk: lc directions' projections of both sets, the sort's second buffer, its counts, the match's slots
+    const bool x_larger = n >= m;
+    const int64_t n_pad = kad::blocks(n) * kTile, m_pad = kad::blocks(m) * kTile, t_pad = std::max(n_pad, m_pad);
+    const int64_t na = x_larger ? n : m, nb = x_larger ? m : n, nblk = cdiv(na, kMatchBlock);
+    const int64_t count_words = std::max(ssort::counts_elems(n, 1), ssort::counts_elems(m, 1));
+    const int64_t per_dir = 4 * (n_pad + m_pad + t_pad) + 4 * (count_words + ssort::kRadix) + 8 * nblk;
+    const int64_t lc = std::max<int64_t>(1, std::min<int64_t>(L, budget / per_dir));
+    const int64_t chunks = cdiv(L, lc);
+    Carve cv;
+    const auto px_r = cv.add<float>(lc * n_pad), py_r = cv.add<float>(lc * m_pad), tmp_r = cv.add<float>(lc * t_pad);
+    const auto counts_r = cv.add<uint32_t>(lc * count_words), bases_r = cv.add<uint32_t>(lc * ssort::kRadix);
+    const auto slots_r = cv.add<double>(lc * nblk), s_r = cv.add<double>(L);
+    const auto zeros_r = cv.add<float>(std::max(t_pad, l_img));
+    const auto flag_r = cv.add<unsigned int>(64);
+    FAD_TRY(cv.reserve(ws.sliced));
+    FAD_HIP_TRY(hipMemsetAsync(cv.ptr(zeros_r), 0, (size_t)std::max(t_pad, l_img) * sizeof(float), st));
+    FAD_HIP_TRY(hipMemsetAsync(cv.ptr(flag_r), 0, 64 * sizeof(unsigned int), st));
+    const ssort::Plan sp = ssort::plan(n, lc);
+    sliced_plan_value() = SlicedPlan{chunks, lc, ssort::kPasses, sp.G > 1 ? -sp.G : sp.W};
+
+    // the sorted arrays are staged on the host: a refusal after the first chunk must leave the caller's arrays as they were
+    std::vector<float> sx, sy;
+    if (detail && detail->sorted_x) sx.resize((size_t)(L * n));
+    if (detail && detail->sorted_y) sy.resize((size_t)(L * m));
+    const char* theta = static_cast<const char*>(ws.sliced_theta.p);
+    float* Px = cv.ptr(px_r);
+    float* Py = cv.ptr(py_r);
+    for (int64_t l0 = 0; l0 < L; l0 += lc) {
+        const int64_t cur = std::min(lc, L - l0);
+        FAD_TRY(sliced_project_sort(cx, px, theta, cv.ptr(zeros_r), l0, cur, Px, n_pad, cv.ptr(tmp_r), cv.ptr(counts_r), cv.ptr(bases_r), cv.ptr(flag_r)));
+        FAD_TRY(sliced_project_sort(cx, py, theta, cv.ptr(zeros_r), l0, cur, Py, m_pad, cv.ptr(tmp_r), cv.ptr(counts_r), cv.ptr(bases_r), cv.ptr(flag_r)));
+        sliced_match_kernel<<<(unsigned int)(cur * nblk), kMatchBlock, 0, st>>>(x_larger ? Px : Py, x_larger ? n_pad : m_pad, na, x_larger ? Py : Px,
+                                                                                x_larger ? m_pad : n_pad, nb, nblk, cv.ptr(slots_r));
+        FAD_HIP_TRY(hipGetLastError());
+        sliced_finish_kernel<<<(unsigned int)cdiv(cur, 256), 256, 0, st>>>(cv.ptr(slots_r), nblk, cur, cv.ptr(s_r) + l0);
+        FAD_HIP_TRY(hipGetLastError());
+        if (!sx.empty())
+            FAD_HIP_TRY(hipMemcpy2DAsync(sx.data() + l0 * n, (size_t)n * 4, Px, (size_t)n_pad * 4, (size_t)n * 4, (size_t)cur, hipMemcpyDeviceToHost, st));
+        if (!sy.empty())
+            FAD_HIP_TRY(hipMemcpy2DAsync(sy.data() + l0 * m, (size_t)m * 4, Py, (size_t)m_pad * 4, (size_t)m * 4, (size_t)cur, hipMemcpyDeviceToHost, st));
+    }
+    std::vector<double> S((size_t)L);
+    unsigned int flag = 0;
+    FAD_HIP_TRY(hipMemcpyAsync(S.data(), cv.ptr(s_r), (size_t)L * sizeof(double), hipMemcpyDeviceToHost, st));
+    FAD_HIP_TRY(hipMemcpyAsync(&flag, cv.ptr(flag_r), sizeof(flag), hipMemcpyDeviceToHost, st));
+    FAD_HIP_TRY(hipStreamSynchronize(st));
+    if (flag) return set_error(FAD_ERR_NOT_FINITE, "%s: a projection is not finite in float32", who);
+
+    // W_l = S_l / (n m q_l), one division; mean, spread and maximum over l in index order
+    const double nm = (double)(n * m);
+    std::vector<double> W((size_t)L);
+    double sum = 0.0, best = -INFINITY;
+    int64_t best_l = 0;
+    for (int64_t l = 0; l < L; ++l) {
+        const double w = S[(size_t)l] / (nm * q[(size_t)l]);
+        W[(size_t)l] = w;
+        sum += w;
+        if (w > best) { best = w; best_l = l; }
+    }
+    const double mean = sum / (double)L;
+    double dev2 = 0.0;
+    for (int64_t l = 0; l < L; ++l) {
+        const double dv = W[(size_t)l] - mean;
+        const double sq = dv * dv;
+        dev2 += sq;
+    }
+    out->sw2_squared = mean;
+    out->std_error = L > 1 ? std::sqrt(dev2 / (double)(L - 1)) / std::sqrt((double)L) : (double)NAN;
+    out->max_sliced = best; out->max_index = best_l;
+    out->n = n; out->m = m; out->projections = projections;
+    if (detail) {
+        if (detail->values) memcpy(detail->values, W.data(), (size_t)L * sizeof(double));
+        if (detail->sorted_x) memcpy(detail->sorted_x, sx.data(), sx.size() * sizeof(float));
+        if (detail->sorted_y) memcpy(detail->sorted_y, sy.data(), sy.size() * sizeof(float));
+    }
+    return FAD_OK;
+}
+
+int fad_sliced_last_plan(int64_t out[4]) {
+    using namespace fad;
+    if (!out) return set_error(FAD_ERR_INVALID, "fad_sliced_last_plan: NULL output");
+    const SlicedPlan& p = sliced_plan_value();
+    out[0] = p.chunks; out[1] = p.lc; out[2] = p.passes; out[3] = p.share;
     return FAD_OK;
 }
 

@@ -1225,3 +1225,59 @@ def sinkhorn(x, y, epsilon: Optional[float] = None, iterations: int = 100, devic
     out = res.as_dict()
     out.update(arrays)
     return out
+
+
+# ------------------------------------------------------------------------ sliced Wasserstein distance between the two sets of rows
+SLICED_MAX_PROJECTIONS = 65536
+
+
+def sliced_directions_array(directions, d: int) -> np.ndarray:
+    """-> ``directions`` as the C ABI takes them: a C-contiguous float32 [L x d] array, L in 1 .. 65536, every entry finite.  Anything
+    else is a ValueError, raised before the native library is touched."""
+    t = np.ascontiguousarray(np.asarray(directions), dtype=np.float32)
+    if t.ndim != 2 or t.shape[1] != d:
+        raise ValueError(f"sliced Wasserstein: directions must be [L x {d}], got shape {t.shape}")
+    if not 1 <= t.shape[0] <= SLICED_MAX_PROJECTIONS:
+        raise ValueError(f"sliced Wasserstein: {t.shape[0]} directions, outside 1 .. {SLICED_MAX_PROJECTIONS}")
+    if not np.all(np.isfinite(t)):
+        raise ValueError("sliced Wasserstein: a direction has an entry that is not finite")
+    return t
+
+
+def sliced_wasserstein(x, y, directions, device: int = 0, values: bool = False, sorted_projections: bool = False) -> dict:
+    """``fad_sliced_wasserstein``: the sliced 2-Wasserstein distance between the rows of x (baseline) and y over the float32 directions
+    [L x D] (not normalised: the library divides by their squared lengths) -> dict of fad_sliced_result (sw2_squared, std_error,
+    max_sliced, max_index, n, m, projections).  ``values=True`` adds the float64 array ``values`` [L] (W_l); ``sorted_projections=True``
+    adds the float32 arrays ``sorted_x`` [L x n] and ``sorted_y`` [L x m].  Both sets are numpy arrays or both torch CUDA tensors of
+    one dtype (float16 / bfloat16 / float32)."""
+    lib = K.load_library()
+    (px, n, d, ldx, cx, dev_x, kx), (py, m, dy, ldy, cy, dev_y, ky) = _kad_pair(x, y, "y", device)
+    if d != dy:
+        raise ValueError(f"sliced Wasserstein: x has D = {d}, y has D = {dy}")
+    if cx != cy:
+        raise ValueError("sliced Wasserstein: x and y must have the same dtype")
+    t = sliced_directions_array(directions, d)
+    L = t.shape[0]
+    res = K.FadSlicedResult()
+    arrays = {}
+    if values:
+        arrays["values"] = np.zeros(L)
+    if sorted_projections:
+        arrays["sorted_x"] = np.zeros((L, n), dtype=np.float32)
+        arrays["sorted_y"] = np.zeros((L, m), dtype=np.float32)
+    det = K.FadSlicedDetail(*(arrays[k].ctypes.data if k in arrays else None for k in ("values", "sorted_x", "sorted_y"))) if arrays else None
+    K.check(lib.fad_sliced_wasserstein(px, n, ldx, py, m, ldy, d, cx, dev_x, t.ctypes.data, L, C.byref(res),
+                                       C.byref(det) if det is not None else None, int(device), K.current_stream_ptr(device)),
+            "fad_sliced_wasserstein")
+    out = res.as_dict()
+    out.update(arrays)
+    return out
+
+
+def sliced_last_plan() -> dict:
+    """``fad_sliced_last_plan``: how this thread's last fad_sliced_wasserstein call was laid out -> dict of ``chunks``,
+    ``directions_per_chunk``, ``sort_passes`` and ``share`` (W >= 1: workgroups per segment of x's sort; -G: one workgroup owns G
+    segments)."""
+    out = (C.c_int64 * 4)()
+    K.check(K.load_library().fad_sliced_last_plan(out), "fad_sliced_last_plan")
+    return dict(zip(("chunks", "directions_per_chunk", "sort_passes", "share"), map(int, out)))

@@ -638,6 +638,50 @@ int fad_sinkhorn(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m
                  double epsilon, int iterations, fad_sinkhorn_result_t* out, fad_sinkhorn_detail_t* detail /* may be NULL */,
                  int device, void* stream);
 
+/* ------------------------------------------------------------------ sliced 2-Wasserstein distance between the two sets of rows
+ * Not in the reference.  The transport distance between the empirical measures of x [n x d] and y [m x d] (uniform weights), averaged
+ * over L = `projections` one-dimensional projections (Rabin et al. 2011; Bonneel et al. 2015): no blur, no iterations, O((n + m) log)
+ * per direction on all rows.  `directions` [L x d] is host float32 and is NOT normalised by the caller or the library: the library
+ * rounds it to the rows' dtype (round to nearest even) when it packs it, so that for 16-bit rows every product is exact in float32,
+ * and q_l = sum_c theta_lc^2 comes from the rounded values in float64, in index order.  Per direction l, with a = sort(x theta_l),
+ * b = sort(y theta_l) and the step quantile functions of the two,
+ *   W_l = (1 / q_l) int_0^1 (Fa^-1(t) - Fb^-1(t))^2 dt = S_l / (n m q_l),
+ *   S_l = sum over the overlapping (i, j) of w_ij (a_(i) - b_(j))^2,  w_ij = min((i + 1) m, (j + 1) n) - max(i m, j n) > 0, an integer
+ * (n == m: S_l = n sum_i (a_(i) - b_(i))^2).
+ *   sw2_squared = mean_l W_l;  std_error = std(W_l, ddof = 1) / sqrt(L), NaN for L = 1;  max_sliced = max_l W_l at max_index (the first).
+ *   D x sw2_squared reads beside FAD's mean term: a pure translation delta and directions uniform on the sphere give E W_l = |delta|^2 / D.
+ *   detail (may be NULL; each array NULL or host): values [L] = W_l; sorted_x [L x n], sorted_y [L x m]: the sorted float32 projections.
+ * Arithmetic: projections in float32 on the matrix cores (KAD's main loop, the directions as a third image); a segmented radix sort of
+ * the float32 keys (csrc/sliced_sort.h: exact, stable, the same passes whatever the keys, -0 before +0); the difference a - b, its
+ * square, the product with the integer weight and every sum in float64, each operation rounded once (no fused multiply-add).  S_l is
+ * summed in a fixed order: per element i of the larger set (x when n == m) over its j ascending, then blocks of 256 consecutive i by a
+ * halving tree (i += i + 128, i += i + 64, ...), then the blocks in index order.  W_l is one division S_l / ((double)(n m) q_l); the mean
+ * (a running sum over l, divided by L), sqrt(sum_l (W_l - mean)^2 / (L - 1)) / sqrt(L) and the maximum are taken on the host in index
+ * order.  So: the same bits on every run, whatever the chunking, and for swapped arguments; exactly 0 for sets of identical bits.
+ * Rows are float16 / bfloat16 / float32; FAD_F64 -> FAD_ERR_INVALID (cast).  d outside 1 .. 2048, a row pitch < d, projections outside
+ * 1 .. 65536, a NULL out or directions, a direction with an entry that is not finite or whose rounded q_l is 0 or not finite,
+ * n m >= 2^53 -> FAD_ERR_INVALID; n or m < 1 -> FAD_ERR_TOO_FEW_ROWS; a NaN/Inf row norm or a projection that is not finite in float32
+ * -> FAD_ERR_NOT_FINITE.  Argument errors come before any device call; any refusal leaves every output untouched.
+ * Workspace: the two images and the directions' ((L rounded up to 128) + 128 rows); then, per direction of a chunk, 4 bytes per padded
+ * row of x, of y and of the larger of the two (the sort's second buffer), 1 KiB per 2048 rows of the larger set (counts) and 8 bytes per
+ * 256 of them.  Directions are processed in chunks so that this second part stays within 1 GiB (a chunk holds at least one direction).
+ * The environment variable FAD_SLICED_WORKSPACE (bytes, read at the start of every call) replaces the 1 GiB: it exists for tests, which
+ * force several chunks at small shapes with it.  sorted_x / sorted_y are staged in host memory until the call succeeds.
+ * Synchronises `stream`. */
+typedef struct fad_sliced_result {
+    double sw2_squared, std_error, max_sliced;
+    int64_t max_index, n, m;
+    int projections;
+} fad_sliced_result_t;
+typedef struct fad_sliced_detail {
+    double* values;      /* [L]      W_l, may be NULL */
+    float* sorted_x;     /* [L x n]  may be NULL */
+    float* sorted_y;     /* [L x m]  may be NULL */
+} fad_sliced_detail_t;
+int fad_sliced_wasserstein(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype,
+                           int on_device, const float* directions /* host, [L x d] */, int projections,
+                           fad_sliced_result_t* out, fad_sliced_detail_t* detail /* may be NULL */, int device, void* stream);
+
 /* ------------------------------------------------------------------ diagnostics (NOT part of the drop-in surface)
  * Nothing in fadtk corresponds to these two calls and no binding of the reference needs them: they exist for bench.py's
  * roofline object (HIP events around the tile kernel on the stream it is launched on) and for the GPU tests that check
@@ -666,6 +710,12 @@ int fad_moments_last_timing(fad_moments_t* h, float* ms_main_kernel, float* ms_r
  * variable FAD_KAD_LAUNCH_BUDGET (cost units per launch, default 2^30, read at the start of every such call; a launch never holds
  * fewer than 64 tiles) exists for tests, which cut small passes into several launches with it. */
 int fad_kad_last_plan(int64_t out[5]);
+
+/* Diagnostic: how the last fad_sliced_wasserstein call of this thread was laid out.  out = { chunks, directions per chunk, sort passes,
+ * share }; all 0 when the call was refused before it planned.  share describes the sort of x's segments in a full chunk: W >= 1 when a
+ * segment of n keys takes W workgroups (2048 keys each), -G when n <= 256 and one workgroup owns G > 1 segments.  The chunking follows
+ * FAD_SLICED_WORKSPACE (above), as fad_kad_last_plan's launch cut follows FAD_KAD_LAUNCH_BUDGET. */
+int fad_sliced_last_plan(int64_t out[4]);
 
 /* A HIP stream confined to a subset of the device's CUs (hipExtStreamCreateWithCUMask; `mask` = `words` x 32 bits, bit i = CU i in
  * the runtime's numbering, which on this 8-XCD part walks the XCDs first: bit i -> XCD i % 8).  bench.py's --chain-cus layout
