@@ -28,6 +28,7 @@
 #include "kid_tiles.h"
 #include "nn_vote.h"
 #include "sliced_sort.h"
+#include "sliced_song_sort.h"
 
 #include <algorithm>
 #include <cmath>
@@ -812,6 +813,92 @@ __global__ void __launch_bounds__(256) sliced_finish_kernel(const double* __rest
     double s = 0.0;
     for (int64_t k = 0; k < nblk; ++k) s += slots[l * nblk + k];
     S[l] = s;
+}
+
+// ------------------------------------------------------------------------------- per-song sliced Wasserstein distance
+// bad[s] = 1 for the song of every row whose h is not finite (a NaN/Inf squared norm): one thread per row, the song by bisection
+__global__ void __launch_bounds__(256) sliced_song_norm_kernel(const float* __restrict__ h, int64_t n_rows, const int64_t* __restrict__ off,
+                                                               int64_t n_songs, unsigned int* __restrict__ bad) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_rows || isfinite(h[i])) return;
+    int64_t lo = 0, hi = n_songs - 1;                      // the first song that ends beyond row i
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (off[mid + 1] > i) hi = mid; else lo = mid + 1;
+    }
+    bad[lo] = 1u;                                          // every writer stores the same word
+}
+
+// The quantile match of one chunk, per song: workgroup (direction l, song s) is sliced_match_kernel and sliced_finish_kernel of the pair
+// (x, song s) in one: it walks the blocks of 256 elements of the sorted larger set (x at a tie) in index order, sums each block's terms
+// as that kernel does -- per element over its j ascending, the block by the halving tree -- and adds the block's sum to a running
+// float64 sum, the finish kernel's order.  The tree needs one barrier a block: every thread stores its sum, then wave 0 forms
+// (red[t] + red[t + 128]) + (red[t + 64] + red[t + 192]), the tree's steps 128 and 64 in its own pairing, and the last six steps as lane
+// shifts that pair the same elements; the stores alternate between two buffers, so the next block's stores cannot reach what wave 0
+// still reads.  The integers are found without a division in the loop: the smaller set never has more elements than the larger, so
+// with i nb = j0 na + r (0 <= r < na) element i meets j0 with the weight min(nb, na - r) and, when r + nb > na, j0 + 1 with r + nb - na
+// -- sliced_match_kernel's j0 .. j1 and its weights -- and a thread's (j0, r) move from block to block by a fixed step.  Integers, so
+// no floating-point result depends on how they were found.  A sorted song whose first or last key is not finite holds a projection
+// that is not finite (key_image puts NaNs and infinities at the two ends): it sets bad[s].  Songs without rows are skipped.
+struct SongMatchArgs {
+    const float* px; int64_t px_pitch, n;                  // the chunk's sorted baseline projections
+    const float* pr; int64_t pr_pitch;                     // the songs'
+    const int64_t* off; int64_t n_songs;
+    double* S;                                             // [chunk directions x n_songs]
+    unsigned int* bad;
+};
+
+__global__ void __launch_bounds__(kMatchBlock) sliced_song_match_kernel(SongMatchArgs p) {
+#pragma clang fp contract(off)
+    __shared__ double red[2][kMatchBlock];
+    const int tid = threadIdx.x;
+    const int64_t l = blockIdx.x / p.n_songs, sg = blockIdx.x % p.n_songs;
+    const int64_t o = p.off[sg], m = p.off[sg + 1] - o;
+    if (m == 0) return;                                    // uniform over the workgroup
+    const float* xs = p.px + l * p.px_pitch;
+    const float* ys = p.pr + l * p.pr_pitch + o;
+    const bool x_leads = p.n >= m;
+    const float* __restrict__ a = x_leads ? xs : ys;
+    const float* __restrict__ b = x_leads ? ys : xs;
+    const int64_t na = x_leads ? p.n : m, nb = x_leads ? m : p.n, nblk = (na + kMatchBlock - 1) / kMatchBlock;
+    if (tid == 0 && (!(fabsf(ys[0]) < INFINITY) || !(fabsf(ys[m - 1]) < INFINITY))) p.bad[sg] = 1u;
+    const int64_t step_q = (kMatchBlock * nb) / na, step_r = (kMatchBlock * nb) % na;
+    int64_t j0 = ((int64_t)tid * nb) / na, r = ((int64_t)tid * nb) % na;              // of element i = tid; then i += 256 a block
+    double run = 0.0;
+    for (int64_t k = 0; k < nblk; ++k) {
+        const int64_t i = k * kMatchBlock + tid;
+        double s = 0.0;
+        if (i < na) {
+            const double ai = (double)a[i];
+            {
+                const int64_t w = nb < na - r ? nb : na - r;
+                const double diff = ai - (double)b[j0];
+                const double sq = diff * diff;
+                const double term = (double)w * sq;
+                s += term;
+            }
+            if (r + nb > na) {
+                const int64_t w = r + nb - na;
+                const double diff = ai - (double)b[j0 + 1];
+                const double sq = diff * diff;
+                const double term = (double)w * sq;
+                s += term;
+            }
+        }
+        j0 += step_q; r += step_r;
+        if (r >= na) { r -= na; ++j0; }
+        double* buf = red[k & 1];
+        buf[tid] = s;
+        __syncthreads();
+        if (tid < 64) {
+            const double lo = buf[tid] + buf[tid + 128], hi = buf[tid + 64] + buf[tid + 192];
+            double v = lo + hi;
+#pragma unroll
+            for (int w = 32; w > 0; w >>= 1) v += __shfl_down(v, w, 64);
+            if (tid == 0) run += v;
+        }
+    }
+    if (tid == 0) p.S[l * p.n_songs + sg] = run;
 }
 
 // ---------------------------------------------------------------------------------------- KAD standard errors
@@ -2097,7 +2184,7 @@ struct KadWorkspace {
     DevBuf near;                                     // fad_nearest: index, dist2, radii, nn radii, copied count; fad_nn_test: index, dist2, counts
     DevBuf kid_index, kid;                           // fad_kid_subsets: the two index lists; the bad-index count, sums and results
     DevBuf sink_slots, sink;                         // fad_sinkhorn: the column states of a half-step; potentials and sums
-    DevBuf sliced_theta, sliced;                     // fad_sliced_wasserstein: the directions' image; projections, sort scratch and sums
+    DevBuf sliced_theta, sliced;                     // fad_sliced_wasserstein, fad_sliced_individual: the directions' image; projections, sort scratch and sums
     void release_all() {
         for (int i = 0; i < 2; ++i) { raw[i].release(); img[i].release(); h[i].release(); }
         slots.release(); small.release(); cross.release(); band.release(); songs.release(); lists.release(); prdc.release();
@@ -3001,6 +3088,44 @@ static int sliced_project_sort(const Ctx& cx, const Packed& set, const char* the
     const unsigned int grid = (unsigned int)std::min<int64_t>(p.TI * p.TJ, grid_cap(cx.device));
     FAD_TRY(with_dtype(cx.dtype, [&](auto dt) { sliced_project_kernel<dt><<<grid, kThreads, kLdsProject, cx.st>>>(p); }));
     FAD_HIP_TRY(ssort::sort_segments(P, tmp, ppitch, set.n, lc, counts, bases, cx.st));
+    return FAD_OK;
+}
+
+// fad_sliced_individual_last_plan: chunks, directions per chunk, resident units per direction, songs on the long path, most songs in
+// one unit, the resident capacity
+struct SlicedSongPlan { int64_t v[6]; };
+static SlicedSongPlan& sliced_song_plan_value() {
+    static thread_local SlicedSongPlan p{{0, 0, 0, 0, 0, 0}};
+    return p;
+}
+
+// The directions rounded to the rows' dtype into their zero-padded image (l_img rows of tpitch bytes), and q_l from the rounded values
+// in index order: what fad_sliced_wasserstein builds, entry by entry.  No device call.
+static int sliced_direction_image(const float* directions, int64_t L, int64_t d, int dtype, int64_t tpitch, int64_t l_img, const char* who,
+                                  std::vector<char>* timg, std::vector<double>* q) {
+    const size_t es = dtype_size(dtype);
+    timg->assign((size_t)(l_img * tpitch), 0);
+    q->resize((size_t)L);
+    for (int64_t l = 0; l < L; ++l) {
+        double ql = 0.0;
+        for (int64_t c = 0; c < d; ++c) {
+            const float f = directions[l * d + c];
+            if (!std::isfinite(f)) return set_error(FAD_ERR_INVALID, "%s: direction %lld has an entry that is not finite", who, (long long)l);
+            double v;
+            const uint32_t bits = round_direction(f, dtype, &v);
+            if (es == 2) {
+                const uint16_t h = (uint16_t)bits;
+                memcpy(&(*timg)[(size_t)(l * tpitch + c * 2)], &h, 2);
+            } else {
+                memcpy(&(*timg)[(size_t)(l * tpitch + c * 4)], &bits, 4);
+            }
+            const double sq = v * v;
+            ql += sq;
+        }
+        if (!(ql > 0) || !std::isfinite(ql))
+            return set_error(FAD_ERR_INVALID, "%s: direction %lld, rounded to the rows' dtype, has the squared length %g", who, (long long)l, ql);
+        (*q)[(size_t)l] = ql;
+    }
     return FAD_OK;
 }
 
@@ -4037,6 +4162,192 @@ int fad_sliced_last_plan(int64_t out[4]) {
     if (!out) return set_error(FAD_ERR_INVALID, "fad_sliced_last_plan: NULL output");
     const SlicedPlan& p = sliced_plan_value();
     out[0] = p.chunks; out[1] = p.lc; out[2] = p.passes; out[3] = p.share;
+    return FAD_OK;
+}
+
+int fad_sliced_individual(const void* x, int64_t n, int64_t ldx, const void* rows, int64_t n_rows, int64_t ldy, const int64_t* offsets,
+                          int64_t n_songs, int64_t d, int dtype, int on_device, const float* directions, int projections, double* out_sw2,
+                          double* out_std_error, double* out_max_sliced, int64_t* out_max_index, int32_t* out_status,
+                          fad_sliced_individual_detail_t* detail, int device, void* stream) {
+    using namespace fad;
+    begin_entry();
+    sliced_song_plan_value() = SlicedSongPlan{{0, 0, 0, 0, 0, 0}};
+    const char* who = "fad_sliced_individual";
+    if (!out_sw2 || !out_std_error || !out_max_sliced || !out_max_index || !out_status)
+        return set_error(FAD_ERR_INVALID, "%s: NULL per-song output", who);
+    if (!x) return set_error(FAD_ERR_INVALID, "%s: NULL rows", who);
+    if (!offsets) return set_error(FAD_ERR_INVALID, "%s: NULL offsets", who);
+    if (!directions) return set_error(FAD_ERR_INVALID, "%s: NULL directions", who);
+    if (dtype == FAD_F64) return set_error(FAD_ERR_INVALID, "%s: float64 rows are not supported; cast to float32 (or float16 / bfloat16)", who);
+    if (dtype != FAD_F16 && dtype != FAD_BF16 && dtype != FAD_F32) return set_error(FAD_ERR_INVALID, "%s: unknown dtype %d", who, dtype);
+    if (d < 1 || d > 2048) return set_error(FAD_ERR_INVALID, "%s: D = %lld is outside 1 .. 2048", who, (long long)d);
+    if (ldx < d) return set_error(FAD_ERR_INVALID, "%s: row pitch %lld < D = %lld", who, (long long)ldx, (long long)d);
+    if (projections < 1 || projections > 65536) return set_error(FAD_ERR_INVALID, "%s: %d projections, outside 1 .. 65536", who, projections);
+    if (n < 1) return set_error(FAD_ERR_TOO_FEW_ROWS, "%s: needs at least 1 baseline row, got %lld", who, (long long)n);
+    if (n > INT32_MAX - kTile) return set_error(FAD_ERR_INVALID, "%s: %lld baseline rows (at most %d)", who, (long long)n, INT32_MAX - kTile);
+    if (n_songs < 1 || n_songs > INT32_MAX) return set_error(FAD_ERR_INVALID, "%s: %lld songs", who, (long long)n_songs);
+    if (n_rows < 0 || n_rows > INT32_MAX - kTile)
+        return set_error(FAD_ERR_INVALID, "%s: %lld song rows (at most %d)", who, (long long)n_rows, INT32_MAX - kTile);
+    if (n_rows > 0 && !rows) return set_error(FAD_ERR_INVALID, "%s: NULL song rows", who);
+    if (n_rows > 0 && ldy < d) return set_error(FAD_ERR_INVALID, "%s: song row pitch %lld < D = %lld", who, (long long)ldy, (long long)d);
+    if (offsets[0] != 0 || offsets[n_songs] != n_rows)
+        return set_error(FAD_ERR_INVALID, "%s: offsets run from %lld to %lld, not 0 to %lld", who, (long long)offsets[0],
+                         (long long)offsets[n_songs], (long long)n_rows);
+    int64_t longest = 0;
+    for (int64_t s = 0; s < n_songs; ++s) {
+        const int64_t m = offsets[s + 1] - offsets[s];
+        if (m < 0) return set_error(FAD_ERR_INVALID, "%s: offsets decrease at song %lld", who, (long long)s);
+        if (m > 0 && n > (((int64_t)1 << 53) - 1) / m)
+            return set_error(FAD_ERR_INVALID, "%s: n m = %lld x %lld (song %lld) is 2^53 or more: the integer weights would not be exact in "
+                             "float64", who, (long long)n, (long long)m, (long long)s);
+        longest = std::max(longest, m);
+    }
+    const int64_t L = projections;
+    const size_t es = dtype_size(dtype);
+    const int64_t dp = depth_elems(d, dtype), tpitch = dp * (int64_t)es, l_img = (kad::blocks(L) + 1) * kTile;
+    std::vector<char> timg;
+    std::vector<double> q;
+    FAD_TRY(sliced_direction_image(directions, L, d, dtype, tpitch, l_img, who, &timg, &q));
+    const char* env = getenv("FAD_SLICED_WORKSPACE");
+    char* end = nullptr;
+    const long long env_v = env && *env ? strtoll(env, &end, 10) : 0;
+    const int64_t budget = end && *end == 0 && env_v > 0 ? (int64_t)env_v : kSlicedWorkspace;
+    const songsort::Table table = songsort::build_units(offsets, n_songs);
+    const int64_t n_units = (int64_t)table.units.size(), n_long = (int64_t)table.long_songs.size();
+
+    Ctx cx;
+    FAD_TRY(cx.open(dtype, FAD_KAD_GAUSSIAN, device, stream));
+    KadWorkspace& ws = *cx.ws;
+    const hipStream_t st = cx.st;
+    Packed px, pr{};                                           // the baseline's norms are checked finite; the songs' per song, below
+    FAD_TRY(pack_set(cx, 0, x, n, ldx, d, on_device, &px));
+    if (n_rows > 0) FAD_TRY(pack_image(cx, 1, rows, n_rows, ldy, d, on_device, &pr));
+    FAD_TRY(ws.sliced_theta.reserve(timg.size()));
+    FAD_HIP_TRY(hipMemcpyAsync(ws.sliced_theta.p, timg.data(), timg.size(), hipMemcpyHostToDevice, st));
+
+    // the chunk: lc directions' projections of the baseline and of all song rows, the global sort's second buffer (as wide as the song
+    // rows only when a song takes the long path) and counts, one sum per song
+    const int64_t n_pad = kad::blocks(n) * kTile, r_pad = kad::blocks(n_rows) * kTile, t_pad = std::max(n_pad, n_long ? r_pad : 0);
+    const int64_t count_words = std::max(ssort::counts_elems(n, 1), ssort::counts_elems(longest > songsort::kCapacity ? longest : 1, 1));
+    const int64_t per_dir = 4 * (n_pad + r_pad + t_pad) + 4 * (count_words + ssort::kRadix) + 8 * n_songs;
+    const int64_t lc = std::max<int64_t>(1, std::min<int64_t>(L, budget / per_dir));
+    const int64_t chunks = cdiv(L, lc);
+    Carve cv;
+    const auto px_r = cv.add<float>(lc * n_pad), pr_r = cv.add<float>(lc * r_pad), tmp_r = cv.add<float>(lc * t_pad);
+    const auto counts_r = cv.add<uint32_t>(lc * count_words), bases_r = cv.add<uint32_t>(lc * ssort::kRadix);
+    const auto s_r = cv.add<double>(lc * n_songs);
+    const auto zeros_r = cv.add<float>(std::max(std::max(n_pad, r_pad), l_img));
+    const auto off_r = cv.add<int64_t>(n_songs + 1);
+    const auto units_r = cv.add<songsort::Unit>(n_units);
+    const auto ends_r = cv.add<int32_t>((int64_t)table.ends.size());
+    const auto bad_r = cv.add<unsigned int>(n_songs);
+    const auto flag_r = cv.add<unsigned int>(128);             // word 0: the baseline's projections; word 64: the song rows', never read
+    FAD_TRY(cv.reserve(ws.sliced));
+    FAD_HIP_TRY(hipMemsetAsync(cv.ptr(zeros_r), 0, (size_t)std::max(std::max(n_pad, r_pad), l_img) * sizeof(float), st));
+    FAD_HIP_TRY(hipMemsetAsync(cv.ptr(flag_r), 0, 128 * sizeof(unsigned int), st));
+    FAD_HIP_TRY(hipMemsetAsync(cv.ptr(bad_r), 0, (size_t)n_songs * sizeof(unsigned int), st));
+    FAD_HIP_TRY(hipMemcpyAsync(cv.ptr(off_r), offsets, (size_t)(n_songs + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    if (n_units) {
+        FAD_HIP_TRY(hipMemcpyAsync(cv.ptr(units_r), table.units.data(), (size_t)n_units * sizeof(songsort::Unit), hipMemcpyHostToDevice, st));
+        FAD_HIP_TRY(hipMemcpyAsync(cv.ptr(ends_r), table.ends.data(), table.ends.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    }
+    sliced_song_plan_value() = SlicedSongPlan{{chunks, lc, n_units, n_long, table.most_songs, songsort::kCapacity}};
+
+    if (n_rows > 0) {
+        sliced_song_norm_kernel<<<(unsigned int)cdiv(n_rows, 256), 256, 0, st>>>(pr.h, n_rows, cv.ptr(off_r), n_songs, cv.ptr(bad_r));
+        FAD_HIP_TRY(hipGetLastError());
+    }
+    // everything is staged on the host: a refusal after the first chunk must leave the caller's arrays as they were
+    std::vector<double> S((size_t)(L * n_songs), 0.0);
+    std::vector<float> sx, sr;
+    if (detail && detail->sorted_x) sx.resize((size_t)(L * n));
+    if (detail && detail->sorted_rows) sr.resize((size_t)(L * n_rows));
+    const char* theta = static_cast<const char*>(ws.sliced_theta.p);
+    float* Px = cv.ptr(px_r);
+    float* Pr = cv.ptr(pr_r);
+    unsigned int* flags = cv.ptr(flag_r);
+    for (int64_t l0 = 0; l0 < L; l0 += lc) {
+        const int64_t cur = std::min(lc, L - l0);
+        FAD_TRY(sliced_project_sort(cx, px, theta, cv.ptr(zeros_r), l0, cur, Px, n_pad, cv.ptr(tmp_r), cv.ptr(counts_r), cv.ptr(bases_r), flags));
+        if (n_rows > 0) {
+            ProjArgs p{};
+            p.th = theta + l0 * pr.pitch; p.rows = pr.img; p.zeros = cv.ptr(zeros_r); p.pitch = pr.pitch; p.nchunks = pr.nchunks;
+            p.TI = kad::blocks(cur); p.TJ = kad::blocks(n_rows); p.lc = cur; p.n = n_rows; p.P = Pr; p.ppitch = r_pad; p.flag = flags + 64;
+            const unsigned int grid = (unsigned int)std::min<int64_t>(p.TI * p.TJ, grid_cap(device));
+            FAD_TRY(with_dtype(dtype, [&](auto dt) { sliced_project_kernel<dt><<<grid, kThreads, kLdsProject, st>>>(p); }));
+            FAD_HIP_TRY(songsort::sort_units(Pr, r_pad, cur, cv.ptr(units_r), cv.ptr(ends_r), n_units, st));
+            for (const int64_t s : table.long_songs)           // the rare path: the global sort, song by song
+                FAD_HIP_TRY(ssort::sort_segments(Pr + offsets[s], cv.ptr(tmp_r) + offsets[s], r_pad, offsets[s + 1] - offsets[s], cur,
+                                                 cv.ptr(counts_r), cv.ptr(bases_r), st));
+            SongMatchArgs ma{Px, n_pad, n, Pr, r_pad, cv.ptr(off_r), n_songs, cv.ptr(s_r), cv.ptr(bad_r)};
+            const int64_t per = std::max<int64_t>(1, (int64_t)INT32_MAX / n_songs);    // directions per launch: the grid's x extent
+            for (int64_t c0 = 0; c0 < cur; c0 += per) {
+                const int64_t cc = std::min(per, cur - c0);
+                ma.px = Px + c0 * n_pad; ma.pr = Pr + c0 * r_pad; ma.S = cv.ptr(s_r) + c0 * n_songs;
+                sliced_song_match_kernel<<<(unsigned int)(cc * n_songs), kMatchBlock, 0, st>>>(ma);
+                FAD_HIP_TRY(hipGetLastError());
+            }
+            FAD_HIP_TRY(hipMemcpyAsync(S.data() + l0 * n_songs, cv.ptr(s_r), (size_t)(cur * n_songs) * sizeof(double), hipMemcpyDeviceToHost, st));
+        }
+        if (!sx.empty())
+            FAD_HIP_TRY(hipMemcpy2DAsync(sx.data() + l0 * n, (size_t)n * 4, Px, (size_t)n_pad * 4, (size_t)n * 4, (size_t)cur, hipMemcpyDeviceToHost, st));
+        if (!sr.empty())
+            FAD_HIP_TRY(hipMemcpy2DAsync(sr.data() + l0 * n_rows, (size_t)n_rows * 4, Pr, (size_t)r_pad * 4, (size_t)n_rows * 4, (size_t)cur,
+                                         hipMemcpyDeviceToHost, st));
+    }
+    std::vector<unsigned int> bad((size_t)n_songs);
+    unsigned int flag = 0;
+    FAD_HIP_TRY(hipMemcpyAsync(bad.data(), cv.ptr(bad_r), (size_t)n_songs * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+    FAD_HIP_TRY(hipMemcpyAsync(&flag, flags, sizeof(flag), hipMemcpyDeviceToHost, st));
+    FAD_HIP_TRY(hipStreamSynchronize(st));
+    if (flag) return set_error(FAD_ERR_NOT_FINITE, "%s: a projection of the baseline is not finite in float32", who);
+
+    // per song, as fad_sliced_wasserstein: W_l = S_l / (n m q_l), one division; mean, spread and maximum over l in index order
+    std::vector<double> W((size_t)L);
+    for (int64_t s = 0; s < n_songs; ++s) {
+        const int64_t m = offsets[s + 1] - offsets[s];
+        double* vals = detail && detail->values ? detail->values + s * L : nullptr;
+        if (m == 0 || bad[(size_t)s]) {
+            out_status[s] = m == 0 ? FAD_ERR_TOO_FEW_ROWS : FAD_ERR_NOT_FINITE;
+            out_sw2[s] = out_std_error[s] = out_max_sliced[s] = NAN;
+            out_max_index[s] = -1;
+            for (int64_t l = 0; vals && l < L; ++l) vals[l] = NAN;
+            continue;
+        }
+        const double nm = (double)(n * m);
+        double sum = 0.0, best = -INFINITY;
+        int64_t best_l = 0;
+        for (int64_t l = 0; l < L; ++l) {
+            const double w = S[(size_t)(l * n_songs + s)] / (nm * q[(size_t)l]);
+            W[(size_t)l] = w;
+            sum += w;
+            if (w > best) { best = w; best_l = l; }
+        }
+        const double mean = sum / (double)L;
+        double dev2 = 0.0;
+        for (int64_t l = 0; l < L; ++l) {
+            const double dv = W[(size_t)l] - mean;
+            const double sq = dv * dv;
+            dev2 += sq;
+        }
+        out_status[s] = FAD_OK;
+        out_sw2[s] = mean;
+        out_std_error[s] = L > 1 ? std::sqrt(dev2 / (double)(L - 1)) / std::sqrt((double)L) : (double)NAN;
+        out_max_sliced[s] = best; out_max_index[s] = best_l;
+        if (vals) memcpy(vals, W.data(), (size_t)L * sizeof(double));
+    }
+    if (detail) {
+        if (detail->sorted_x) memcpy(detail->sorted_x, sx.data(), sx.size() * sizeof(float));
+        if (detail->sorted_rows && !sr.empty()) memcpy(detail->sorted_rows, sr.data(), sr.size() * sizeof(float));
+    }
+    return FAD_OK;
+}
+
+int fad_sliced_individual_last_plan(int64_t out[6]) {
+    using namespace fad;
+    if (!out) return set_error(FAD_ERR_INVALID, "fad_sliced_individual_last_plan: NULL output");
+    const SlicedSongPlan& p = sliced_song_plan_value();
+    for (int i = 0; i < 6; ++i) out[i] = p.v[i];
     return FAD_OK;
 }
 

@@ -1281,3 +1281,53 @@ def sliced_last_plan() -> dict:
     out = (C.c_int64 * 4)()
     K.check(K.load_library().fad_sliced_last_plan(out), "fad_sliced_last_plan")
     return dict(zip(("chunks", "directions_per_chunk", "sort_passes", "share"), map(int, out)))
+
+
+def sliced_individual(x, rows, offsets: Sequence[int], directions, device: int = 0, values: bool = False, sorted: bool = False) -> dict:
+    """``fad_sliced_individual``: the sliced 2-Wasserstein distance between the baseline rows x and every song s =
+    rows[offsets[s]:offsets[s + 1]] over the float32 directions [L x D], bit for bit what ``sliced_wasserstein(x, song_s, directions)``
+    gives -> dict of float64 arrays ``sw2_squared``, ``std_error``, ``max_sliced``, int64 ``max_index`` and int32 ``status`` [S] (NaN
+    and -1 where status is FAD_ERR_TOO_FEW_ROWS or FAD_ERR_NOT_FINITE), plus ``n`` and ``projections``.  ``values=True`` adds the
+    float64 array ``values`` [S x L]; ``sorted=True`` adds the float32 arrays ``sorted_x`` [L x n] and ``sorted_rows`` [L x n_rows]
+    (every song's range sorted on its own).  x and rows are both numpy arrays or both torch CUDA tensors of one dtype (float16 /
+    bfloat16 / float32)."""
+    lib = K.load_library()
+    (px, n, d, ldx, cx, dev_x, kx), (py, m, dy, ldy, cy, dev_y, ky) = _kad_pair(x, rows, "rows", device)
+    if m > 0 and d != dy:
+        raise ValueError(f"sliced Wasserstein: x has D = {d}, the songs have D = {dy}")
+    if m > 0 and cx != cy:
+        raise ValueError("sliced Wasserstein: x and the songs must have the same dtype")
+    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+    if off.ndim != 1 or off.shape[0] < 2:
+        raise ValueError("sliced Wasserstein: offsets must be a 1-D sequence of S + 1 row indices, S >= 1")
+    S = off.shape[0] - 1
+    t = sliced_directions_array(directions, d)
+    L = t.shape[0]
+    out = {k: np.full(S, np.nan) for k in ("sw2_squared", "std_error", "max_sliced")}
+    out["max_index"] = np.full(S, -1, dtype=np.int64)
+    out["status"] = np.zeros(S, dtype=np.int32)
+    arrays = {}
+    if values:
+        arrays["values"] = np.full((S, L), np.nan)
+    if sorted:
+        arrays["sorted_x"] = np.zeros((L, n), dtype=np.float32)
+        arrays["sorted_rows"] = np.zeros((L, m), dtype=np.float32)
+    det = K.FadSlicedIndividualDetail(*(arrays[k].ctypes.data if k in arrays else None
+                                        for k in ("values", "sorted_x", "sorted_rows"))) if arrays else None
+    K.check(lib.fad_sliced_individual(px, n, ldx, py if m > 0 else None, m, max(ldy, d), off.ctypes.data_as(C.POINTER(C.c_int64)), S, d,
+                                      cx, dev_x, t.ctypes.data, L, out["sw2_squared"].ctypes.data, out["std_error"].ctypes.data,
+                                      out["max_sliced"].ctypes.data, out["max_index"].ctypes.data, out["status"].ctypes.data,
+                                      C.byref(det) if det is not None else None, int(device), K.current_stream_ptr(device)),
+            "fad_sliced_individual")
+    out.update(arrays)
+    out.update(n=n, projections=L)
+    return out
+
+
+def sliced_individual_last_plan() -> dict:
+    """``fad_sliced_individual_last_plan``: how this thread's last fad_sliced_individual call was laid out -> dict of ``chunks``,
+    ``directions_per_chunk``, ``units`` (resident units per direction), ``long_songs`` (songs beyond the resident capacity, on the
+    global sort), ``most_songs`` (in one unit) and ``capacity`` (C, keys a unit holds at most)."""
+    out = (C.c_int64 * 6)()
+    K.check(K.load_library().fad_sliced_individual_last_plan(out), "fad_sliced_individual_last_plan")
+    return dict(zip(("chunks", "directions_per_chunk", "units", "long_songs", "most_songs", "capacity"), map(int, out)))

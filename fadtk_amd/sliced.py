@@ -5,11 +5,16 @@ no blur, no iterations and no convergence question, on all rows, in O((n + m) lo
 directions has an honest estimate (``std_error``).  Everything runs in one GPU call (``fad_sliced_wasserstein``, include/fad_hip.h;
 DESIGN.md 4.17): projections on the matrix cores, a segmented radix sort, the match in float64.
 
-    python -m fadtk_amd.sliced <model> <baseline_dir> <eval_dir> [csv] [--projections 512] [--seed 0] [-w N]
+    python -m fadtk_amd.sliced <model> <baseline_dir> <eval_dir> [csv] [--projections 512] [--seed 0] [-w N] [--indiv]
 
 The directions are ``sliced_directions(D, projections, seed)``: standard normal, NOT normalised (the library divides each direction's
 value by its squared length).  ``fad_scale`` = D x ``sw2_squared`` reads beside FAD's mean term: a pure translation delta gives
 E W_l = |delta|^2 / D.  The CSV gets one row per call under CSV_HEADER.  Embeddings are cached as ``python -m fadtk_amd.kad`` caches them.
+
+Per song (``--indiv``): every file of the evaluation directory alone against the baseline, all songs in one GPU call
+(``fad_sliced_individual``), each with the bits ``calc_sliced_wasserstein(x, song)`` gives: the parameter-free per-song
+ranking beside FAD's and KAD's.  The CSV (default ``sliced-individual-results.csv``) gets one row per file under INDIV_CSV_HEADER,
+sorted by ``sw2_squared`` descending.
 """
 from __future__ import annotations
 
@@ -25,6 +30,9 @@ from .utils import PathLike
 
 log = logging.getLogger("fadtk_amd")
 CSV_HEADER = "model,baseline,eval,n,m,sw2_squared,sliced_w2,std_error,max_sliced,max_index,fad_scale,projections,seed\n"
+INDIV_CSV_HEADER = "file,rows,sw2_squared,sliced_w2,std_error,fad_scale\n"
+INDIV_CSV_NAME = "sliced-individual-results.csv"
+INDIV_BYTES = 4 << 30          # song rows per fad_sliced_individual call at most (a larger set is split: the same bits either way)
 MAX_PROJECTIONS = 65536
 
 
@@ -101,14 +109,107 @@ def calc_sliced_wasserstein(x, y, projections: int = 512, seed: int = 0, directi
     return out
 
 
-def check_csv(target: PathLike) -> None:
-    """Refuse (ValueError) an existing CSV whose first line is not CSV_HEADER."""
+def calc_sliced_wasserstein_individual(x, songs, projections: int = 512, seed: int = 0, directions=None, per_direction: bool = False,
+                                       device: int = 0, max_bytes: int = INDIV_BYTES) -> dict:
+    """The sliced 2-Wasserstein distance of every song [m_s x D] alone against the baseline x, every song in one GPU call
+    (``fad_sliced_individual``): song s gets the bits of ``calc_sliced_wasserstein(x, songs[s])`` with the same directions.  numpy arrays
+    or torch CUDA tensors of float16 / bfloat16 / float32; mixed dtypes go to float32; a song without rows is allowed and gives NaN.
+    -> dict of float64 arrays [S] ``sw2_squared``, ``sliced_w2``, ``std_error``, ``max_sliced``, ``max_index`` (-1 where there is
+    none), ``fad_scale``, ``rows`` and ``status`` (0, FAD_ERR_TOO_FEW_ROWS or FAD_ERR_NOT_FINITE: NaN values), plus ``n``,
+    ``projections``, ``seed`` (None with directions of one's own) and, with ``per_direction``, ``values`` [S x L].  Songs whose rows
+    together exceed ``max_bytes`` go in several calls of whole songs: with the same directions that cannot change a bit."""
+    sx = _shape_of(x)
+    songs = list(songs)
+    shapes = [_shape_of(y) for y in songs]
+    if len(sx) != 2:
+        raise ValueError(f"sliced Wasserstein needs a 2-D baseline, got shape {sx}")
+    if sx[1] < 1 or sx[1] > 2048:
+        raise ValueError(f"sliced Wasserstein: D = {sx[1]} is outside 1 .. 2048")
+    if sx[0] < 1:
+        raise ValueError(f"sliced Wasserstein needs at least 1 baseline row, got {sx[0]}")
+    if not songs:
+        raise ValueError("sliced Wasserstein per song needs at least 1 song")
+    for sh in shapes:
+        if len(sh) != 2 or (sh[0] > 0 and sh[1] != sx[1]):
+            raise ValueError(f"sliced Wasserstein: a song of shape {sh} against a baseline of D = {sx[1]}")
+        if sx[0] * sh[0] >= 2 ** 53:
+            raise ValueError(f"sliced Wasserstein: n m = {sx[0]} x {sh[0]} is 2^53 or more")
+    n, d = int(sx[0]), int(sx[1])
+    if directions is None:
+        directions = sliced_directions(d, projections, seed)
+    else:
+        from .hip import sliced_directions_array
+        directions = sliced_directions_array(directions, d)
+        seed = None
+    from . import hip
+    torch_in = hip.K._is_torch(x)
+    if torch_in:
+        import torch
+        if len({x.dtype, *(y.dtype for y in songs)}) > 1:
+            x, songs = x.float(), [y.float() for y in songs]
+        cat = lambda parts: torch.cat(parts, 0) if parts else x[:0]                  # noqa: E731
+    else:
+        x = np.asarray(x)
+        songs = [np.asarray(y) for y in songs]
+        if len({x.dtype, *(y.dtype for y in songs)}) > 1:
+            x, songs = x.astype(np.float32), [y.astype(np.float32) for y in songs]
+        cat = lambda parts: np.concatenate(parts, 0) if parts else x[:0]             # noqa: E731
+    row_bytes = max(1, d * (x.element_size() if torch_in else x.itemsize))
+    S, L = len(songs), directions.shape[0]
+    res = {k: np.full(S, np.nan) for k in ("sw2_squared", "std_error", "max_sliced")}
+    res["max_index"] = np.full(S, -1.0)
+    status = np.zeros(S)
+    values = np.full((S, L), np.nan) if per_direction else None
+    s0 = 0
+    while s0 < S:                                 # batches of whole songs under the byte budget (at least one song each)
+        s1, size = s0, 0
+        while s1 < S and (s1 == s0 or size + shapes[s1][0] * row_bytes <= max_bytes):
+            size += shapes[s1][0] * row_bytes
+            s1 += 1
+        part = [y.reshape(-1, d) if shapes[s0 + i][0] == 0 else y for i, y in enumerate(songs[s0:s1])]
+        off = np.concatenate([[0], np.cumsum([shapes[s][0] for s in range(s0, s1)], dtype=np.int64)])
+        r = hip.sliced_individual(x, cat(part), off, directions, device=device, values=per_direction)
+        for k in res:
+            res[k][s0:s1] = r[k]
+        status[s0:s1] = r["status"]
+        if per_direction:
+            values[s0:s1] = r["values"]
+        s0 = s1
+    out = {"sw2_squared": res["sw2_squared"], "sliced_w2": np.sqrt(np.maximum(res["sw2_squared"], 0.0)), "std_error": res["std_error"],
+           "max_sliced": res["max_sliced"], "max_index": res["max_index"], "fad_scale": d * res["sw2_squared"],
+           "rows": np.array([float(sh[0]) for sh in shapes]), "status": status, "n": n, "projections": int(L), "seed": seed}
+    if per_direction:
+        out["values"] = values
+    return out
+
+
+def check_csv(target: PathLike, header: str = CSV_HEADER) -> None:
+    """Refuse (ValueError) an existing CSV whose first line is not ``header`` (CSV_HEADER; INDIV_CSV_HEADER for the per-song file)."""
     if Path(target).is_file():
         with open(target) as fh:
             first = fh.readline()
-        if first.rstrip("\r\n") != CSV_HEADER.rstrip("\n"):
+        if first.rstrip("\r\n") != header.rstrip("\n"):
             raise ValueError(f"{target} has the header {first.strip()!r}; a row of the sliced Wasserstein distance goes under "
-                             f"{CSV_HEADER.strip()!r}: write it to another file")
+                             f"{header.strip()!r}: write it to another file")
+
+
+def indiv_csv_row(file, res: dict, s: int) -> str:
+    """One CSV row (no line end) of song ``s`` of a calc_sliced_wasserstein_individual result under INDIV_CSV_HEADER."""
+    return (f"{str(file).replace(',', '_')},{int(res['rows'][s])},{float(res['sw2_squared'][s])!r},{float(res['sliced_w2'][s])!r},"
+            f"{float(res['std_error'][s])!r},{float(res['fad_scale'][s])!r}")
+
+
+def write_indiv_csv(target: PathLike, files, res: dict) -> int:
+    """The per-song CSV: INDIV_CSV_HEADER, then one row per file of ``files`` whose status is 0, sorted by ``sw2_squared`` descending
+    (ties in the order of ``files``).  A file with another header is refused, untouched; one with this header is replaced.  -> the
+    rows written."""
+    check_csv(target, INDIV_CSV_HEADER)
+    keep = [s for s in range(len(files)) if res["status"][s] == 0]
+    keep.sort(key=lambda s: -res["sw2_squared"][s])
+    target = Path(target)
+    target.parent.mkdir(parents=True, exist_ok=True)
+    target.write_text(INDIV_CSV_HEADER + "".join(indiv_csv_row(files[s], res, s) + "\n" for s in keep))
+    return len(keep)
 
 
 def append_csv(target: PathLike, row: str) -> None:
@@ -148,6 +249,43 @@ class SlicedWasserstein:
         return calc_sliced_wasserstein(x, y, projections=self.projections, seed=self.seed, per_direction=per_direction,
                                        device=self.device_index)
 
+    def score_individual(self, baseline: PathLike, eval_dir: PathLike, csv: PathLike = INDIV_CSV_NAME) -> Path:
+        """calc_sliced_wasserstein_individual of every file of ``eval_dir`` against all rows of ``baseline``, written to ``csv`` under
+        INDIV_CSV_HEADER, sorted by ``sw2_squared`` descending.  Files whose embedding is missing, unreadable, of another D, empty or not
+        finite are logged and dropped, as KAD's are.  A CSV with another header is refused before any work."""
+        check_csv(csv, INDIV_CSV_HEADER)
+        x = self.kad.load_rows(baseline)
+        files = sorted(Path(eval_dir).glob("*.*"))
+        keep = []
+        for f in files:
+            try:
+                e = self.kad.fad.read_embedding_file(f)
+            except Exception as err:      # noqa: BLE001
+                log.error(f"An error occurred calculating the individual sliced Wasserstein distance using model {self.ml.name} on file {f}")
+                log.error(err)
+                continue
+            if e.ndim != 2 or e.shape[1] != x.shape[1]:
+                log.error(f"Embedding of {f} has shape {e.shape}; expected [*, {x.shape[1]}]")
+            elif e.shape[0] < 1:
+                log.error(f"Individual sliced Wasserstein distance of {f} dropped: no frames")
+            else:
+                keep.append((f, e))
+        dts = {x.dtype, *(e.dtype for _, e in keep)}
+        if len(dts) > 1 or np.float64 in dts:      # one dtype for the call; float64 caches are narrowed, as score() does
+            x, keep = x.astype(np.float32), [(f, e.astype(np.float32)) for f, e in keep]
+        csv = Path(csv)
+        if not keep:
+            write_indiv_csv(csv, [], {"status": [], "sw2_squared": []})
+            return csv
+        res = calc_sliced_wasserstein_individual(x, [e for _, e in keep], projections=self.projections, seed=self.seed,
+                                                 device=self.device_index)
+        for (f, _), st in zip(keep, res["status"]):
+            if st != 0:
+                log.error(f"An error occurred calculating the individual sliced Wasserstein distance using model {self.ml.name} on file "
+                          f"{f} (status {int(st)}: {'no frames' if st == -6 else 'non-finite rows'})")
+        write_indiv_csv(csv, [f for f, _ in keep], res)
+        return csv
+
 
 def main(argv=None):
     from .cli import _registry, _setup_logging
@@ -158,24 +296,32 @@ def main(argv=None):
     p.add_argument("model", type=str, choices=list(models), help="embedding model")
     p.add_argument("baseline", type=str, help="baseline dataset directory")
     p.add_argument("eval", type=str, help="directory to evaluate")
-    p.add_argument("csv", type=str, nargs="?", help="append the result to this CSV")
+    p.add_argument("csv", type=str, nargs="?", help=f"append the result to this CSV; with --indiv: where the per-song rows go "
+                   f"(default {INDIV_CSV_NAME})")
     p.add_argument("--projections", type=int, default=512, help="random directions (default 512)")
     p.add_argument("--seed", type=int, default=0, help="seed of the directions (default 0)")
     p.add_argument("-w", "--workers", type=int, default=8, help="number of workers")
+    p.add_argument("--indiv", action="store_true", help="one row per file of the eval directory")
     a = p.parse_args(argv)
     try:
         check_params(a.projections, a.seed)
     except ValueError as e:
         p.error(str(e))
     model = models[a.model]
+    if a.indiv:
+        a.csv = a.csv or INDIV_CSV_NAME
     if a.csv:
-        check_csv(a.csv)                                  # before any work: a CSV with another header is refused
+        check_csv(a.csv, INDIV_CSV_HEADER if a.indiv else CSV_HEADER)   # before any work: a CSV with another header is refused
 
     from .fad_batch import cache_embedding_files
     for dataset in (a.baseline, a.eval):
         if Path(dataset).is_dir():
             cache_embedding_files(dataset, model, workers=a.workers)
     sw = SlicedWasserstein(model, audio_load_worker=a.workers, load_model=False, projections=a.projections, seed=a.seed)
+    if a.indiv:
+        csv = sw.score_individual(a.baseline, a.eval, a.csv)
+        log.info(f"Individual sliced Wasserstein distances {model.name} of {a.eval} against {a.baseline} saved to {csv}")
+        return
     res = sw.score(a.baseline, a.eval)
     log.info(f"The sliced Wasserstein distance {model.name} between {a.baseline} and {a.eval} is: SW2^2 = {res['sw2_squared']} "
              f"+- {res['std_error']:.3g} over {res['projections']} directions (SW2 {res['sliced_w2']}, on FAD's scale {res['fad_scale']}, "

@@ -682,6 +682,47 @@ int fad_sliced_wasserstein(const void* x, int64_t n, int64_t ldx, const void* y,
                            int on_device, const float* directions /* host, [L x d] */, int projections,
                            fad_sliced_result_t* out, fad_sliced_detail_t* detail /* may be NULL */, int device, void* stream);
 
+/* ------------------------------------------------------------------ per-song sliced 2-Wasserstein distance against a baseline
+ * Not in the reference.  Every song s = rows[offsets[s] .. offsets[s + 1]) (m_s rows) against the baseline x [n x d], in one call: song
+ * s gets, bit for bit, what fad_sliced_wasserstein(x, song_s) returns with the same directions -- W_l^s (detail->values, song-major
+ * [n_songs x L]), out_sw2, out_std_error, out_max_sliced and out_max_index -- on every run, for any chunking of the directions,
+ * wherever the song sits among the rows and whatever its neighbours are.  The same directions, rounding, q_l, float32 projections and
+ * float64 match in the same fixed order (the larger of x and song s leads, x at m_s = n; per leading element over its j ascending;
+ * blocks of 256 leading elements by the halving tree; the blocks in index order; one division S / ((double)(n m_s) q_l)); the
+ * statistics over l in index order on the host.  No floating-point atomics.
+ * The baseline is packed once and its projections are sorted once per direction; all song rows are packed once and projected in one
+ * launch per chunk; every song of at most C = 4096 rows is sorted inside one workgroup's LDS (csrc/sliced_song_sort.h: units of
+ * consecutive songs, at most C keys and 256 songs each, one coalesced read and one coalesced write); longer songs go through
+ * csrc/sliced_sort.h's global sort one by one; one workgroup per (direction, song) matches.  The match walks the whole sorted baseline
+ * for every song: O(L sum_s max(n, m_s)).
+ *   detail (may be NULL; each array NULL or host): values [n_songs x L]; sorted_x [L x n]; sorted_rows [L x n_rows], every song's
+ *   range of every direction sorted on its own.
+ * out_status[s]: FAD_OK; FAD_ERR_TOO_FEW_ROWS for a song without rows; FAD_ERR_NOT_FINITE for a song with a NaN/Inf row norm or a
+ * projection that is not finite in float32 -- both with NaN outputs (values included) and max_index = -1; the other songs do not
+ * depend on them.  m_s = 1 is a valid song.
+ * Refusals: dtype, d, pitches, projections and directions as fad_sliced_wasserstein; NULL x, offsets, directions or per-song output,
+ * NULL rows with n_rows > 0, n_songs < 1, n_rows < 0 or > 2^31 - 129, offsets that do not start at 0, end at n_rows or that decrease,
+ * n m_s >= 2^53 for a song -> FAD_ERR_INVALID; n < 1 -> FAD_ERR_TOO_FEW_ROWS; a NaN/Inf baseline row norm or a baseline projection that
+ * is not finite -> FAD_ERR_NOT_FINITE.  Argument errors come before any device call; any refusal leaves every output untouched
+ * (results are staged in host memory until the call succeeds).
+ * Workspace: the two images and the directions'; the song table; then, per direction of a chunk,
+ *   4 (n_pad + r_pad + t_pad) + 4 (count_words + 256) + 8 n_songs  bytes,
+ * n_pad and r_pad the baseline's and the song rows' counts rounded up to 128, t_pad (the global sort's second buffer) = n_pad, or the
+ * larger of n_pad and r_pad when a song has more than C rows, count_words = 256 per 2048 rows of the baseline or of the longest such
+ * song, whichever is larger.  Directions go in chunks so that this stays within 1 GiB, or within FAD_SLICED_WORKSPACE bytes (read at
+ * the start of every call; for tests); a chunk holds at least one direction.  Synchronises `stream`. */
+typedef struct fad_sliced_individual_detail {
+    double* values;      /* [n_songs x L]   W_l^s, may be NULL */
+    float* sorted_x;     /* [L x n]         may be NULL */
+    float* sorted_rows;  /* [L x n_rows]    may be NULL */
+} fad_sliced_individual_detail_t;
+int fad_sliced_individual(const void* x, int64_t n, int64_t ldx, const void* rows, int64_t n_rows, int64_t ldy,
+                          const int64_t* offsets, int64_t n_songs, int64_t d, int dtype, int on_device,
+                          const float* directions /* host, [L x d] */, int projections,
+                          double* out_sw2, double* out_std_error, double* out_max_sliced, int64_t* out_max_index,
+                          int32_t* out_status /* each [n_songs], host */,
+                          fad_sliced_individual_detail_t* detail /* may be NULL */, int device, void* stream);
+
 /* ------------------------------------------------------------------ diagnostics (NOT part of the drop-in surface)
  * Nothing in fadtk corresponds to these two calls and no binding of the reference needs them: they exist for bench.py's
  * roofline object (HIP events around the tile kernel on the stream it is launched on) and for the GPU tests that check
@@ -716,6 +757,11 @@ int fad_kad_last_plan(int64_t out[5]);
  * segment of n keys takes W workgroups (2048 keys each), -G when n <= 256 and one workgroup owns G > 1 segments.  The chunking follows
  * FAD_SLICED_WORKSPACE (above), as fad_kad_last_plan's launch cut follows FAD_KAD_LAUNCH_BUDGET. */
 int fad_sliced_last_plan(int64_t out[4]);
+
+/* Diagnostic: how the last fad_sliced_individual call of this thread was laid out.  out = { chunks, directions per chunk, resident
+ * units per direction, songs on the long path (more than C rows), most songs in one unit, C }; all 0 when the call was refused
+ * before it planned. */
+int fad_sliced_individual_last_plan(int64_t out[6]);
 
 /* A HIP stream confined to a subset of the device's CUs (hipExtStreamCreateWithCUMask; `mask` = `words` x 32 bits, bit i = CU i in
  * the runtime's numbering, which on this 8-XCD part walks the XCDs first: bit i -> XCD i % 8).  bench.py's --chain-cus layout
