@@ -40,7 +40,8 @@ def __getattr__(name):
     if name in ("SinkhornDivergence", "calc_sinkhorn_divergence"):      # lazy, as KAD's
         from . import sinkhorn
         return getattr(sinkhorn, name)
-    if name in ("SlicedWasserstein", "calc_sliced_wasserstein", "calc_sliced_wasserstein_individual", "sliced_directions"):      # lazy, as KAD's
+    if name in ("SlicedWasserstein", "calc_sliced_wasserstein", "calc_sliced_wasserstein_individual", "calc_sliced_wasserstein_shares",
+                "sliced_directions"):      # lazy, as KAD's
         from . import sliced
         return getattr(sliced, name)
     if name == "cache_embedding_files":

@@ -116,6 +116,10 @@ class FadSlicedDetail(C.Structure):
     _fields_ = [("values", C.c_void_p), ("sorted_x", C.c_void_p), ("sorted_y", C.c_void_p)]
 
 
+class FadSlicedSharesDetail(C.Structure):
+    _fields_ = [("values", C.c_void_p), ("sorted_x", C.c_void_p), ("sorted_y", C.c_void_p), ("index_x", C.c_void_p), ("index_y", C.c_void_p)]
+
+
 class FadSlicedIndividualDetail(C.Structure):
     _fields_ = [("values", C.c_void_p), ("sorted_x", C.c_void_p), ("sorted_rows", C.c_void_p)]
 
@@ -207,6 +211,8 @@ SIGNATURES = {
                                   C.c_int, _P, _P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, _P]),
     "fad_sliced_wasserstein": (C.c_int, [_P, _I64, _I64, _P, _I64, _I64, _I64, C.c_int, C.c_int, _P, C.c_int, C.POINTER(FadSlicedResult),
                                          C.POINTER(FadSlicedDetail), C.c_int, _P]),
+    "fad_sliced_shares": (C.c_int, [_P, _I64, _I64, _P, _I64, _I64, _I64, C.c_int, C.c_int, _P, C.c_int, C.POINTER(FadSlicedResult), _P, _P,
+                                    C.POINTER(FadSlicedSharesDetail), C.c_int, _P]),
     "fad_sliced_last_plan": (C.c_int, [C.POINTER(_I64)]),
     "fad_sliced_individual": (C.c_int, [_P, _I64, _I64, _P, _I64, _I64, C.POINTER(_I64), _I64, _I64, C.c_int, C.c_int, _P, C.c_int,
                                         _P, _P, _P, _P, _P, C.POINTER(FadSlicedIndividualDetail), C.c_int, _P]),

@@ -28,6 +28,7 @@
 #include "kid_tiles.h"
 #include "nn_vote.h"
 #include "sliced_sort.h"
+#include "sliced_sort_pairs.h"
 #include "sliced_song_sort.h"
 
 #include <algorithm>
@@ -813,6 +814,75 @@ __global__ void __launch_bounds__(256) sliced_finish_kernel(const double* __rest
     double s = 0.0;
     for (int64_t k = 0; k < nblk; ++k) s += slots[l * nblk + k];
     S[l] = s;
+}
+
+// ------------------------------------------------------------------------------------ sliced Wasserstein per-row shares
+// sliced_match_kernel that also keeps every leading element's sum: the per-thread s (over j ascending), divided once by den[l] =
+// (double)(n m) q_l, goes to cost[l][ra[l][i]], ra the row at rank i (ssort::sort_segment_pairs).  ra is a permutation of 0 .. na - 1, so
+// every row of a direction is written exactly once: plain 8-byte stores.  The tree and the slot are sliced_match_kernel's, so
+// sliced_finish_kernel gives S_l with the bits of the plain call.
+__global__ void __launch_bounds__(kMatchBlock) sliced_match_cost_kernel(const float* __restrict__ a, const uint32_t* __restrict__ ra,
+                                                                        int64_t pa, int64_t na, const float* __restrict__ b, int64_t pb,
+                                                                        int64_t nb, int64_t nblk, const double* __restrict__ den,
+                                                                        double* __restrict__ slots, double* __restrict__ cost) {
+#pragma clang fp contract(off)
+    __shared__ double red[kMatchBlock];
+    const int64_t l = blockIdx.x / nblk, k = blockIdx.x % nblk, i = k * kMatchBlock + threadIdx.x;
+    double s = 0.0;
+    if (i < na) {
+        const double ai = (double)a[l * pa + i];
+        const int64_t lo = i * nb, hi = lo + nb, j0 = lo / na, j1 = (hi - 1) / na;
+        for (int64_t j = j0; j <= j1 && j < nb; ++j) {
+            const int64_t w = (hi < (j + 1) * na ? hi : (j + 1) * na) - (lo > j * na ? lo : j * na);
+            const double diff = ai - (double)b[l * pb + j];
+            const double sq = diff * diff;
+            const double term = (double)w * sq;
+            s += term;
+        }
+        const int64_t row = ra[l * pa + i];
+        if (row < na) cost[l * pa + row] = s / den[l];                                 // always true; keeps a wrong index inside the row
+    }
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = kMatchBlock / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) slots[blockIdx.x] = red[0];
+}
+
+// The other side: one thread per element j of the sorted smaller set b (y at n == m) sums the same terms w_ij (a_i - b_j)^2 over its
+// i0 .. i1 of the sorted larger set a, i ascending, and stores the sum / den[l] at cost[l][rb[l][j]].  Grid: lc * jblk workgroups.
+__global__ void __launch_bounds__(kMatchBlock) sliced_other_cost_kernel(const float* __restrict__ a, int64_t pa, int64_t na,
+                                                                        const float* __restrict__ b, const uint32_t* __restrict__ rb,
+                                                                        int64_t pb, int64_t nb, int64_t jblk,
+                                                                        const double* __restrict__ den, double* __restrict__ cost) {
+#pragma clang fp contract(off)
+    const int64_t l = blockIdx.x / jblk, j = (blockIdx.x % jblk) * kMatchBlock + threadIdx.x;
+    if (j >= nb) return;
+    const double bj = (double)b[l * pb + j];
+    const int64_t lo = j * na, hi = lo + na, i0 = lo / nb, i1 = (hi - 1) / nb;
+    double s = 0.0;
+    for (int64_t i = i0; i <= i1 && i < na; ++i) {
+        const int64_t w = (hi < (i + 1) * nb ? hi : (i + 1) * nb) - (lo > i * nb ? lo : i * nb);
+        const double diff = (double)a[l * pa + i] - bj;
+        const double sq = diff * diff;
+        const double term = (double)w * sq;
+        s += term;
+    }
+    const int64_t row = rb[l * pb + j];
+    if (row < nb) cost[l * pb + row] = s / den[l];                                     // always true; keeps a wrong index inside the row
+}
+
+// acc[row] += cost[l][row] over the lc directions of the chunk, l ascending: one thread per row, one running float64 sum per row that
+// lives across the chunks
+__global__ void __launch_bounds__(256) sliced_share_sum_kernel(const double* __restrict__ cost, int64_t pitch, int64_t n, int64_t lc,
+                                                               double* __restrict__ acc) {
+    const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (row >= n) return;
+    double s = acc[row];
+    for (int64_t l = 0; l < lc; ++l) s += cost[l * pitch + row];
+    acc[row] = s;
 }
 
 // ------------------------------------------------------------------------------- per-song sliced Wasserstein distance
@@ -3079,15 +3149,18 @@ static SlicedPlan& sliced_plan_value() {
     return p;
 }
 
-// One set's side of a chunk: projections of lc directions from direction l0 on, then the segmented sort.  Enqueued only.
+// One set's side of a chunk: projections of lc directions from direction l0 on, then the segmented sort -- keys only, or with `idx`
+// the key-index sort that leaves the row of every rank in idx.  Enqueued only.
 static int sliced_project_sort(const Ctx& cx, const Packed& set, const char* theta, const float* zeros, int64_t l0, int64_t lc, float* P,
-                               int64_t ppitch, float* tmp, uint32_t* counts, uint32_t* bases, unsigned int* flag) {
+                               int64_t ppitch, float* tmp, uint32_t* idx, uint32_t* idx_tmp, uint32_t* counts, uint32_t* bases,
+                               unsigned int* flag) {
     ProjArgs p{};
     p.th = theta + l0 * set.pitch; p.rows = set.img; p.zeros = zeros; p.pitch = set.pitch; p.nchunks = set.nchunks;
     p.TI = kad::blocks(lc); p.TJ = kad::blocks(set.n); p.lc = lc; p.n = set.n; p.P = P; p.ppitch = ppitch; p.flag = flag;
     const unsigned int grid = (unsigned int)std::min<int64_t>(p.TI * p.TJ, grid_cap(cx.device));
     FAD_TRY(with_dtype(cx.dtype, [&](auto dt) { sliced_project_kernel<dt><<<grid, kThreads, kLdsProject, cx.st>>>(p); }));
-    FAD_HIP_TRY(ssort::sort_segments(P, tmp, ppitch, set.n, lc, counts, bases, cx.st));
+    if (idx) FAD_HIP_TRY(ssort::sort_segment_pairs(P, tmp, idx, idx_tmp, ppitch, set.n, lc, counts, bases, cx.st));
+    else FAD_HIP_TRY(ssort::sort_segments(P, tmp, ppitch, set.n, lc, counts, bases, cx.st));
     return FAD_OK;
 }
 
@@ -3125,6 +3198,179 @@ static int sliced_direction_image(const float* directions, int64_t L, int64_t d,
         if (!(ql > 0) || !std::isfinite(ql))
             return set_error(FAD_ERR_INVALID, "%s: direction %lld, rounded to the rows' dtype, has the squared length %g", who, (long long)l, ql);
         (*q)[(size_t)l] = ql;
+    }
+    return FAD_OK;
+}
+
+// What a call over the two whole sets writes besides the result: fad_sliced_wasserstein's detail and, with `shares`,
+// fad_sliced_shares' per-row arrays.  All host; every pointer but the two shares may be NULL.
+struct SlicedOut {
+    double* values; float* sorted_x; float* sorted_y;
+    bool shares;
+    double* share_x; double* share_y; int32_t* index_x; int32_t* index_y;
+};
+
+// fad_sliced_wasserstein and fad_sliced_shares: one body.  Without o.shares the launches are the keys-only sort and sliced_match_kernel;
+// with it the key-index sort, the two cost kernels and the per-row sums -- and the same slots, S_l and statistics either way.
+static int sliced_sets(const char* who, const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype,
+                       int on_device, const float* directions, int projections, fad_sliced_result_t* out, const SlicedOut& o, int device,
+                       void* stream) {
+    if (!x || !y) return set_error(FAD_ERR_INVALID, "%s: NULL rows", who);
+    if (!directions) return set_error(FAD_ERR_INVALID, "%s: NULL directions", who);
+    if (dtype == FAD_F64) return set_error(FAD_ERR_INVALID, "%s: float64 rows are not supported; cast to float32 (or float16 / bfloat16)", who);
+    if (dtype != FAD_F16 && dtype != FAD_BF16 && dtype != FAD_F32) return set_error(FAD_ERR_INVALID, "%s: unknown dtype %d", who, dtype);
+    if (d < 1 || d > 2048) return set_error(FAD_ERR_INVALID, "%s: D = %lld is outside 1 .. 2048", who, (long long)d);
+    if (ldx < d || ldy < d) return set_error(FAD_ERR_INVALID, "%s: row pitch %lld / %lld < D = %lld", who, (long long)ldx, (long long)ldy, (long long)d);
+    if (projections < 1 || projections > 65536) return set_error(FAD_ERR_INVALID, "%s: %d projections, outside 1 .. 65536", who, projections);
+    if (n < 1 || m < 1) return set_error(FAD_ERR_TOO_FEW_ROWS, "%s: needs at least 1 row per set, got %lld and %lld", who, (long long)n, (long long)m);
+    if (n > INT32_MAX - kTile || m > INT32_MAX - kTile)
+        return set_error(FAD_ERR_INVALID, "%s: %lld and %lld rows (at most %d per set)", who, (long long)n, (long long)m, INT32_MAX - kTile);
+    if (n > (((int64_t)1 << 53) - 1) / m)
+        return set_error(FAD_ERR_INVALID, "%s: n m = %lld x %lld is 2^53 or more: the integer weights would not be exact in float64", who,
+                         (long long)n, (long long)m);
+    const int64_t L = projections;
+    const size_t es = dtype_size(dtype);
+    const int64_t dp = depth_elems(d, dtype), tpitch = dp * (int64_t)es, l_img = (kad::blocks(L) + 1) * kTile;
+
+    // the directions rounded to the rows' dtype into their zero-padded image, and q_l from the rounded values, before any device call
+    std::vector<char> timg;
+    std::vector<double> q;
+    FAD_TRY(sliced_direction_image(directions, L, d, dtype, tpitch, l_img, who, &timg, &q));
+    const char* env = getenv("FAD_SLICED_WORKSPACE");
+    char* end = nullptr;
+    const long long env_v = env && *env ? strtoll(env, &end, 10) : 0;
+    const int64_t budget = end && *end == 0 && env_v > 0 ? (int64_t)env_v : kSlicedWorkspace;
+
+    Ctx cx;
+    FAD_TRY(cx.open(dtype, FAD_KAD_GAUSSIAN, device, stream));
+    KadWorkspace& ws = *cx.ws;
+    const hipStream_t st = cx.st;
+    Packed px, py;                                             // each set packed once, its norms checked finite
+    FAD_TRY(pack_set(cx, 0, x, n, ldx, d, on_device, &px));
+    FAD_TRY(pack_set(cx, 1, y, m, ldy, d, on_device, &py));
+    FAD_TRY(ws.sliced_theta.reserve(timg.size()));
+    FAD_HIP_TRY(hipMemcpyAsync(ws.sliced_theta.p, timg.data(), timg.size(), hipMemcpyHostToDevice, st));
+
+    // the chunk: lc directions' projections of both sets, the sort's second buffer, its counts, the match's slots; with shares also
+    // the rows at every rank of both sets, the index sort's second buffer and a float64 cost per row of both sets
+    const bool x_larger = n >= m, sh = o.shares;
+    const int64_t n_pad = kad::blocks(n) * kTile, m_pad = kad::blocks(m) * kTile, t_pad = std::max(n_pad, m_pad);
+    const int64_t na = x_larger ? n : m, nb = x_larger ? m : n, nblk = cdiv(na, kMatchBlock), jblk = cdiv(nb, kMatchBlock);
+    const int64_t count_words = std::max(ssort::counts_elems(n, 1), ssort::counts_elems(m, 1));
+    const int64_t per_dir = 4 * (n_pad + m_pad + t_pad) + 4 * (count_words + ssort::kRadix) + 8 * nblk +
+                            (sh ? 4 * (n_pad + m_pad + t_pad) + 8 * (n_pad + m_pad) : 0);
+    const int64_t lc = std::max<int64_t>(1, std::min<int64_t>(L, budget / per_dir));
+    const int64_t chunks = cdiv(L, lc);
+    Carve cv;
+    const auto px_r = cv.add<float>(lc * n_pad), py_r = cv.add<float>(lc * m_pad), tmp_r = cv.add<float>(lc * t_pad);
+    const auto counts_r = cv.add<uint32_t>(lc * count_words), bases_r = cv.add<uint32_t>(lc * ssort::kRadix);
+    const auto slots_r = cv.add<double>(lc * nblk), s_r = cv.add<double>(L);
+    const auto zeros_r = cv.add<float>(std::max(t_pad, l_img));
+    const auto flag_r = cv.add<unsigned int>(64);
+    const auto ix_r = cv.add<uint32_t>(sh ? lc * n_pad : 0), iy_r = cv.add<uint32_t>(sh ? lc * m_pad : 0);
+    const auto itmp_r = cv.add<uint32_t>(sh ? lc * t_pad : 0);
+    const auto cx_r = cv.add<double>(sh ? lc * n_pad : 0), cy_r = cv.add<double>(sh ? lc * m_pad : 0);
+    const auto den_r = cv.add<double>(sh ? L : 0), acc_r = cv.add<double>(sh ? n + m : 0);
+    FAD_TRY(cv.reserve(ws.sliced));
+    FAD_HIP_TRY(hipMemsetAsync(cv.ptr(zeros_r), 0, (size_t)std::max(t_pad, l_img) * sizeof(float), st));
+    FAD_HIP_TRY(hipMemsetAsync(cv.ptr(flag_r), 0, 64 * sizeof(unsigned int), st));
+    const ssort::Plan sp = ssort::plan(n, lc);
+    sliced_plan_value() = SlicedPlan{chunks, lc, ssort::kPasses, sp.G > 1 ? -sp.G : sp.W};
+
+    // W_l's denominator (double)(n m) q_l: the per-row costs are divided by it on the device, S_l on the host below
+    const double nm = (double)(n * m);
+    std::vector<double> den((size_t)L);
+    for (int64_t l = 0; l < L; ++l) den[(size_t)l] = nm * q[(size_t)l];
+    if (sh) {
+        FAD_HIP_TRY(hipMemcpyAsync(cv.ptr(den_r), den.data(), (size_t)L * sizeof(double), hipMemcpyHostToDevice, st));
+        FAD_HIP_TRY(hipMemsetAsync(cv.ptr(acc_r), 0, (size_t)(n + m) * sizeof(double), st));
+    }
+
+    // the sorted arrays are staged on the host: a refusal after the first chunk must leave the caller's arrays as they were
+    std::vector<float> sx, sy;
+    std::vector<int32_t> hx, hy;
+    if (o.sorted_x) sx.resize((size_t)(L * n));
+    if (o.sorted_y) sy.resize((size_t)(L * m));
+    if (o.index_x) hx.resize((size_t)(L * n));
+    if (o.index_y) hy.resize((size_t)(L * m));
+    const char* theta = static_cast<const char*>(ws.sliced_theta.p);
+    float* Px = cv.ptr(px_r);
+    float* Py = cv.ptr(py_r);
+    uint32_t* Ix = cv.ptr(ix_r);
+    uint32_t* Iy = cv.ptr(iy_r);
+    double* acc_x = cv.ptr(acc_r);
+    double* acc_y = acc_x + n;
+    for (int64_t l0 = 0; l0 < L; l0 += lc) {
+        const int64_t cur = std::min(lc, L - l0);
+        FAD_TRY(sliced_project_sort(cx, px, theta, cv.ptr(zeros_r), l0, cur, Px, n_pad, cv.ptr(tmp_r), sh ? Ix : nullptr, cv.ptr(itmp_r),
+                                    cv.ptr(counts_r), cv.ptr(bases_r), cv.ptr(flag_r)));
+        FAD_TRY(sliced_project_sort(cx, py, theta, cv.ptr(zeros_r), l0, cur, Py, m_pad, cv.ptr(tmp_r), sh ? Iy : nullptr, cv.ptr(itmp_r),
+                                    cv.ptr(counts_r), cv.ptr(bases_r), cv.ptr(flag_r)));
+        const float* A = x_larger ? Px : Py;
+        const float* B = x_larger ? Py : Px;
+        const int64_t a_pad = x_larger ? n_pad : m_pad, b_pad = x_larger ? m_pad : n_pad;
+        if (sh) {
+            sliced_match_cost_kernel<<<(unsigned int)(cur * nblk), kMatchBlock, 0, st>>>(A, x_larger ? Ix : Iy, a_pad, na, B, b_pad, nb, nblk,
+                                                                                         cv.ptr(den_r) + l0, cv.ptr(slots_r),
+                                                                                         cv.ptr(x_larger ? cx_r : cy_r));
+            FAD_HIP_TRY(hipGetLastError());
+            sliced_other_cost_kernel<<<(unsigned int)(cur * jblk), kMatchBlock, 0, st>>>(A, a_pad, na, B, x_larger ? Iy : Ix, b_pad, nb, jblk,
+                                                                                         cv.ptr(den_r) + l0, cv.ptr(x_larger ? cy_r : cx_r));
+            FAD_HIP_TRY(hipGetLastError());
+            sliced_share_sum_kernel<<<(unsigned int)cdiv(n, 256), 256, 0, st>>>(cv.ptr(cx_r), n_pad, n, cur, acc_x);
+            sliced_share_sum_kernel<<<(unsigned int)cdiv(m, 256), 256, 0, st>>>(cv.ptr(cy_r), m_pad, m, cur, acc_y);
+        } else {
+            sliced_match_kernel<<<(unsigned int)(cur * nblk), kMatchBlock, 0, st>>>(A, a_pad, na, B, b_pad, nb, nblk, cv.ptr(slots_r));
+        }
+        FAD_HIP_TRY(hipGetLastError());
+        sliced_finish_kernel<<<(unsigned int)cdiv(cur, 256), 256, 0, st>>>(cv.ptr(slots_r), nblk, cur, cv.ptr(s_r) + l0);
+        FAD_HIP_TRY(hipGetLastError());
+        if (!sx.empty())
+            FAD_HIP_TRY(hipMemcpy2DAsync(sx.data() + l0 * n, (size_t)n * 4, Px, (size_t)n_pad * 4, (size_t)n * 4, (size_t)cur, hipMemcpyDeviceToHost, st));
+        if (!sy.empty())
+            FAD_HIP_TRY(hipMemcpy2DAsync(sy.data() + l0 * m, (size_t)m * 4, Py, (size_t)m_pad * 4, (size_t)m * 4, (size_t)cur, hipMemcpyDeviceToHost, st));
+        if (!hx.empty())
+            FAD_HIP_TRY(hipMemcpy2DAsync(hx.data() + l0 * n, (size_t)n * 4, Ix, (size_t)n_pad * 4, (size_t)n * 4, (size_t)cur, hipMemcpyDeviceToHost, st));
+        if (!hy.empty())
+            FAD_HIP_TRY(hipMemcpy2DAsync(hy.data() + l0 * m, (size_t)m * 4, Iy, (size_t)m_pad * 4, (size_t)m * 4, (size_t)cur, hipMemcpyDeviceToHost, st));
+    }
+    std::vector<double> S((size_t)L), acc(sh ? (size_t)(n + m) : 0);
+    unsigned int flag = 0;
+    FAD_HIP_TRY(hipMemcpyAsync(S.data(), cv.ptr(s_r), (size_t)L * sizeof(double), hipMemcpyDeviceToHost, st));
+    FAD_HIP_TRY(hipMemcpyAsync(&flag, cv.ptr(flag_r), sizeof(flag), hipMemcpyDeviceToHost, st));
+    if (sh) FAD_HIP_TRY(hipMemcpyAsync(acc.data(), acc_x, (size_t)(n + m) * sizeof(double), hipMemcpyDeviceToHost, st));
+    FAD_HIP_TRY(hipStreamSynchronize(st));
+    if (flag) return set_error(FAD_ERR_NOT_FINITE, "%s: a projection is not finite in float32", who);
+
+    // W_l = S_l / (n m q_l), one division; mean, spread and maximum over l in index order
+    std::vector<double> W((size_t)L);
+    double sum = 0.0, best = -INFINITY;
+    int64_t best_l = 0;
+    for (int64_t l = 0; l < L; ++l) {
+        const double w = S[(size_t)l] / den[(size_t)l];
+        W[(size_t)l] = w;
+        sum += w;
+        if (w > best) { best = w; best_l = l; }
+    }
+    const double mean = sum / (double)L;
+    double dev2 = 0.0;
+    for (int64_t l = 0; l < L; ++l) {
+        const double dv = W[(size_t)l] - mean;
+        const double sq = dv * dv;
+        dev2 += sq;
+    }
+    out->sw2_squared = mean;
+    out->std_error = L > 1 ? std::sqrt(dev2 / (double)(L - 1)) / std::sqrt((double)L) : (double)NAN;
+    out->max_sliced = best; out->max_index = best_l;
+    out->n = n; out->m = m; out->projections = projections;
+    if (o.values) memcpy(o.values, W.data(), (size_t)L * sizeof(double));
+    if (o.sorted_x) memcpy(o.sorted_x, sx.data(), sx.size() * sizeof(float));
+    if (o.sorted_y) memcpy(o.sorted_y, sy.data(), sy.size() * sizeof(float));
+    if (o.index_x) memcpy(o.index_x, hx.data(), hx.size() * sizeof(int32_t));
+    if (o.index_y) memcpy(o.index_y, hy.data(), hy.size() * sizeof(int32_t));
+    if (sh) {                                                  // share = (the running sum over l) / L
+        for (int64_t i = 0; i < n; ++i) o.share_x[i] = acc[(size_t)i] / (double)L;
+        for (int64_t j = 0; j < m; ++j) o.share_y[j] = acc[(size_t)(n + j)] / (double)L;
     }
     return FAD_OK;
 }
@@ -4024,137 +4270,26 @@ int fad_sliced_wasserstein(const void* x, int64_t n, int64_t ldx, const void* y,
     sliced_plan_value() = SlicedPlan{0, 0, 0, 0};
     const char* who = "fad_sliced_wasserstein";
     if (!out) return set_error(FAD_ERR_INVALID, "%s: NULL output", who);
-    if (!x || !y) return set_error(FAD_ERR_INVALID, "%s: NULL rows", who);
-    if (!directions) return set_error(FAD_ERR_INVALID, "%s: NULL directions", who);
-    if (dtype == FAD_F64) return set_error(FAD_ERR_INVALID, "%s: float64 rows are not supported; cast to float32 (or float16 / bfloat16)", who);
-    if (dtype != FAD_F16 && dtype != FAD_BF16 && dtype != FAD_F32) return set_error(FAD_ERR_INVALID, "%s: unknown dtype %d", who, dtype);
-    if (d < 1 || d > 2048) return set_error(FAD_ERR_INVALID, "%s: D = %lld is outside 1 .. 2048", who, (long long)d);
-    if (ldx < d || ldy < d) return set_error(FAD_ERR_INVALID, "%s: row pitch %lld / %lld < D = %lld", who, (long long)ldx, (long long)ldy, (long long)d);
-    if (projections < 1 || projections > 65536) return set_error(FAD_ERR_INVALID, "%s: %d projections, outside 1 .. 65536", who, projections);
-    if (n < 1 || m < 1) return set_error(FAD_ERR_TOO_FEW_ROWS, "%s: needs at least 1 row per set, got %lld and %lld", who, (long long)n, (long long)m);
-    if (n > INT32_MAX - kTile || m > INT32_MAX - kTile)
-        return set_error(FAD_ERR_INVALID, "%s: %lld and %lld rows (at most %d per set)", who, (long long)n, (long long)m, INT32_MAX - kTile);
-    if (n > (((int64_t)1 << 53) - 1) / m)
-        return set_error(FAD_ERR_INVALID, "%s: n m = %lld x %lld is 2^53 or more: the integer weights would not be exact in float64", who,
-                         (long long)n, (long long)m);
-    const int64_t L = projections;
-    const size_t es = dtype_size(dtype);
-    const int64_t dp = depth_elems(d, dtype), tpitch = dp * (int64_t)es, l_img = (kad::blocks(L) + 1) * kTile;
+    SlicedOut o{};
+    if (detail) { o.values = detail->values; o.sorted_x = detail->sorted_x; o.sorted_y = detail->sorted_y; }
+    return sliced_sets(who, x, n, ldx, y, m, ldy, d, dtype, on_device, directions, projections, out, o, device, stream);
+}
 
-    // the directions rounded to the rows' dtype into their zero-padded image, and q_l from the rounded values, before any device call
-    std::vector<char> timg((size_t)(l_img * tpitch), 0);
-    std::vector<double> q((size_t)L);
-    for (int64_t l = 0; l < L; ++l) {
-        double ql = 0.0;
-        for (int64_t c = 0; c < d; ++c) {
-            const float f = directions[l * d + c];
-            if (!std::isfinite(f)) return set_error(FAD_ERR_INVALID, "%s: direction %lld has an entry that is not finite", who, (long long)l);
-            double v;
-            const uint32_t bits = round_direction(f, dtype, &v);
-            if (es == 2) {
-                const uint16_t h = (uint16_t)bits;
-                memcpy(&timg[(size_t)(l * tpitch + c * 2)], &h, 2);
-            } else {
-                memcpy(&timg[(size_t)(l * tpitch + c * 4)], &bits, 4);
-            }
-            const double sq = v * v;
-            ql += sq;
-        }
-        if (!(ql > 0) || !std::isfinite(ql))
-            return set_error(FAD_ERR_INVALID, "%s: direction %lld, rounded to the rows' dtype, has the squared length %g", who, (long long)l, ql);
-        q[(size_t)l] = ql;
-    }
-    const char* env = getenv("FAD_SLICED_WORKSPACE");
-    char* end = nullptr;
-    const long long env_v = env && *env ? strtoll(env, &end, 10) : 0;
-    const int64_t budget = end && *end == 0 && env_v > 0 ? (int64_t)env_v : kSlicedWorkspace;
-
-    Ctx cx;
-    FAD_TRY(cx.open(dtype, FAD_KAD_GAUSSIAN, device, stream));
-    KadWorkspace& ws = *cx.ws;
-    const hipStream_t st = cx.st;
-    Packed px, py;                                             // each set packed once, its norms checked finite
-    FAD_TRY(pack_set(cx, 0, x, n, ldx, d, on_device, &px));
-    FAD_TRY(pack_set(cx, 1, y, m, ldy, d, on_device, &py));
-    FAD_TRY(ws.sliced_theta.reserve(timg.size()));
-    FAD_HIP_TRY(hipMemcpyAsync(ws.sliced_theta.p, timg.data(), timg.size(), hipMemcpyHostToDevice, st));
-
-    // the chunk: lc directions' projections of both sets, the sort's second buffer, its counts, the match's slots
-    const bool x_larger = n >= m;
-    const int64_t n_pad = kad::blocks(n) * kTile, m_pad = kad::blocks(m) * kTile, t_pad = std::max(n_pad, m_pad);
-    const int64_t na = x_larger ? n : m, nb = x_larger ? m : n, nblk = cdiv(na, kMatchBlock);
-    const int64_t count_words = std::max(ssort::counts_elems(n, 1), ssort::counts_elems(m, 1));
-    const int64_t per_dir = 4 * (n_pad + m_pad + t_pad) + 4 * (count_words + ssort::kRadix) + 8 * nblk;
-    const int64_t lc = std::max<int64_t>(1, std::min<int64_t>(L, budget / per_dir));
-    const int64_t chunks = cdiv(L, lc);
-    Carve cv;
-    const auto px_r = cv.add<float>(lc * n_pad), py_r = cv.add<float>(lc * m_pad), tmp_r = cv.add<float>(lc * t_pad);
-    const auto counts_r = cv.add<uint32_t>(lc * count_words), bases_r = cv.add<uint32_t>(lc * ssort::kRadix);
-    const auto slots_r = cv.add<double>(lc * nblk), s_r = cv.add<double>(L);
-    const auto zeros_r = cv.add<float>(std::max(t_pad, l_img));
-    const auto flag_r = cv.add<unsigned int>(64);
-    FAD_TRY(cv.reserve(ws.sliced));
-    FAD_HIP_TRY(hipMemsetAsync(cv.ptr(zeros_r), 0, (size_t)std::max(t_pad, l_img) * sizeof(float), st));
-    FAD_HIP_TRY(hipMemsetAsync(cv.ptr(flag_r), 0, 64 * sizeof(unsigned int), st));
-    const ssort::Plan sp = ssort::plan(n, lc);
-    sliced_plan_value() = SlicedPlan{chunks, lc, ssort::kPasses, sp.G > 1 ? -sp.G : sp.W};
-
-    // the sorted arrays are staged on the host: a refusal after the first chunk must leave the caller's arrays as they were
-    std::vector<float> sx, sy;
-    if (detail && detail->sorted_x) sx.resize((size_t)(L * n));
-    if (detail && detail->sorted_y) sy.resize((size_t)(L * m));
-    const char* theta = static_cast<const char*>(ws.sliced_theta.p);
-    float* Px = cv.ptr(px_r);
-    float* Py = cv.ptr(py_r);
-    for (int64_t l0 = 0; l0 < L; l0 += lc) {
-        const int64_t cur = std::min(lc, L - l0);
-        FAD_TRY(sliced_project_sort(cx, px, theta, cv.ptr(zeros_r), l0, cur, Px, n_pad, cv.ptr(tmp_r), cv.ptr(counts_r), cv.ptr(bases_r), cv.ptr(flag_r)));
-        FAD_TRY(sliced_project_sort(cx, py, theta, cv.ptr(zeros_r), l0, cur, Py, m_pad, cv.ptr(tmp_r), cv.ptr(counts_r), cv.ptr(bases_r), cv.ptr(flag_r)));
-        sliced_match_kernel<<<(unsigned int)(cur * nblk), kMatchBlock, 0, st>>>(x_larger ? Px : Py, x_larger ? n_pad : m_pad, na, x_larger ? Py : Px,
-                                                                                x_larger ? m_pad : n_pad, nb, nblk, cv.ptr(slots_r));
-        FAD_HIP_TRY(hipGetLastError());
-        sliced_finish_kernel<<<(unsigned int)cdiv(cur, 256), 256, 0, st>>>(cv.ptr(slots_r), nblk, cur, cv.ptr(s_r) + l0);
-        FAD_HIP_TRY(hipGetLastError());
-        if (!sx.empty())
-            FAD_HIP_TRY(hipMemcpy2DAsync(sx.data() + l0 * n, (size_t)n * 4, Px, (size_t)n_pad * 4, (size_t)n * 4, (size_t)cur, hipMemcpyDeviceToHost, st));
-        if (!sy.empty())
-            FAD_HIP_TRY(hipMemcpy2DAsync(sy.data() + l0 * m, (size_t)m * 4, Py, (size_t)m_pad * 4, (size_t)m * 4, (size_t)cur, hipMemcpyDeviceToHost, st));
-    }
-    std::vector<double> S((size_t)L);
-    unsigned int flag = 0;
-    FAD_HIP_TRY(hipMemcpyAsync(S.data(), cv.ptr(s_r), (size_t)L * sizeof(double), hipMemcpyDeviceToHost, st));
-    FAD_HIP_TRY(hipMemcpyAsync(&flag, cv.ptr(flag_r), sizeof(flag), hipMemcpyDeviceToHost, st));
-    FAD_HIP_TRY(hipStreamSynchronize(st));
-    if (flag) return set_error(FAD_ERR_NOT_FINITE, "%s: a projection is not finite in float32", who);
-
-    // W_l = S_l / (n m q_l), one division; mean, spread and maximum over l in index order
-    const double nm = (double)(n * m);
-    std::vector<double> W((size_t)L);
-    double sum = 0.0, best = -INFINITY;
-    int64_t best_l = 0;
-    for (int64_t l = 0; l < L; ++l) {
-        const double w = S[(size_t)l] / (nm * q[(size_t)l]);
-        W[(size_t)l] = w;
-        sum += w;
-        if (w > best) { best = w; best_l = l; }
-    }
-    const double mean = sum / (double)L;
-    double dev2 = 0.0;
-    for (int64_t l = 0; l < L; ++l) {
-        const double dv = W[(size_t)l] - mean;
-        const double sq = dv * dv;
-        dev2 += sq;
-    }
-    out->sw2_squared = mean;
-    out->std_error = L > 1 ? std::sqrt(dev2 / (double)(L - 1)) / std::sqrt((double)L) : (double)NAN;
-    out->max_sliced = best; out->max_index = best_l;
-    out->n = n; out->m = m; out->projections = projections;
+int fad_sliced_shares(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype, int on_device,
+                      const float* directions, int projections, fad_sliced_result_t* out, double* share_x, double* share_y,
+                      fad_sliced_shares_detail_t* detail, int device, void* stream) {
+    using namespace fad;
+    begin_entry();
+    sliced_plan_value() = SlicedPlan{0, 0, 0, 0};
+    const char* who = "fad_sliced_shares";
+    if (!out || !share_x || !share_y) return set_error(FAD_ERR_INVALID, "%s: NULL output", who);
+    SlicedOut o{};
+    o.shares = true; o.share_x = share_x; o.share_y = share_y;
     if (detail) {
-        if (detail->values) memcpy(detail->values, W.data(), (size_t)L * sizeof(double));
-        if (detail->sorted_x) memcpy(detail->sorted_x, sx.data(), sx.size() * sizeof(float));
-        if (detail->sorted_y) memcpy(detail->sorted_y, sy.data(), sy.size() * sizeof(float));
+        o.values = detail->values; o.sorted_x = detail->sorted_x; o.sorted_y = detail->sorted_y;
+        o.index_x = detail->index_x; o.index_y = detail->index_y;
     }
-    return FAD_OK;
+    return sliced_sets(who, x, n, ldx, y, m, ldy, d, dtype, on_device, directions, projections, out, o, device, stream);
 }
 
 int fad_sliced_last_plan(int64_t out[4]) {
@@ -4268,7 +4403,8 @@ int fad_sliced_individual(const void* x, int64_t n, int64_t ldx, const void* row
     unsigned int* flags = cv.ptr(flag_r);
     for (int64_t l0 = 0; l0 < L; l0 += lc) {
         const int64_t cur = std::min(lc, L - l0);
-        FAD_TRY(sliced_project_sort(cx, px, theta, cv.ptr(zeros_r), l0, cur, Px, n_pad, cv.ptr(tmp_r), cv.ptr(counts_r), cv.ptr(bases_r), flags));
+        FAD_TRY(sliced_project_sort(cx, px, theta, cv.ptr(zeros_r), l0, cur, Px, n_pad, cv.ptr(tmp_r), nullptr, nullptr, cv.ptr(counts_r),
+                                    cv.ptr(bases_r), flags));
         if (n_rows > 0) {
             ProjArgs p{};
             p.th = theta + l0 * pr.pitch; p.rows = pr.img; p.zeros = cv.ptr(zeros_r); p.pitch = pr.pitch; p.nchunks = pr.nchunks;

@@ -1274,8 +1274,43 @@ def sliced_wasserstein(x, y, directions, device: int = 0, values: bool = False, 
     return out
 
 
+def sliced_shares(x, y, directions, device: int = 0, values: bool = False, sorted_projections: bool = False, indices: bool = False) -> dict:
+    """``fad_sliced_shares``: ``sliced_wasserstein`` (the same result fields, bit for bit) plus every row's share of ``sw2_squared`` ->
+    that dict with the float64 arrays ``share_x`` [n] and ``share_y`` [m], each summing to ``sw2_squared`` up to rounding.  ``values``
+    and ``sorted_projections`` as there; ``indices=True`` adds the int32 arrays ``index_x`` [L x n] and ``index_y`` [L x m]: the row at
+    every rank of every direction (equal projections in ascending row order)."""
+    lib = K.load_library()
+    (px, n, d, ldx, cx, dev_x, kx), (py, m, dy, ldy, cy, dev_y, ky) = _kad_pair(x, y, "y", device)
+    if d != dy:
+        raise ValueError(f"sliced Wasserstein: x has D = {d}, y has D = {dy}")
+    if cx != cy:
+        raise ValueError("sliced Wasserstein: x and y must have the same dtype")
+    t = sliced_directions_array(directions, d)
+    L = t.shape[0]
+    res = K.FadSlicedResult()
+    share_x, share_y = np.zeros(max(n, 0)), np.zeros(max(m, 0))
+    arrays = {}
+    if values:
+        arrays["values"] = np.zeros(L)
+    if sorted_projections:
+        arrays["sorted_x"] = np.zeros((L, n), dtype=np.float32)
+        arrays["sorted_y"] = np.zeros((L, m), dtype=np.float32)
+    if indices:
+        arrays["index_x"] = np.zeros((L, n), dtype=np.int32)
+        arrays["index_y"] = np.zeros((L, m), dtype=np.int32)
+    det = K.FadSlicedSharesDetail(*(arrays[k].ctypes.data if k in arrays else None
+                                    for k in ("values", "sorted_x", "sorted_y", "index_x", "index_y"))) if arrays else None
+    K.check(lib.fad_sliced_shares(px, n, ldx, py, m, ldy, d, cx, dev_x, t.ctypes.data, L, C.byref(res), share_x.ctypes.data,
+                                  share_y.ctypes.data, C.byref(det) if det is not None else None, int(device),
+                                  K.current_stream_ptr(device)),
+            "fad_sliced_shares")
+    out = res.as_dict()
+    out.update(arrays, share_x=share_x, share_y=share_y)
+    return out
+
+
 def sliced_last_plan() -> dict:
-    """``fad_sliced_last_plan``: how this thread's last fad_sliced_wasserstein call was laid out -> dict of ``chunks``,
+    """``fad_sliced_last_plan``: how this thread's last fad_sliced_wasserstein or fad_sliced_shares call was laid out -> dict of ``chunks``,
     ``directions_per_chunk``, ``sort_passes`` and ``share`` (W >= 1: workgroups per segment of x's sort; -G: one workgroup owns G
     segments)."""
     out = (C.c_int64 * 4)()

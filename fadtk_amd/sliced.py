@@ -5,7 +5,7 @@ no blur, no iterations and no convergence question, on all rows, in O((n + m) lo
 directions has an honest estimate (``std_error``).  Everything runs in one GPU call (``fad_sliced_wasserstein``, include/fad_hip.h;
 DESIGN.md 4.17): projections on the matrix cores, a segmented radix sort, the match in float64.
 
-    python -m fadtk_amd.sliced <model> <baseline_dir> <eval_dir> [csv] [--projections 512] [--seed 0] [-w N] [--indiv]
+    python -m fadtk_amd.sliced <model> <baseline_dir> <eval_dir> [csv] [--projections 512] [--seed 0] [-w N] [--indiv | --shares]
 
 The directions are ``sliced_directions(D, projections, seed)``: standard normal, NOT normalised (the library divides each direction's
 value by its squared length).  ``fad_scale`` = D x ``sw2_squared`` reads beside FAD's mean term: a pure translation delta gives
@@ -15,6 +15,14 @@ Per song (``--indiv``): every file of the evaluation directory alone against the
 (``fad_sliced_individual``), each with the bits ``calc_sliced_wasserstein(x, song)`` gives: the parameter-free per-song
 ranking beside FAD's and KAD's.  The CSV (default ``sliced-individual-results.csv``) gets one row per file under INDIV_CSV_HEADER,
 sorted by ``sw2_squared`` descending.
+
+Per-row shares (``--shares``): where the set-level number comes from, on BOTH sides -- every row's share of ``sw2_squared``
+(``fad_sliced_shares``, DESIGN.md 4.19: the sort carries the row index, the match keeps every element's cost), summed per file.  The CSV
+(default ``sliced-shares.csv``) gets one row per file of both directories under SHARES_CSV_HEADER: ``share`` (the sum of the file's
+rows' shares), ``fraction`` (of ``sw2_squared``) and ``lift`` (fraction / the file's fraction of its set's rows: 1 for a file that
+carries the distance in proportion to its length); the baseline's files first, each side sorted by ``share`` descending.  A baseline
+file with a high lift holds rows the evaluation set does not cover (mode dropping); an evaluation file with one holds rows far from
+the baseline.
 """
 from __future__ import annotations
 
@@ -32,6 +40,8 @@ log = logging.getLogger("fadtk_amd")
 CSV_HEADER = "model,baseline,eval,n,m,sw2_squared,sliced_w2,std_error,max_sliced,max_index,fad_scale,projections,seed\n"
 INDIV_CSV_HEADER = "file,rows,sw2_squared,sliced_w2,std_error,fad_scale\n"
 INDIV_CSV_NAME = "sliced-individual-results.csv"
+SHARES_CSV_HEADER = "side,file,rows,share,fraction,lift\n"
+SHARES_CSV_NAME = "sliced-shares.csv"
 INDIV_BYTES = 4 << 30          # song rows per fad_sliced_individual call at most (a larger set is split: the same bits either way)
 MAX_PROJECTIONS = 65536
 
@@ -183,6 +193,63 @@ def calc_sliced_wasserstein_individual(x, songs, projections: int = 512, seed: i
     return out
 
 
+def _check_offsets(offsets, rows: int, name: str) -> np.ndarray:
+    """-> ``offsets`` as int64 [F + 1], or a ValueError: not 1-D, fewer than 2 entries, not starting at 0, decreasing, or not ending at
+    ``rows``"""
+    off = np.asarray(offsets)
+    if off.ndim != 1 or off.shape[0] < 2 or not np.issubdtype(off.dtype, np.integer):
+        raise ValueError(f"sliced Wasserstein shares: {name} must be a 1-D sequence of F + 1 integer row indices, F >= 1")
+    off = off.astype(np.int64)
+    if off[0] != 0 or off[-1] != rows or np.any(np.diff(off) < 0):
+        raise ValueError(f"sliced Wasserstein shares: {name} must start at 0, never decrease and end at the {rows} rows of its set")
+    return off
+
+
+def file_sums(share: np.ndarray, offsets: np.ndarray) -> np.ndarray:
+    """-> float64 [F]: the sum of ``share[offsets[f]:offsets[f + 1]]`` per file (0 for a file without rows)"""
+    return np.array([float(np.sum(share[offsets[f]:offsets[f + 1]])) for f in range(len(offsets) - 1)], dtype=np.float64)
+
+
+def file_lift(file_share: np.ndarray, offsets: np.ndarray, sw2_squared: float) -> np.ndarray:
+    """-> float64 [F]: (file share / sw2_squared) / (file rows / set rows); NaN for a file without rows or at sw2_squared == 0"""
+    rows = np.diff(offsets).astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return (file_share / sw2_squared) / (rows / float(offsets[-1]))
+
+
+def calc_sliced_wasserstein_shares(x, y, projections: int = 512, seed: int = 0, directions=None, x_offsets=None, y_offsets=None,
+                                   device: int = 0) -> dict:
+    """``calc_sliced_wasserstein`` of y against the baseline x (the same dict, the same bits) plus every row's share of ``sw2_squared``
+    on both sides (``fad_sliced_shares``): the float64 arrays ``share_x`` [n] and ``share_y`` [m].  Each sums to ``sw2_squared`` up to
+    rounding; n x ``share_x[i]`` is row i's mean squared one-dimensional displacement under the optimal one-dimensional matchings.
+    Rows with equal projections are ranked by row index: shares are discontinuous at such ties.  Inputs, dtypes and ValueErrors as
+    ``calc_sliced_wasserstein``.  With ``x_offsets`` [F + 1] (row f0 of file f is ``x_offsets[f]``; starts at 0, ends at n) the dict also
+    has ``file_share_x`` [F] (the sum of the file's rows' shares) and ``file_lift_x`` = (file share / sw2_squared) / (file rows / n);
+    ``y_offsets`` likewise gives ``file_share_y`` and ``file_lift_y``."""
+    n, m, d = _check(x, y)
+    if x_offsets is not None:
+        x_offsets = _check_offsets(x_offsets, n, "x_offsets")
+    if y_offsets is not None:
+        y_offsets = _check_offsets(y_offsets, m, "y_offsets")
+    if directions is None:
+        directions = sliced_directions(d, projections, seed)
+    else:
+        from .hip import sliced_directions_array
+        directions = sliced_directions_array(directions, d)
+        seed = None
+    from . import hip
+    x, y = _one_dtype(x, y)
+    res = hip.sliced_shares(x, y, directions, device=device)
+    out = {"sw2_squared": res["sw2_squared"], "sliced_w2": math.sqrt(max(res["sw2_squared"], 0.0)), "std_error": res["std_error"],
+           "max_sliced": res["max_sliced"], "max_index": res["max_index"], "fad_scale": d * res["sw2_squared"], "n": res["n"],
+           "m": res["m"], "projections": res["projections"], "seed": seed, "share_x": res["share_x"], "share_y": res["share_y"]}
+    for side, off in (("x", x_offsets), ("y", y_offsets)):
+        if off is not None:
+            out[f"file_share_{side}"] = file_sums(out[f"share_{side}"], off)
+            out[f"file_lift_{side}"] = file_lift(out[f"file_share_{side}"], off, out["sw2_squared"])
+    return out
+
+
 def check_csv(target: PathLike, header: str = CSV_HEADER) -> None:
     """Refuse (ValueError) an existing CSV whose first line is not ``header`` (CSV_HEADER; INDIV_CSV_HEADER for the per-song file)."""
     if Path(target).is_file():
@@ -210,6 +277,26 @@ def write_indiv_csv(target: PathLike, files, res: dict) -> int:
     target.parent.mkdir(parents=True, exist_ok=True)
     target.write_text(INDIV_CSV_HEADER + "".join(indiv_csv_row(files[s], res, s) + "\n" for s in keep))
     return len(keep)
+
+
+def write_shares_csv(target: PathLike, x_files, y_files, res: dict, x_offsets, y_offsets) -> int:
+    """The per-file CSV of a calc_sliced_wasserstein_shares result with offsets: SHARES_CSV_HEADER, then one row per file -- the
+    baseline's (``side`` = baseline) before the evaluation set's (eval), each side sorted by ``share`` descending (ties in the order of
+    the files).  ``fraction`` = share / sw2_squared, ``lift`` as ``file_lift``.  A file with another header is refused, untouched; one
+    with this header is replaced.  -> the rows written."""
+    check_csv(target, SHARES_CSV_HEADER)
+    lines = []
+    for side, files, off, k in (("baseline", x_files, x_offsets, "x"), ("eval", y_files, y_offsets, "y")):
+        share, lift = res[f"file_share_{k}"], res[f"file_lift_{k}"]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            fraction = share / res["sw2_squared"]
+        for f in sorted(range(len(files)), key=lambda f: -share[f]):
+            lines.append(f"{side},{str(files[f]).replace(',', '_')},{int(off[f + 1] - off[f])},{float(share[f])!r},{float(fraction[f])!r},"
+                         f"{float(lift[f])!r}\n")
+    target = Path(target)
+    target.parent.mkdir(parents=True, exist_ok=True)
+    target.write_text(SHARES_CSV_HEADER + "".join(lines))
+    return len(lines)
 
 
 def append_csv(target: PathLike, row: str) -> None:
@@ -287,6 +374,50 @@ class SlicedWasserstein:
         return csv
 
 
+    def _embedding_files(self, directory: PathLike, d: Optional[int]) -> list:
+        """-> [(file, embedding)] of ``directory`` in sorted order; a file whose embedding is missing, unreadable, not [* x d] (d None:
+        the D of the first readable one) or empty is logged and dropped"""
+        keep = []
+        for f in sorted(Path(directory).glob("*.*")):
+            try:
+                e = self.kad.fad.read_embedding_file(f)
+            except Exception as err:      # noqa: BLE001
+                log.error(f"An error occurred calculating the sliced Wasserstein shares using model {self.ml.name} on file {f}")
+                log.error(err)
+                continue
+            if e.ndim != 2 or (d is not None and e.shape[1] != d):
+                log.error(f"Embedding of {f} has shape {e.shape}; expected [*, {'D' if d is None else d}]")
+            elif e.shape[0] < 1:
+                log.error(f"Sliced Wasserstein shares of {f} dropped: no frames")
+            else:
+                d = e.shape[1]
+                keep.append((f, e))
+        return keep
+
+    def score_shares(self, baseline: PathLike, eval_dir: PathLike, csv: PathLike = SHARES_CSV_NAME) -> dict:
+        """calc_sliced_wasserstein_shares of all rows of ``eval_dir`` against all rows of ``baseline`` with one offset per file, written
+        to ``csv`` under SHARES_CSV_HEADER (write_shares_csv) -> the result, with ``x_files`` and ``y_files``.  Files are dropped and
+        logged as score_individual drops them; a file with non-finite rows refuses the call, as it does ``score``.  A CSV with another
+        header is refused before any work."""
+        check_csv(csv, SHARES_CSV_HEADER)
+        xs = self._embedding_files(baseline, None)
+        if not xs:
+            raise ValueError(f"sliced Wasserstein shares: no embedding rows under {baseline}")
+        ys = self._embedding_files(eval_dir, xs[0][1].shape[1])
+        if not ys:
+            raise ValueError(f"sliced Wasserstein shares: no embedding rows under {eval_dir}")
+        dts = {e.dtype for _, e in xs + ys}
+        cast = (lambda e: e.astype(np.float32)) if len(dts) > 1 or np.float64 in dts else (lambda e: e)
+        x, y = np.concatenate([cast(e) for _, e in xs]), np.concatenate([cast(e) for _, e in ys])
+        xo = np.concatenate([[0], np.cumsum([len(e) for _, e in xs], dtype=np.int64)])
+        yo = np.concatenate([[0], np.cumsum([len(e) for _, e in ys], dtype=np.int64)])
+        res = calc_sliced_wasserstein_shares(x, y, projections=self.projections, seed=self.seed, x_offsets=xo, y_offsets=yo,
+                                             device=self.device_index)
+        res["x_files"], res["y_files"] = [f for f, _ in xs], [f for f, _ in ys]
+        write_shares_csv(csv, res["x_files"], res["y_files"], res, xo, yo)
+        return res
+
+
 def main(argv=None):
     from .cli import _registry, _setup_logging
     _setup_logging()
@@ -296,22 +427,25 @@ def main(argv=None):
     p.add_argument("model", type=str, choices=list(models), help="embedding model")
     p.add_argument("baseline", type=str, help="baseline dataset directory")
     p.add_argument("eval", type=str, help="directory to evaluate")
-    p.add_argument("csv", type=str, nargs="?", help=f"append the result to this CSV; with --indiv: where the per-song rows go "
-                   f"(default {INDIV_CSV_NAME})")
+    p.add_argument("csv", type=str, nargs="?", help=f"append the result to this CSV; with --indiv or --shares: where the per-file rows go "
+                   f"(default {INDIV_CSV_NAME} / {SHARES_CSV_NAME})")
     p.add_argument("--projections", type=int, default=512, help="random directions (default 512)")
     p.add_argument("--seed", type=int, default=0, help="seed of the directions (default 0)")
     p.add_argument("-w", "--workers", type=int, default=8, help="number of workers")
-    p.add_argument("--indiv", action="store_true", help="one row per file of the eval directory")
+    mode = p.add_mutually_exclusive_group()
+    mode.add_argument("--indiv", action="store_true", help="one row per file of the eval directory")
+    mode.add_argument("--shares", action="store_true", help=f"every file's share of the distance, both directories (default CSV "
+                      f"{SHARES_CSV_NAME})")
     a = p.parse_args(argv)
     try:
         check_params(a.projections, a.seed)
     except ValueError as e:
         p.error(str(e))
     model = models[a.model]
-    if a.indiv:
-        a.csv = a.csv or INDIV_CSV_NAME
-    if a.csv:
-        check_csv(a.csv, INDIV_CSV_HEADER if a.indiv else CSV_HEADER)   # before any work: a CSV with another header is refused
+    if a.indiv or a.shares:
+        a.csv = a.csv or (INDIV_CSV_NAME if a.indiv else SHARES_CSV_NAME)
+    if a.csv:                                                           # before any work: a CSV with another header is refused
+        check_csv(a.csv, INDIV_CSV_HEADER if a.indiv else SHARES_CSV_HEADER if a.shares else CSV_HEADER)
 
     from .fad_batch import cache_embedding_files
     for dataset in (a.baseline, a.eval):
@@ -321,6 +455,10 @@ def main(argv=None):
     if a.indiv:
         csv = sw.score_individual(a.baseline, a.eval, a.csv)
         log.info(f"Individual sliced Wasserstein distances {model.name} of {a.eval} against {a.baseline} saved to {csv}")
+        return
+    if a.shares:
+        res = sw.score_shares(a.baseline, a.eval, a.csv)
+        log.info(f"Sliced Wasserstein shares {model.name} of {a.eval} against {a.baseline} (SW2^2 = {res['sw2_squared']}) saved to {a.csv}")
         return
     res = sw.score(a.baseline, a.eval)
     log.info(f"The sliced Wasserstein distance {model.name} between {a.baseline} and {a.eval} is: SW2^2 = {res['sw2_squared']} "

@@ -723,6 +723,44 @@ int fad_sliced_individual(const void* x, int64_t n, int64_t ldx, const void* row
                           int32_t* out_status /* each [n_songs], host */,
                           fad_sliced_individual_detail_t* detail /* may be NULL */, int device, void* stream);
 
+/* ------------------------------------------------------------------ sliced 2-Wasserstein distance: every row's share
+ * Not in the reference.  fad_sliced_wasserstein on the same arguments -- the same rounding of the directions, q_l, float32 projections,
+ * stable ascending sort (-0 before +0), weights, order of every sum; `out` and detail->values, sorted_x, sorted_y get the bits of that
+ * call -- and, for every row of x and of y, its share of sw2_squared: where the distance comes from, on both sides.
+ * Per direction l, a = sorted x theta_l, b = sorted y theta_l, rx_l[r] / ry_l[r] = the row of x / y at rank r; equal keys (equal float32
+ * bits) stand in ascending row order: the sort is stable, and the tie rule is part of the definition (two rows with equal projections
+ * swap partners, so shares are discontinuous at ties).  "Lead" is the larger set (x at n == m), A [na]; the other is B [nb].
+ *   lead element at rank i:   c(i) = sum_{j = j0 .. j1} w_ij (A_i - B_j)^2,  j0 = floor(i nb / na), j1 = floor(((i + 1) nb - 1) / na), j ascending
+ *                             (the per-element sum of fad_sliced_wasserstein, before its tree)
+ *   other element at rank j:  c(j) = sum_{i = i0 .. i1} w_ij (A_i - B_j)^2,  i0 = floor(j na / nb), i1 = floor(((j + 1) na - 1) / nb), i ascending
+ *   w_ij = min((i + 1) nb, (j + 1) na) - max(i nb, j na); difference, square, product with the weight and sums in float64, each rounded
+ *   once (no fused multiply-add).
+ *   t_l(row) = c / ((double)(n m) q_l): one division, by the denominator of W_l.
+ *   share[row] = (sum_l t_l(row), l ascending, one running float64 sum carried across the chunks of directions) / L.
+ * So sum_rows share_x = sum_rows share_y = sw2_squared up to summation rounding, and n share_x[row] is the row's mean squared
+ * one-dimensional displacement.  The same bits on every run and for any chunking; swapped arguments swap the shares; sets of identical
+ * bits give shares of exactly 0.  No floating-point atomics: every (direction, row) cost is stored once, and a row's sum has one owner.
+ *   share_x [n], share_y [m]: host, required.
+ *   detail (may be NULL; each array NULL or host): values, sorted_x, sorted_y as fad_sliced_detail; index_x [L x n], index_y [L x m]:
+ *   rx_l and ry_l, so that sorted_x[l][r] is the projection of row index_x[l][r] of x.
+ * Refusals: as fad_sliced_wasserstein, and a NULL share_x or share_y -> FAD_ERR_INVALID; any refusal leaves every output untouched
+ * (everything is staged in host memory until the call succeeds).
+ * Workspace: fad_sliced_wasserstein's and, per direction of a chunk, 4 more bytes per padded row of x, of y and of the larger of the
+ * two (the rows at every rank, and the index sort's second buffer: csrc/sliced_sort_pairs.h) and 8 per padded row of x and of y (the
+ * costs); chunked under the same 1 GiB or FAD_SLICED_WORKSPACE.  Beside the chunks: 8 bytes per row and per direction.
+ * fad_sliced_last_plan reports this call's plan too.  Synchronises `stream`. */
+typedef struct fad_sliced_shares_detail {
+    double* values;      /* [L]      W_l, may be NULL */
+    float* sorted_x;     /* [L x n]  may be NULL */
+    float* sorted_y;     /* [L x m]  may be NULL */
+    int32_t* index_x;    /* [L x n]  may be NULL */
+    int32_t* index_y;    /* [L x m]  may be NULL */
+} fad_sliced_shares_detail_t;
+int fad_sliced_shares(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype, int on_device,
+                      const float* directions /* host, [L x d] */, int projections, fad_sliced_result_t* out,
+                      double* share_x /* host, [n] */, double* share_y /* host, [m] */,
+                      fad_sliced_shares_detail_t* detail /* may be NULL */, int device, void* stream);
+
 /* ------------------------------------------------------------------ diagnostics (NOT part of the drop-in surface)
  * Nothing in fadtk corresponds to these two calls and no binding of the reference needs them: they exist for bench.py's
  * roofline object (HIP events around the tile kernel on the stream it is launched on) and for the GPU tests that check
@@ -752,7 +790,7 @@ int fad_moments_last_timing(fad_moments_t* h, float* ms_main_kernel, float* ms_r
  * fewer than 64 tiles) exists for tests, which cut small passes into several launches with it. */
 int fad_kad_last_plan(int64_t out[5]);
 
-/* Diagnostic: how the last fad_sliced_wasserstein call of this thread was laid out.  out = { chunks, directions per chunk, sort passes,
+/* Diagnostic: how the last fad_sliced_wasserstein or fad_sliced_shares call of this thread was laid out.  out = { chunks, directions per chunk, sort passes,
  * share }; all 0 when the call was refused before it planned.  share describes the sort of x's segments in a full chunk: W >= 1 when a
  * segment of n keys takes W workgroups (2048 keys each), -G when n <= 256 and one workgroup owns G > 1 segments.  The chunking follows
  * FAD_SLICED_WORKSPACE (above), as fad_kad_last_plan's launch cut follows FAD_KAD_LAUNCH_BUDGET. */
