@@ -102,9 +102,10 @@ def build_native_tests(force: bool = False, verbose: bool = True) -> list:
     """tests/native/*.hip -> tests/native/<name> (gfx950 executables that check single kernels of csrc/ against host
     arithmetic; run by `pytest -m gpu`).  Test infrastructure, not part of the library."""
     out = []
+    headers = [*HEADERS, *sorted(NATIVE_TESTS.glob("*.h"))]
     for src in sorted(NATIVE_TESTS.glob("*.hip")):
         exe = src.with_suffix("")
-        if force or _stale(exe, [src, *HEADERS]):
+        if force or _stale(exe, [src, *headers]):
             cmd = [_hipcc(), f"--offload-arch={ARCH}", "-O2", "-std=c++17", "-o", str(exe), str(src)]
             if verbose:
                 print("[fadtk_amd.build]", " ".join(cmd), flush=True)

@@ -775,29 +775,31 @@ __global__ void __launch_bounds__(kThreads, 2) sliced_project_kernel(ProjArgs p)
 constexpr size_t kLdsProject = 2 * kOpBytes + 2 * kTile * 4;
 constexpr int kMatchBlock = 256;
 
-// The quantile match of one chunk: workgroup (direction l, block k) takes the elements i in [256 k, 256 k + 256) of the sorted larger
-// set a [na] and, for each, the elements j0 .. j1 of the sorted smaller set b [nb] whose quantile interval [j nb', (j + 1) nb') meets
-// [i, i + 1) na' (in units of 1 / (na nb)): the overlap w is an exact integer, the term w * (a_i - b_j)^2 is float64 (difference, square
-// and product each rounded once: contraction into a fused multiply-add is switched off), summed over j ascending per element, then by the workgroup's halving tree, one
-// slot per workgroup.
-__global__ void __launch_bounds__(kMatchBlock) sliced_match_kernel(const float* __restrict__ a, int64_t pa, int64_t na,
-                                                                   const float* __restrict__ b, int64_t pb, int64_t nb, int64_t nblk,
-                                                                   double* __restrict__ slots) {
+// One term of the quantile match: w (a - b)^2 in float64, w an exact integer; the difference, the square and the product are each
+// rounded once (contraction into a fused multiply-add is switched off, here and where the terms are added).  (a - b)^2 has the bits
+// of (b - a)^2.
+__device__ __forceinline__ double sliced_term(int64_t w, double a, double b) {
 #pragma clang fp contract(off)
-    __shared__ double red[kMatchBlock];
-    const int64_t l = blockIdx.x / nblk, k = blockIdx.x % nblk, i = k * kMatchBlock + threadIdx.x;
+    const double diff = a - b;
+    const double sq = diff * diff;
+    return (double)w * sq;
+}
+
+// One element's side of the match: element e of a sorted set of ne elements, value v, against the sorted other set o [no].  It meets
+// the elements j0 .. j1 of o whose quantile interval [j ne, (j + 1) ne) meets [e, e + 1) no (in units of 1 / (ne no)), each with the
+// overlap as its weight; the terms are summed over j ascending.  Either set may be the element's.
+__device__ __forceinline__ double sliced_overlap_sum(double v, int64_t e, int64_t ne, const float* __restrict__ o, int64_t no) {
+#pragma clang fp contract(off)
+    const int64_t lo = e * no, hi = lo + no, j0 = lo / ne, j1 = (hi - 1) / ne;
     double s = 0.0;
-    if (i < na) {
-        const double ai = (double)a[l * pa + i];
-        const int64_t lo = i * nb, hi = lo + nb, j0 = lo / na, j1 = (hi - 1) / na;
-        for (int64_t j = j0; j <= j1 && j < nb; ++j) {
-            const int64_t w = (hi < (j + 1) * na ? hi : (j + 1) * na) - (lo > j * na ? lo : j * na);
-            const double diff = ai - (double)b[l * pb + j];
-            const double sq = diff * diff;
-            const double term = (double)w * sq;
-            s += term;
-        }
-    }
+    for (int64_t j = j0; j <= j1 && j < no; ++j)
+        s += sliced_term((hi < (j + 1) * ne ? hi : (j + 1) * ne) - (lo > j * ne ? lo : j * ne), v, (double)o[j]);
+    return s;
+}
+
+// the workgroup's halving tree over every thread's s, stored in the workgroup's slot
+__device__ __forceinline__ void sliced_tree_store(double s, double* __restrict__ slots) {
+    __shared__ double red[kMatchBlock];
     red[threadIdx.x] = s;
     __syncthreads();
     for (int w = kMatchBlock / 2; w > 0; w >>= 1) {
@@ -805,6 +807,28 @@ __global__ void __launch_bounds__(kMatchBlock) sliced_match_kernel(const float* 
         __syncthreads();
     }
     if (threadIdx.x == 0) slots[blockIdx.x] = red[0];
+}
+
+// The quantile match of one chunk: workgroup (direction l, block k) takes the elements i in [256 k, 256 k + 256) of the sorted larger
+// set a [na], each its sliced_overlap_sum against the sorted smaller set b [nb], then the tree, one slot per workgroup.  With COST
+// (fad_sliced_shares) every element's sum is kept as well: divided once by den[l] = (double)(n m) q_l it goes to
+// cost[l][ra[l][i]], ra the row at rank i (ssort::sort_segment_pairs).  ra is a permutation of 0 .. na - 1, so every row of a direction
+// is written exactly once: plain 8-byte stores.  Without COST ra, den and cost are never touched; the slots are the same either way.
+template <bool COST>
+__global__ void __launch_bounds__(kMatchBlock) sliced_match_kernel(const float* __restrict__ a, const uint32_t* __restrict__ ra, int64_t pa,
+                                                                   int64_t na, const float* __restrict__ b, int64_t pb, int64_t nb,
+                                                                   int64_t nblk, const double* __restrict__ den,
+                                                                   double* __restrict__ slots, double* __restrict__ cost) {
+    const int64_t l = blockIdx.x / nblk, k = blockIdx.x % nblk, i = k * kMatchBlock + threadIdx.x;
+    double s = 0.0;
+    if (i < na) {
+        s = sliced_overlap_sum((double)a[l * pa + i], i, na, b + l * pb, nb);
+        if (COST) {
+            const int64_t row = ra[l * pa + i];
+            if (row < na) cost[l * pa + row] = s / den[l];                             // always true; keeps a wrong index inside the row
+        }
+    }
+    sliced_tree_store(s, slots);
 }
 
 // S[l] = the nblk slots of direction l summed in index order, one thread per direction of the chunk
@@ -817,59 +841,16 @@ __global__ void __launch_bounds__(256) sliced_finish_kernel(const double* __rest
 }
 
 // ------------------------------------------------------------------------------------ sliced Wasserstein per-row shares
-// sliced_match_kernel that also keeps every leading element's sum: the per-thread s (over j ascending), divided once by den[l] =
-// (double)(n m) q_l, goes to cost[l][ra[l][i]], ra the row at rank i (ssort::sort_segment_pairs).  ra is a permutation of 0 .. na - 1, so
-// every row of a direction is written exactly once: plain 8-byte stores.  The tree and the slot are sliced_match_kernel's, so
-// sliced_finish_kernel gives S_l with the bits of the plain call.
-__global__ void __launch_bounds__(kMatchBlock) sliced_match_cost_kernel(const float* __restrict__ a, const uint32_t* __restrict__ ra,
-                                                                        int64_t pa, int64_t na, const float* __restrict__ b, int64_t pb,
-                                                                        int64_t nb, int64_t nblk, const double* __restrict__ den,
-                                                                        double* __restrict__ slots, double* __restrict__ cost) {
-#pragma clang fp contract(off)
-    __shared__ double red[kMatchBlock];
-    const int64_t l = blockIdx.x / nblk, k = blockIdx.x % nblk, i = k * kMatchBlock + threadIdx.x;
-    double s = 0.0;
-    if (i < na) {
-        const double ai = (double)a[l * pa + i];
-        const int64_t lo = i * nb, hi = lo + nb, j0 = lo / na, j1 = (hi - 1) / na;
-        for (int64_t j = j0; j <= j1 && j < nb; ++j) {
-            const int64_t w = (hi < (j + 1) * na ? hi : (j + 1) * na) - (lo > j * na ? lo : j * na);
-            const double diff = ai - (double)b[l * pb + j];
-            const double sq = diff * diff;
-            const double term = (double)w * sq;
-            s += term;
-        }
-        const int64_t row = ra[l * pa + i];
-        if (row < na) cost[l * pa + row] = s / den[l];                                 // always true; keeps a wrong index inside the row
-    }
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = kMatchBlock / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) slots[blockIdx.x] = red[0];
-}
-
-// The other side: one thread per element j of the sorted smaller set b (y at n == m) sums the same terms w_ij (a_i - b_j)^2 over its
-// i0 .. i1 of the sorted larger set a, i ascending, and stores the sum / den[l] at cost[l][rb[l][j]].  Grid: lc * jblk workgroups.
+// The other side of sliced_match_kernel<true>: one thread per element j of the sorted smaller set b (y at n == m) sums the same terms
+// w_ij (a_i - b_j)^2 over its i0 .. i1 of the sorted larger set a, i ascending, and stores the sum / den[l] at cost[l][rb[l][j]].
+// Grid: lc * jblk workgroups.
 __global__ void __launch_bounds__(kMatchBlock) sliced_other_cost_kernel(const float* __restrict__ a, int64_t pa, int64_t na,
                                                                         const float* __restrict__ b, const uint32_t* __restrict__ rb,
                                                                         int64_t pb, int64_t nb, int64_t jblk,
                                                                         const double* __restrict__ den, double* __restrict__ cost) {
-#pragma clang fp contract(off)
     const int64_t l = blockIdx.x / jblk, j = (blockIdx.x % jblk) * kMatchBlock + threadIdx.x;
     if (j >= nb) return;
-    const double bj = (double)b[l * pb + j];
-    const int64_t lo = j * na, hi = lo + na, i0 = lo / nb, i1 = (hi - 1) / nb;
-    double s = 0.0;
-    for (int64_t i = i0; i <= i1 && i < na; ++i) {
-        const int64_t w = (hi < (i + 1) * nb ? hi : (i + 1) * nb) - (lo > i * nb ? lo : i * nb);
-        const double diff = (double)a[l * pa + i] - bj;
-        const double sq = diff * diff;
-        const double term = (double)w * sq;
-        s += term;
-    }
+    const double s = sliced_overlap_sum((double)b[l * pb + j], j, nb, a + l * pa, na);
     const int64_t row = rb[l * pb + j];
     if (row < nb) cost[l * pb + row] = s / den[l];                                     // always true; keeps a wrong index inside the row
 }
@@ -940,20 +921,8 @@ __global__ void __launch_bounds__(kMatchBlock) sliced_song_match_kernel(SongMatc
         double s = 0.0;
         if (i < na) {
             const double ai = (double)a[i];
-            {
-                const int64_t w = nb < na - r ? nb : na - r;
-                const double diff = ai - (double)b[j0];
-                const double sq = diff * diff;
-                const double term = (double)w * sq;
-                s += term;
-            }
-            if (r + nb > na) {
-                const int64_t w = r + nb - na;
-                const double diff = ai - (double)b[j0 + 1];
-                const double sq = diff * diff;
-                const double term = (double)w * sq;
-                s += term;
-            }
+            s += sliced_term(nb < na - r ? nb : na - r, ai, (double)b[j0]);
+            if (r + nb > na) s += sliced_term(r + nb - na, ai, (double)b[j0 + 1]);
         }
         j0 += step_q; r += step_r;
         if (r >= na) { r -= na; ++j0; }
@@ -3143,25 +3112,18 @@ static uint32_t round_direction(float f, int dtype, double* value) {
 }
 
 constexpr int64_t kSlicedWorkspace = (int64_t)1 << 30;     // bytes of chunked buffers by default (FAD_SLICED_WORKSPACE)
+// a call's budget: FAD_SLICED_WORKSPACE where it is a whole number > 0, read per call
+static int64_t sliced_budget() {
+    const char* env = getenv("FAD_SLICED_WORKSPACE");
+    char* end = nullptr;
+    const long long v = env && *env ? strtoll(env, &end, 10) : 0;
+    return end && *end == 0 && v > 0 ? (int64_t)v : kSlicedWorkspace;
+}
+
 struct SlicedPlan { int64_t chunks, lc, passes, share; };
 static SlicedPlan& sliced_plan_value() {
     static thread_local SlicedPlan p{0, 0, 0, 0};
     return p;
-}
-
-// One set's side of a chunk: projections of lc directions from direction l0 on, then the segmented sort -- keys only, or with `idx`
-// the key-index sort that leaves the row of every rank in idx.  Enqueued only.
-static int sliced_project_sort(const Ctx& cx, const Packed& set, const char* theta, const float* zeros, int64_t l0, int64_t lc, float* P,
-                               int64_t ppitch, float* tmp, uint32_t* idx, uint32_t* idx_tmp, uint32_t* counts, uint32_t* bases,
-                               unsigned int* flag) {
-    ProjArgs p{};
-    p.th = theta + l0 * set.pitch; p.rows = set.img; p.zeros = zeros; p.pitch = set.pitch; p.nchunks = set.nchunks;
-    p.TI = kad::blocks(lc); p.TJ = kad::blocks(set.n); p.lc = lc; p.n = set.n; p.P = P; p.ppitch = ppitch; p.flag = flag;
-    const unsigned int grid = (unsigned int)std::min<int64_t>(p.TI * p.TJ, grid_cap(cx.device));
-    FAD_TRY(with_dtype(cx.dtype, [&](auto dt) { sliced_project_kernel<dt><<<grid, kThreads, kLdsProject, cx.st>>>(p); }));
-    if (idx) FAD_HIP_TRY(ssort::sort_segment_pairs(P, tmp, idx, idx_tmp, ppitch, set.n, lc, counts, bases, cx.st));
-    else FAD_HIP_TRY(ssort::sort_segments(P, tmp, ppitch, set.n, lc, counts, bases, cx.st));
-    return FAD_OK;
 }
 
 // fad_sliced_individual_last_plan: chunks, directions per chunk, resident units per direction, songs on the long path, most songs in
@@ -3172,34 +3134,119 @@ static SlicedSongPlan& sliced_song_plan_value() {
     return p;
 }
 
-// The directions rounded to the rows' dtype into their zero-padded image (l_img rows of tpitch bytes), and q_l from the rounded values
-// in index order: what fad_sliced_wasserstein builds, entry by entry.  No device call.
-static int sliced_direction_image(const float* directions, int64_t L, int64_t d, int dtype, int64_t tpitch, int64_t l_img, const char* who,
-                                  std::vector<char>* timg, std::vector<double>* q) {
-    const size_t es = dtype_size(dtype);
-    timg->assign((size_t)(l_img * tpitch), 0);
-    q->resize((size_t)L);
-    for (int64_t l = 0; l < L; ++l) {
-        double ql = 0.0;
-        for (int64_t c = 0; c < d; ++c) {
-            const float f = directions[l * d + c];
-            if (!std::isfinite(f)) return set_error(FAD_ERR_INVALID, "%s: direction %lld has an entry that is not finite", who, (long long)l);
-            double v;
-            const uint32_t bits = round_direction(f, dtype, &v);
-            if (es == 2) {
-                const uint16_t h = (uint16_t)bits;
-                memcpy(&(*timg)[(size_t)(l * tpitch + c * 2)], &h, 2);
-            } else {
-                memcpy(&(*timg)[(size_t)(l * tpitch + c * 4)], &bits, 4);
-            }
-            const double sq = v * v;
-            ql += sq;
-        }
-        if (!(ql > 0) || !std::isfinite(ql))
-            return set_error(FAD_ERR_INVALID, "%s: direction %lld, rounded to the rows' dtype, has the squared length %g", who, (long long)l, ql);
-        (*q)[(size_t)l] = ql;
-    }
+// What the three entries check alike, after their NULL rows and before their row counts, in this order.  ldy: the second set's pitch
+// where the entry checks it here (NULL: fad_sliced_individual checks its songs' pitch later, with its own text).
+static int sliced_check_args(const char* who, const float* directions, int dtype, int64_t d, int64_t ldx, const int64_t* ldy, int projections) {
+    if (!directions) return set_error(FAD_ERR_INVALID, "%s: NULL directions", who);
+    if (dtype == FAD_F64) return set_error(FAD_ERR_INVALID, "%s: float64 rows are not supported; cast to float32 (or float16 / bfloat16)", who);
+    if (dtype != FAD_F16 && dtype != FAD_BF16 && dtype != FAD_F32) return set_error(FAD_ERR_INVALID, "%s: unknown dtype %d", who, dtype);
+    if (d < 1 || d > 2048) return set_error(FAD_ERR_INVALID, "%s: D = %lld is outside 1 .. 2048", who, (long long)d);
+    if (ldy && (ldx < d || *ldy < d))
+        return set_error(FAD_ERR_INVALID, "%s: row pitch %lld / %lld < D = %lld", who, (long long)ldx, (long long)*ldy, (long long)d);
+    if (ldx < d) return set_error(FAD_ERR_INVALID, "%s: row pitch %lld < D = %lld", who, (long long)ldx, (long long)d);
+    if (projections < 1 || projections > 65536) return set_error(FAD_ERR_INVALID, "%s: %d projections, outside 1 .. 65536", who, projections);
     return FAD_OK;
+}
+
+// The directions rounded to the rows' dtype in their zero-padded image (l_img rows of the sets' pitch: kTile rows of zeros follow the
+// last direction), and q_l from the rounded values in index order.  build makes no device call.
+struct SlicedDirections {
+    std::vector<char> timg;
+    std::vector<double> q;
+    int64_t l_img = 0;
+
+    int build(const float* directions, int64_t L, int64_t d, int dtype, const char* who) {
+        const size_t es = dtype_size(dtype);
+        const int64_t tpitch = depth_elems(d, dtype) * (int64_t)es;
+        l_img = (kad::blocks(L) + 1) * kTile;
+        timg.assign((size_t)(l_img * tpitch), 0);
+        q.resize((size_t)L);
+        for (int64_t l = 0; l < L; ++l) {
+            double ql = 0.0;
+            for (int64_t c = 0; c < d; ++c) {
+                const float f = directions[l * d + c];
+                if (!std::isfinite(f)) return set_error(FAD_ERR_INVALID, "%s: direction %lld has an entry that is not finite", who, (long long)l);
+                double v;
+                const uint32_t bits = round_direction(f, dtype, &v);
+                if (es == 2) {
+                    const uint16_t h = (uint16_t)bits;
+                    memcpy(&timg[(size_t)(l * tpitch + c * 2)], &h, 2);
+                } else {
+                    memcpy(&timg[(size_t)(l * tpitch + c * 4)], &bits, 4);
+                }
+                const double sq = v * v;
+                ql += sq;
+            }
+            if (!(ql > 0) || !std::isfinite(ql))
+                return set_error(FAD_ERR_INVALID, "%s: direction %lld, rounded to the rows' dtype, has the squared length %g", who, (long long)l, ql);
+            q[(size_t)l] = ql;
+        }
+        return FAD_OK;
+    }
+    // the image into ws.sliced_theta, enqueued; *theta is its device address
+    int upload(const Ctx& cx, const char** theta) const {
+        FAD_TRY(cx.ws->sliced_theta.reserve(timg.size()));
+        FAD_HIP_TRY(hipMemcpyAsync(cx.ws->sliced_theta.p, timg.data(), timg.size(), hipMemcpyHostToDevice, cx.st));
+        *theta = static_cast<const char*>(cx.ws->sliced_theta.p);
+        return FAD_OK;
+    }
+};
+
+// The projections of one set's rows on lc directions from direction l0 on: the one place that fills ProjArgs.  Enqueued only.
+static int sliced_project(const Ctx& cx, const Packed& set, const char* theta, const float* zeros, int64_t l0, int64_t lc, float* P,
+                          int64_t ppitch, unsigned int* flag) {
+    ProjArgs p{};
+    p.th = theta + l0 * set.pitch; p.rows = set.img; p.zeros = zeros; p.pitch = set.pitch; p.nchunks = set.nchunks;
+    p.TI = kad::blocks(lc); p.TJ = kad::blocks(set.n); p.lc = lc; p.n = set.n; p.P = P; p.ppitch = ppitch; p.flag = flag;
+    const unsigned int grid = (unsigned int)std::min<int64_t>(p.TI * p.TJ, grid_cap(cx.device));
+    return with_dtype(cx.dtype, [&](auto dt) { sliced_project_kernel<dt><<<grid, kThreads, kLdsProject, cx.st>>>(p); });
+}
+
+// the sort's buffers besides the keys: the second key buffer, counts and bases, and for the key-index sort the second
+// index buffer
+struct SlicedSortScratch { float* tmp; uint32_t* idx_tmp; uint32_t* counts; uint32_t* bases; };
+
+// One set's side of a chunk: sliced_project, then the segmented sort -- keys only, or with `idx` the key-index sort that leaves the row
+// of every rank in idx.  Enqueued only.
+static int sliced_project_sort(const Ctx& cx, const Packed& set, const char* theta, const float* zeros, int64_t l0, int64_t lc, float* P,
+                               int64_t ppitch, uint32_t* idx, const SlicedSortScratch& sc, unsigned int* flag) {
+    FAD_TRY(sliced_project(cx, set, theta, zeros, l0, lc, P, ppitch, flag));
+    if (idx) FAD_HIP_TRY(ssort::sort_segment_pairs(P, sc.tmp, idx, sc.idx_tmp, ppitch, set.n, lc, sc.counts, sc.bases, cx.st));
+    else FAD_HIP_TRY(ssort::sort_segments(P, sc.tmp, ppitch, set.n, lc, sc.counts, sc.bases, cx.st));
+    return FAD_OK;
+}
+
+// `cur` rows of n 4-byte words, at a pitch of `pad` words on the device, into the host staging array from its row l0 on; nothing where
+// the array is empty (not asked for).  The sorted arrays are staged on the host: a refusal after the first chunk must leave the
+// caller's arrays as they were.
+template <typename T>
+static int sliced_stage(std::vector<T>& host, int64_t l0, int64_t n, const void* dev, int64_t pad, int64_t cur, hipStream_t st) {
+    static_assert(sizeof(T) == 4, "projections and ranks are 4-byte words");
+    if (host.empty()) return FAD_OK;
+    FAD_HIP_TRY(hipMemcpy2DAsync(host.data() + l0 * n, (size_t)n * 4, dev, (size_t)pad * 4, (size_t)n * 4, (size_t)cur, hipMemcpyDeviceToHost, st));
+    return FAD_OK;
+}
+
+// W_l = S[l * stride] / (nm q_l), one division, into W [L]; mean, spread and maximum over l in index order
+struct SlicedStats { double mean, std_error, best; int64_t best_l; };
+static SlicedStats sliced_stats(const double* S, int64_t stride, double nm, const std::vector<double>& q, double* W) {
+    const int64_t L = (int64_t)q.size();
+    double sum = 0.0, best = -INFINITY;
+    int64_t best_l = 0;
+    for (int64_t l = 0; l < L; ++l) {
+        const double w = S[l * stride] / (nm * q[(size_t)l]);
+        W[l] = w;
+        sum += w;
+        if (w > best) { best = w; best_l = l; }
+    }
+    const double mean = sum / (double)L;
+    double dev2 = 0.0;
+    for (int64_t l = 0; l < L; ++l) {
+        const double dv = W[l] - mean;
+        const double sq = dv * dv;
+        dev2 += sq;
+    }
+    return SlicedStats{mean, L > 1 ? std::sqrt(dev2 / (double)(L - 1)) / std::sqrt((double)L) : (double)NAN, best, best_l};
 }
 
 // What a call over the two whole sets writes besides the result: fad_sliced_wasserstein's detail and, with `shares`,
@@ -3210,18 +3257,14 @@ struct SlicedOut {
     double* share_x; double* share_y; int32_t* index_x; int32_t* index_y;
 };
 
-// fad_sliced_wasserstein and fad_sliced_shares: one body.  Without o.shares the launches are the keys-only sort and sliced_match_kernel;
-// with it the key-index sort, the two cost kernels and the per-row sums -- and the same slots, S_l and statistics either way.
+// fad_sliced_wasserstein and fad_sliced_shares: one body.  Without o.shares the launches are the keys-only sort and
+// sliced_match_kernel<false>; with it the key-index sort, sliced_match_kernel<true>, the other side's cost kernel and the per-row sums
+// -- and the same slots, S_l and statistics either way.
 static int sliced_sets(const char* who, const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype,
                        int on_device, const float* directions, int projections, fad_sliced_result_t* out, const SlicedOut& o, int device,
                        void* stream) {
     if (!x || !y) return set_error(FAD_ERR_INVALID, "%s: NULL rows", who);
-    if (!directions) return set_error(FAD_ERR_INVALID, "%s: NULL directions", who);
-    if (dtype == FAD_F64) return set_error(FAD_ERR_INVALID, "%s: float64 rows are not supported; cast to float32 (or float16 / bfloat16)", who);
-    if (dtype != FAD_F16 && dtype != FAD_BF16 && dtype != FAD_F32) return set_error(FAD_ERR_INVALID, "%s: unknown dtype %d", who, dtype);
-    if (d < 1 || d > 2048) return set_error(FAD_ERR_INVALID, "%s: D = %lld is outside 1 .. 2048", who, (long long)d);
-    if (ldx < d || ldy < d) return set_error(FAD_ERR_INVALID, "%s: row pitch %lld / %lld < D = %lld", who, (long long)ldx, (long long)ldy, (long long)d);
-    if (projections < 1 || projections > 65536) return set_error(FAD_ERR_INVALID, "%s: %d projections, outside 1 .. 65536", who, projections);
+    FAD_TRY(sliced_check_args(who, directions, dtype, d, ldx, &ldy, projections));
     if (n < 1 || m < 1) return set_error(FAD_ERR_TOO_FEW_ROWS, "%s: needs at least 1 row per set, got %lld and %lld", who, (long long)n, (long long)m);
     if (n > INT32_MAX - kTile || m > INT32_MAX - kTile)
         return set_error(FAD_ERR_INVALID, "%s: %lld and %lld rows (at most %d per set)", who, (long long)n, (long long)m, INT32_MAX - kTile);
@@ -3229,27 +3272,18 @@ static int sliced_sets(const char* who, const void* x, int64_t n, int64_t ldx, c
         return set_error(FAD_ERR_INVALID, "%s: n m = %lld x %lld is 2^53 or more: the integer weights would not be exact in float64", who,
                          (long long)n, (long long)m);
     const int64_t L = projections;
-    const size_t es = dtype_size(dtype);
-    const int64_t dp = depth_elems(d, dtype), tpitch = dp * (int64_t)es, l_img = (kad::blocks(L) + 1) * kTile;
-
-    // the directions rounded to the rows' dtype into their zero-padded image, and q_l from the rounded values, before any device call
-    std::vector<char> timg;
-    std::vector<double> q;
-    FAD_TRY(sliced_direction_image(directions, L, d, dtype, tpitch, l_img, who, &timg, &q));
-    const char* env = getenv("FAD_SLICED_WORKSPACE");
-    char* end = nullptr;
-    const long long env_v = env && *env ? strtoll(env, &end, 10) : 0;
-    const int64_t budget = end && *end == 0 && env_v > 0 ? (int64_t)env_v : kSlicedWorkspace;
+    SlicedDirections dirs;                                     // before any device call
+    FAD_TRY(dirs.build(directions, L, d, dtype, who));
+    const int64_t budget = sliced_budget();
 
     Ctx cx;
     FAD_TRY(cx.open(dtype, FAD_KAD_GAUSSIAN, device, stream));
-    KadWorkspace& ws = *cx.ws;
     const hipStream_t st = cx.st;
     Packed px, py;                                             // each set packed once, its norms checked finite
     FAD_TRY(pack_set(cx, 0, x, n, ldx, d, on_device, &px));
     FAD_TRY(pack_set(cx, 1, y, m, ldy, d, on_device, &py));
-    FAD_TRY(ws.sliced_theta.reserve(timg.size()));
-    FAD_HIP_TRY(hipMemcpyAsync(ws.sliced_theta.p, timg.data(), timg.size(), hipMemcpyHostToDevice, st));
+    const char* theta;
+    FAD_TRY(dirs.upload(cx, &theta));
 
     // the chunk: lc directions' projections of both sets, the sort's second buffer, its counts, the match's slots; with shares also
     // the rows at every rank of both sets, the index sort's second buffer and a float64 cost per row of both sets
@@ -3260,59 +3294,51 @@ static int sliced_sets(const char* who, const void* x, int64_t n, int64_t ldx, c
     const int64_t per_dir = 4 * (n_pad + m_pad + t_pad) + 4 * (count_words + ssort::kRadix) + 8 * nblk +
                             (sh ? 4 * (n_pad + m_pad + t_pad) + 8 * (n_pad + m_pad) : 0);
     const int64_t lc = std::max<int64_t>(1, std::min<int64_t>(L, budget / per_dir));
-    const int64_t chunks = cdiv(L, lc);
     Carve cv;
     const auto px_r = cv.add<float>(lc * n_pad), py_r = cv.add<float>(lc * m_pad), tmp_r = cv.add<float>(lc * t_pad);
     const auto counts_r = cv.add<uint32_t>(lc * count_words), bases_r = cv.add<uint32_t>(lc * ssort::kRadix);
     const auto slots_r = cv.add<double>(lc * nblk), s_r = cv.add<double>(L);
-    const auto zeros_r = cv.add<float>(std::max(t_pad, l_img));
+    const auto zeros_r = cv.add<float>(std::max(t_pad, dirs.l_img));
     const auto flag_r = cv.add<unsigned int>(64);
     const auto ix_r = cv.add<uint32_t>(sh ? lc * n_pad : 0), iy_r = cv.add<uint32_t>(sh ? lc * m_pad : 0);
     const auto itmp_r = cv.add<uint32_t>(sh ? lc * t_pad : 0);
     const auto cx_r = cv.add<double>(sh ? lc * n_pad : 0), cy_r = cv.add<double>(sh ? lc * m_pad : 0);
     const auto den_r = cv.add<double>(sh ? L : 0), acc_r = cv.add<double>(sh ? n + m : 0);
-    FAD_TRY(cv.reserve(ws.sliced));
-    FAD_HIP_TRY(hipMemsetAsync(cv.ptr(zeros_r), 0, (size_t)std::max(t_pad, l_img) * sizeof(float), st));
+    FAD_TRY(cv.reserve(cx.ws->sliced));
+    FAD_HIP_TRY(hipMemsetAsync(cv.ptr(zeros_r), 0, (size_t)std::max(t_pad, dirs.l_img) * sizeof(float), st));
     FAD_HIP_TRY(hipMemsetAsync(cv.ptr(flag_r), 0, 64 * sizeof(unsigned int), st));
     const ssort::Plan sp = ssort::plan(n, lc);
-    sliced_plan_value() = SlicedPlan{chunks, lc, ssort::kPasses, sp.G > 1 ? -sp.G : sp.W};
+    sliced_plan_value() = SlicedPlan{cdiv(L, lc), lc, ssort::kPasses, sp.G > 1 ? -sp.G : sp.W};
 
     // W_l's denominator (double)(n m) q_l: the per-row costs are divided by it on the device, S_l on the host below
     const double nm = (double)(n * m);
-    std::vector<double> den((size_t)L);
-    for (int64_t l = 0; l < L; ++l) den[(size_t)l] = nm * q[(size_t)l];
+    std::vector<double> den(sh ? (size_t)L : 0);               // lives until the stream is synchronised below
     if (sh) {
+        for (int64_t l = 0; l < L; ++l) den[(size_t)l] = nm * dirs.q[(size_t)l];
         FAD_HIP_TRY(hipMemcpyAsync(cv.ptr(den_r), den.data(), (size_t)L * sizeof(double), hipMemcpyHostToDevice, st));
         FAD_HIP_TRY(hipMemsetAsync(cv.ptr(acc_r), 0, (size_t)(n + m) * sizeof(double), st));
     }
 
-    // the sorted arrays are staged on the host: a refusal after the first chunk must leave the caller's arrays as they were
-    std::vector<float> sx, sy;
-    std::vector<int32_t> hx, hy;
-    if (o.sorted_x) sx.resize((size_t)(L * n));
-    if (o.sorted_y) sy.resize((size_t)(L * m));
-    if (o.index_x) hx.resize((size_t)(L * n));
-    if (o.index_y) hy.resize((size_t)(L * m));
-    const char* theta = static_cast<const char*>(ws.sliced_theta.p);
+    std::vector<float> sx(o.sorted_x ? (size_t)(L * n) : 0), sy(o.sorted_y ? (size_t)(L * m) : 0);
+    std::vector<int32_t> hx(o.index_x ? (size_t)(L * n) : 0), hy(o.index_y ? (size_t)(L * m) : 0);
     float* Px = cv.ptr(px_r);
     float* Py = cv.ptr(py_r);
     uint32_t* Ix = cv.ptr(ix_r);
     uint32_t* Iy = cv.ptr(iy_r);
     double* acc_x = cv.ptr(acc_r);
     double* acc_y = acc_x + n;
+    const SlicedSortScratch sc{cv.ptr(tmp_r), cv.ptr(itmp_r), cv.ptr(counts_r), cv.ptr(bases_r)};
+    const float* A = x_larger ? Px : Py;
+    const float* B = x_larger ? Py : Px;
+    const int64_t a_pad = x_larger ? n_pad : m_pad, b_pad = x_larger ? m_pad : n_pad;
     for (int64_t l0 = 0; l0 < L; l0 += lc) {
         const int64_t cur = std::min(lc, L - l0);
-        FAD_TRY(sliced_project_sort(cx, px, theta, cv.ptr(zeros_r), l0, cur, Px, n_pad, cv.ptr(tmp_r), sh ? Ix : nullptr, cv.ptr(itmp_r),
-                                    cv.ptr(counts_r), cv.ptr(bases_r), cv.ptr(flag_r)));
-        FAD_TRY(sliced_project_sort(cx, py, theta, cv.ptr(zeros_r), l0, cur, Py, m_pad, cv.ptr(tmp_r), sh ? Iy : nullptr, cv.ptr(itmp_r),
-                                    cv.ptr(counts_r), cv.ptr(bases_r), cv.ptr(flag_r)));
-        const float* A = x_larger ? Px : Py;
-        const float* B = x_larger ? Py : Px;
-        const int64_t a_pad = x_larger ? n_pad : m_pad, b_pad = x_larger ? m_pad : n_pad;
+        FAD_TRY(sliced_project_sort(cx, px, theta, cv.ptr(zeros_r), l0, cur, Px, n_pad, sh ? Ix : nullptr, sc, cv.ptr(flag_r)));
+        FAD_TRY(sliced_project_sort(cx, py, theta, cv.ptr(zeros_r), l0, cur, Py, m_pad, sh ? Iy : nullptr, sc, cv.ptr(flag_r)));
         if (sh) {
-            sliced_match_cost_kernel<<<(unsigned int)(cur * nblk), kMatchBlock, 0, st>>>(A, x_larger ? Ix : Iy, a_pad, na, B, b_pad, nb, nblk,
-                                                                                         cv.ptr(den_r) + l0, cv.ptr(slots_r),
-                                                                                         cv.ptr(x_larger ? cx_r : cy_r));
+            sliced_match_kernel<true><<<(unsigned int)(cur * nblk), kMatchBlock, 0, st>>>(A, x_larger ? Ix : Iy, a_pad, na, B, b_pad, nb, nblk,
+                                                                                          cv.ptr(den_r) + l0, cv.ptr(slots_r),
+                                                                                          cv.ptr(x_larger ? cx_r : cy_r));
             FAD_HIP_TRY(hipGetLastError());
             sliced_other_cost_kernel<<<(unsigned int)(cur * jblk), kMatchBlock, 0, st>>>(A, a_pad, na, B, x_larger ? Iy : Ix, b_pad, nb, jblk,
                                                                                          cv.ptr(den_r) + l0, cv.ptr(x_larger ? cy_r : cx_r));
@@ -3320,19 +3346,16 @@ static int sliced_sets(const char* who, const void* x, int64_t n, int64_t ldx, c
             sliced_share_sum_kernel<<<(unsigned int)cdiv(n, 256), 256, 0, st>>>(cv.ptr(cx_r), n_pad, n, cur, acc_x);
             sliced_share_sum_kernel<<<(unsigned int)cdiv(m, 256), 256, 0, st>>>(cv.ptr(cy_r), m_pad, m, cur, acc_y);
         } else {
-            sliced_match_kernel<<<(unsigned int)(cur * nblk), kMatchBlock, 0, st>>>(A, a_pad, na, B, b_pad, nb, nblk, cv.ptr(slots_r));
+            sliced_match_kernel<false><<<(unsigned int)(cur * nblk), kMatchBlock, 0, st>>>(A, nullptr, a_pad, na, B, b_pad, nb, nblk, nullptr,
+                                                                                           cv.ptr(slots_r), nullptr);
         }
         FAD_HIP_TRY(hipGetLastError());
         sliced_finish_kernel<<<(unsigned int)cdiv(cur, 256), 256, 0, st>>>(cv.ptr(slots_r), nblk, cur, cv.ptr(s_r) + l0);
         FAD_HIP_TRY(hipGetLastError());
-        if (!sx.empty())
-            FAD_HIP_TRY(hipMemcpy2DAsync(sx.data() + l0 * n, (size_t)n * 4, Px, (size_t)n_pad * 4, (size_t)n * 4, (size_t)cur, hipMemcpyDeviceToHost, st));
-        if (!sy.empty())
-            FAD_HIP_TRY(hipMemcpy2DAsync(sy.data() + l0 * m, (size_t)m * 4, Py, (size_t)m_pad * 4, (size_t)m * 4, (size_t)cur, hipMemcpyDeviceToHost, st));
-        if (!hx.empty())
-            FAD_HIP_TRY(hipMemcpy2DAsync(hx.data() + l0 * n, (size_t)n * 4, Ix, (size_t)n_pad * 4, (size_t)n * 4, (size_t)cur, hipMemcpyDeviceToHost, st));
-        if (!hy.empty())
-            FAD_HIP_TRY(hipMemcpy2DAsync(hy.data() + l0 * m, (size_t)m * 4, Iy, (size_t)m_pad * 4, (size_t)m * 4, (size_t)cur, hipMemcpyDeviceToHost, st));
+        FAD_TRY(sliced_stage(sx, l0, n, Px, n_pad, cur, st));
+        FAD_TRY(sliced_stage(sy, l0, m, Py, m_pad, cur, st));
+        FAD_TRY(sliced_stage(hx, l0, n, Ix, n_pad, cur, st));
+        FAD_TRY(sliced_stage(hy, l0, m, Iy, m_pad, cur, st));
     }
     std::vector<double> S((size_t)L), acc(sh ? (size_t)(n + m) : 0);
     unsigned int flag = 0;
@@ -3342,26 +3365,10 @@ static int sliced_sets(const char* who, const void* x, int64_t n, int64_t ldx, c
     FAD_HIP_TRY(hipStreamSynchronize(st));
     if (flag) return set_error(FAD_ERR_NOT_FINITE, "%s: a projection is not finite in float32", who);
 
-    // W_l = S_l / (n m q_l), one division; mean, spread and maximum over l in index order
     std::vector<double> W((size_t)L);
-    double sum = 0.0, best = -INFINITY;
-    int64_t best_l = 0;
-    for (int64_t l = 0; l < L; ++l) {
-        const double w = S[(size_t)l] / den[(size_t)l];
-        W[(size_t)l] = w;
-        sum += w;
-        if (w > best) { best = w; best_l = l; }
-    }
-    const double mean = sum / (double)L;
-    double dev2 = 0.0;
-    for (int64_t l = 0; l < L; ++l) {
-        const double dv = W[(size_t)l] - mean;
-        const double sq = dv * dv;
-        dev2 += sq;
-    }
-    out->sw2_squared = mean;
-    out->std_error = L > 1 ? std::sqrt(dev2 / (double)(L - 1)) / std::sqrt((double)L) : (double)NAN;
-    out->max_sliced = best; out->max_index = best_l;
+    const SlicedStats t = sliced_stats(S.data(), 1, nm, dirs.q, W.data());
+    out->sw2_squared = t.mean; out->std_error = t.std_error;
+    out->max_sliced = t.best; out->max_index = t.best_l;
     out->n = n; out->m = m; out->projections = projections;
     if (o.values) memcpy(o.values, W.data(), (size_t)L * sizeof(double));
     if (o.sorted_x) memcpy(o.sorted_x, sx.data(), sx.size() * sizeof(float));
@@ -3372,6 +3379,145 @@ static int sliced_sets(const char* who, const void* x, int64_t n, int64_t ldx, c
         for (int64_t i = 0; i < n; ++i) o.share_x[i] = acc[(size_t)i] / (double)L;
         for (int64_t j = 0; j < m; ++j) o.share_y[j] = acc[(size_t)(n + j)] / (double)L;
     }
+    return FAD_OK;
+}
+
+// What fad_sliced_individual writes: five values per song and, where not NULL, its detail's arrays.  All host.
+struct SlicedSongOut {
+    double* sw2; double* std_error; double* max_sliced; int64_t* max_index; int32_t* status;
+    double* values; float* sorted_x; float* sorted_rows;
+};
+
+// fad_sliced_individual: the baseline's side of a chunk as sliced_sets has it; the song rows projected in one launch, every song's
+// range sorted on its own (resident units, the long songs by the global sort), one match workgroup per (direction, song).
+static int sliced_songs(const char* who, const void* x, int64_t n, int64_t ldx, const void* rows, int64_t n_rows, int64_t ldy,
+                        const int64_t* offsets, int64_t n_songs, int64_t d, int dtype, int on_device, const float* directions,
+                        int projections, const SlicedSongOut& o, int device, void* stream) {
+    if (!x) return set_error(FAD_ERR_INVALID, "%s: NULL rows", who);
+    if (!offsets) return set_error(FAD_ERR_INVALID, "%s: NULL offsets", who);
+    FAD_TRY(sliced_check_args(who, directions, dtype, d, ldx, nullptr, projections));
+    if (n < 1) return set_error(FAD_ERR_TOO_FEW_ROWS, "%s: needs at least 1 baseline row, got %lld", who, (long long)n);
+    if (n > INT32_MAX - kTile) return set_error(FAD_ERR_INVALID, "%s: %lld baseline rows (at most %d)", who, (long long)n, INT32_MAX - kTile);
+    if (n_songs < 1 || n_songs > INT32_MAX) return set_error(FAD_ERR_INVALID, "%s: %lld songs", who, (long long)n_songs);
+    if (n_rows < 0 || n_rows > INT32_MAX - kTile)
+        return set_error(FAD_ERR_INVALID, "%s: %lld song rows (at most %d)", who, (long long)n_rows, INT32_MAX - kTile);
+    if (n_rows > 0 && !rows) return set_error(FAD_ERR_INVALID, "%s: NULL song rows", who);
+    if (n_rows > 0 && ldy < d) return set_error(FAD_ERR_INVALID, "%s: song row pitch %lld < D = %lld", who, (long long)ldy, (long long)d);
+    if (offsets[0] != 0 || offsets[n_songs] != n_rows)
+        return set_error(FAD_ERR_INVALID, "%s: offsets run from %lld to %lld, not 0 to %lld", who, (long long)offsets[0],
+                         (long long)offsets[n_songs], (long long)n_rows);
+    int64_t longest = 0;
+    for (int64_t s = 0; s < n_songs; ++s) {
+        const int64_t m = offsets[s + 1] - offsets[s];
+        if (m < 0) return set_error(FAD_ERR_INVALID, "%s: offsets decrease at song %lld", who, (long long)s);
+        if (m > 0 && n > (((int64_t)1 << 53) - 1) / m)
+            return set_error(FAD_ERR_INVALID, "%s: n m = %lld x %lld (song %lld) is 2^53 or more: the integer weights would not be exact in "
+                             "float64", who, (long long)n, (long long)m, (long long)s);
+        longest = std::max(longest, m);
+    }
+    const int64_t L = projections;
+    SlicedDirections dirs;                                     // before any device call
+    FAD_TRY(dirs.build(directions, L, d, dtype, who));
+    const int64_t budget = sliced_budget();
+    const songsort::Table table = songsort::build_units(offsets, n_songs);
+    const int64_t n_units = (int64_t)table.units.size(), n_long = (int64_t)table.long_songs.size();
+
+    Ctx cx;
+    FAD_TRY(cx.open(dtype, FAD_KAD_GAUSSIAN, device, stream));
+    const hipStream_t st = cx.st;
+    Packed px, pr{};                                           // the baseline's norms are checked finite; the songs' per song, below
+    FAD_TRY(pack_set(cx, 0, x, n, ldx, d, on_device, &px));
+    if (n_rows > 0) FAD_TRY(pack_image(cx, 1, rows, n_rows, ldy, d, on_device, &pr));
+    const char* theta;
+    FAD_TRY(dirs.upload(cx, &theta));
+
+    // the chunk: lc directions' projections of the baseline and of all song rows, the global sort's second buffer (as wide as the song
+    // rows only when a song takes the long path) and counts, one sum per song
+    const int64_t n_pad = kad::blocks(n) * kTile, r_pad = kad::blocks(n_rows) * kTile, t_pad = std::max(n_pad, n_long ? r_pad : 0);
+    const int64_t count_words = std::max(ssort::counts_elems(n, 1), ssort::counts_elems(longest > songsort::kCapacity ? longest : 1, 1));
+    const int64_t per_dir = 4 * (n_pad + r_pad + t_pad) + 4 * (count_words + ssort::kRadix) + 8 * n_songs;
+    const int64_t lc = std::max<int64_t>(1, std::min<int64_t>(L, budget / per_dir));
+    const int64_t n_zeros = std::max(std::max(n_pad, r_pad), dirs.l_img);
+    Carve cv;
+    const auto px_r = cv.add<float>(lc * n_pad), pr_r = cv.add<float>(lc * r_pad), tmp_r = cv.add<float>(lc * t_pad);
+    const auto counts_r = cv.add<uint32_t>(lc * count_words), bases_r = cv.add<uint32_t>(lc * ssort::kRadix);
+    const auto s_r = cv.add<double>(lc * n_songs);
+    const auto zeros_r = cv.add<float>(n_zeros);
+    const auto off_r = cv.add<int64_t>(n_songs + 1);
+    const auto units_r = cv.add<songsort::Unit>(n_units);
+    const auto ends_r = cv.add<int32_t>((int64_t)table.ends.size());
+    const auto bad_r = cv.add<unsigned int>(n_songs);
+    const auto flag_r = cv.add<unsigned int>(128);             // word 0: the baseline's projections; word 64: the song rows', never read
+    FAD_TRY(cv.reserve(cx.ws->sliced));
+    FAD_HIP_TRY(hipMemsetAsync(cv.ptr(zeros_r), 0, (size_t)n_zeros * sizeof(float), st));
+    FAD_HIP_TRY(hipMemsetAsync(cv.ptr(flag_r), 0, 128 * sizeof(unsigned int), st));
+    FAD_HIP_TRY(hipMemsetAsync(cv.ptr(bad_r), 0, (size_t)n_songs * sizeof(unsigned int), st));
+    FAD_HIP_TRY(hipMemcpyAsync(cv.ptr(off_r), offsets, (size_t)(n_songs + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    if (n_units) {
+        FAD_HIP_TRY(hipMemcpyAsync(cv.ptr(units_r), table.units.data(), (size_t)n_units * sizeof(songsort::Unit), hipMemcpyHostToDevice, st));
+        FAD_HIP_TRY(hipMemcpyAsync(cv.ptr(ends_r), table.ends.data(), table.ends.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    }
+    sliced_song_plan_value() = SlicedSongPlan{{cdiv(L, lc), lc, n_units, n_long, table.most_songs, songsort::kCapacity}};
+
+    if (n_rows > 0) {
+        sliced_song_norm_kernel<<<(unsigned int)cdiv(n_rows, 256), 256, 0, st>>>(pr.h, n_rows, cv.ptr(off_r), n_songs, cv.ptr(bad_r));
+        FAD_HIP_TRY(hipGetLastError());
+    }
+    std::vector<double> S((size_t)(L * n_songs), 0.0);
+    std::vector<float> sx(o.sorted_x ? (size_t)(L * n) : 0), sr(o.sorted_rows ? (size_t)(L * n_rows) : 0);
+    float* Px = cv.ptr(px_r);
+    float* Pr = cv.ptr(pr_r);
+    unsigned int* flags = cv.ptr(flag_r);
+    const SlicedSortScratch sc{cv.ptr(tmp_r), nullptr, cv.ptr(counts_r), cv.ptr(bases_r)};
+    for (int64_t l0 = 0; l0 < L; l0 += lc) {
+        const int64_t cur = std::min(lc, L - l0);
+        FAD_TRY(sliced_project_sort(cx, px, theta, cv.ptr(zeros_r), l0, cur, Px, n_pad, nullptr, sc, flags));
+        if (n_rows > 0) {
+            FAD_TRY(sliced_project(cx, pr, theta, cv.ptr(zeros_r), l0, cur, Pr, r_pad, flags + 64));
+            FAD_HIP_TRY(songsort::sort_units(Pr, r_pad, cur, cv.ptr(units_r), cv.ptr(ends_r), n_units, st));
+            for (const int64_t s : table.long_songs)           // the rare path: the global sort, song by song
+                FAD_HIP_TRY(ssort::sort_segments(Pr + offsets[s], sc.tmp + offsets[s], r_pad, offsets[s + 1] - offsets[s], cur, sc.counts,
+                                                 sc.bases, st));
+            SongMatchArgs ma{Px, n_pad, n, Pr, r_pad, cv.ptr(off_r), n_songs, cv.ptr(s_r), cv.ptr(bad_r)};
+            const int64_t per = std::max<int64_t>(1, (int64_t)INT32_MAX / n_songs);    // directions per launch: the grid's x extent
+            for (int64_t c0 = 0; c0 < cur; c0 += per) {
+                const int64_t cc = std::min(per, cur - c0);
+                ma.px = Px + c0 * n_pad; ma.pr = Pr + c0 * r_pad; ma.S = cv.ptr(s_r) + c0 * n_songs;
+                sliced_song_match_kernel<<<(unsigned int)(cc * n_songs), kMatchBlock, 0, st>>>(ma);
+                FAD_HIP_TRY(hipGetLastError());
+            }
+            FAD_HIP_TRY(hipMemcpyAsync(S.data() + l0 * n_songs, cv.ptr(s_r), (size_t)(cur * n_songs) * sizeof(double), hipMemcpyDeviceToHost, st));
+        }
+        FAD_TRY(sliced_stage(sx, l0, n, Px, n_pad, cur, st));
+        FAD_TRY(sliced_stage(sr, l0, n_rows, Pr, r_pad, cur, st));
+    }
+    std::vector<unsigned int> bad((size_t)n_songs);
+    unsigned int flag = 0;
+    FAD_HIP_TRY(hipMemcpyAsync(bad.data(), cv.ptr(bad_r), (size_t)n_songs * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+    FAD_HIP_TRY(hipMemcpyAsync(&flag, flags, sizeof(flag), hipMemcpyDeviceToHost, st));
+    FAD_HIP_TRY(hipStreamSynchronize(st));
+    if (flag) return set_error(FAD_ERR_NOT_FINITE, "%s: a projection of the baseline is not finite in float32", who);
+
+    // per song, the statistics of fad_sliced_wasserstein over the pair (x, song)
+    std::vector<double> W((size_t)L);
+    for (int64_t s = 0; s < n_songs; ++s) {
+        const int64_t m = offsets[s + 1] - offsets[s];
+        double* vals = o.values ? o.values + s * L : nullptr;
+        if (m == 0 || bad[(size_t)s]) {
+            o.status[s] = m == 0 ? FAD_ERR_TOO_FEW_ROWS : FAD_ERR_NOT_FINITE;
+            o.sw2[s] = o.std_error[s] = o.max_sliced[s] = NAN;
+            o.max_index[s] = -1;
+            for (int64_t l = 0; vals && l < L; ++l) vals[l] = NAN;
+            continue;
+        }
+        const SlicedStats t = sliced_stats(S.data() + s, n_songs, (double)(n * m), dirs.q, W.data());
+        o.status[s] = FAD_OK;
+        o.sw2[s] = t.mean; o.std_error[s] = t.std_error;
+        o.max_sliced[s] = t.best; o.max_index[s] = t.best_l;
+        if (vals) memcpy(vals, W.data(), (size_t)L * sizeof(double));
+    }
+    if (o.sorted_x) memcpy(o.sorted_x, sx.data(), sx.size() * sizeof(float));
+    if (o.sorted_rows && !sr.empty()) memcpy(o.sorted_rows, sr.data(), sr.size() * sizeof(float));
     return FAD_OK;
 }
 
@@ -4310,173 +4456,9 @@ int fad_sliced_individual(const void* x, int64_t n, int64_t ldx, const void* row
     const char* who = "fad_sliced_individual";
     if (!out_sw2 || !out_std_error || !out_max_sliced || !out_max_index || !out_status)
         return set_error(FAD_ERR_INVALID, "%s: NULL per-song output", who);
-    if (!x) return set_error(FAD_ERR_INVALID, "%s: NULL rows", who);
-    if (!offsets) return set_error(FAD_ERR_INVALID, "%s: NULL offsets", who);
-    if (!directions) return set_error(FAD_ERR_INVALID, "%s: NULL directions", who);
-    if (dtype == FAD_F64) return set_error(FAD_ERR_INVALID, "%s: float64 rows are not supported; cast to float32 (or float16 / bfloat16)", who);
-    if (dtype != FAD_F16 && dtype != FAD_BF16 && dtype != FAD_F32) return set_error(FAD_ERR_INVALID, "%s: unknown dtype %d", who, dtype);
-    if (d < 1 || d > 2048) return set_error(FAD_ERR_INVALID, "%s: D = %lld is outside 1 .. 2048", who, (long long)d);
-    if (ldx < d) return set_error(FAD_ERR_INVALID, "%s: row pitch %lld < D = %lld", who, (long long)ldx, (long long)d);
-    if (projections < 1 || projections > 65536) return set_error(FAD_ERR_INVALID, "%s: %d projections, outside 1 .. 65536", who, projections);
-    if (n < 1) return set_error(FAD_ERR_TOO_FEW_ROWS, "%s: needs at least 1 baseline row, got %lld", who, (long long)n);
-    if (n > INT32_MAX - kTile) return set_error(FAD_ERR_INVALID, "%s: %lld baseline rows (at most %d)", who, (long long)n, INT32_MAX - kTile);
-    if (n_songs < 1 || n_songs > INT32_MAX) return set_error(FAD_ERR_INVALID, "%s: %lld songs", who, (long long)n_songs);
-    if (n_rows < 0 || n_rows > INT32_MAX - kTile)
-        return set_error(FAD_ERR_INVALID, "%s: %lld song rows (at most %d)", who, (long long)n_rows, INT32_MAX - kTile);
-    if (n_rows > 0 && !rows) return set_error(FAD_ERR_INVALID, "%s: NULL song rows", who);
-    if (n_rows > 0 && ldy < d) return set_error(FAD_ERR_INVALID, "%s: song row pitch %lld < D = %lld", who, (long long)ldy, (long long)d);
-    if (offsets[0] != 0 || offsets[n_songs] != n_rows)
-        return set_error(FAD_ERR_INVALID, "%s: offsets run from %lld to %lld, not 0 to %lld", who, (long long)offsets[0],
-                         (long long)offsets[n_songs], (long long)n_rows);
-    int64_t longest = 0;
-    for (int64_t s = 0; s < n_songs; ++s) {
-        const int64_t m = offsets[s + 1] - offsets[s];
-        if (m < 0) return set_error(FAD_ERR_INVALID, "%s: offsets decrease at song %lld", who, (long long)s);
-        if (m > 0 && n > (((int64_t)1 << 53) - 1) / m)
-            return set_error(FAD_ERR_INVALID, "%s: n m = %lld x %lld (song %lld) is 2^53 or more: the integer weights would not be exact in "
-                             "float64", who, (long long)n, (long long)m, (long long)s);
-        longest = std::max(longest, m);
-    }
-    const int64_t L = projections;
-    const size_t es = dtype_size(dtype);
-    const int64_t dp = depth_elems(d, dtype), tpitch = dp * (int64_t)es, l_img = (kad::blocks(L) + 1) * kTile;
-    std::vector<char> timg;
-    std::vector<double> q;
-    FAD_TRY(sliced_direction_image(directions, L, d, dtype, tpitch, l_img, who, &timg, &q));
-    const char* env = getenv("FAD_SLICED_WORKSPACE");
-    char* end = nullptr;
-    const long long env_v = env && *env ? strtoll(env, &end, 10) : 0;
-    const int64_t budget = end && *end == 0 && env_v > 0 ? (int64_t)env_v : kSlicedWorkspace;
-    const songsort::Table table = songsort::build_units(offsets, n_songs);
-    const int64_t n_units = (int64_t)table.units.size(), n_long = (int64_t)table.long_songs.size();
-
-    Ctx cx;
-    FAD_TRY(cx.open(dtype, FAD_KAD_GAUSSIAN, device, stream));
-    KadWorkspace& ws = *cx.ws;
-    const hipStream_t st = cx.st;
-    Packed px, pr{};                                           // the baseline's norms are checked finite; the songs' per song, below
-    FAD_TRY(pack_set(cx, 0, x, n, ldx, d, on_device, &px));
-    if (n_rows > 0) FAD_TRY(pack_image(cx, 1, rows, n_rows, ldy, d, on_device, &pr));
-    FAD_TRY(ws.sliced_theta.reserve(timg.size()));
-    FAD_HIP_TRY(hipMemcpyAsync(ws.sliced_theta.p, timg.data(), timg.size(), hipMemcpyHostToDevice, st));
-
-    // the chunk: lc directions' projections of the baseline and of all song rows, the global sort's second buffer (as wide as the song
-    // rows only when a song takes the long path) and counts, one sum per song
-    const int64_t n_pad = kad::blocks(n) * kTile, r_pad = kad::blocks(n_rows) * kTile, t_pad = std::max(n_pad, n_long ? r_pad : 0);
-    const int64_t count_words = std::max(ssort::counts_elems(n, 1), ssort::counts_elems(longest > songsort::kCapacity ? longest : 1, 1));
-    const int64_t per_dir = 4 * (n_pad + r_pad + t_pad) + 4 * (count_words + ssort::kRadix) + 8 * n_songs;
-    const int64_t lc = std::max<int64_t>(1, std::min<int64_t>(L, budget / per_dir));
-    const int64_t chunks = cdiv(L, lc);
-    Carve cv;
-    const auto px_r = cv.add<float>(lc * n_pad), pr_r = cv.add<float>(lc * r_pad), tmp_r = cv.add<float>(lc * t_pad);
-    const auto counts_r = cv.add<uint32_t>(lc * count_words), bases_r = cv.add<uint32_t>(lc * ssort::kRadix);
-    const auto s_r = cv.add<double>(lc * n_songs);
-    const auto zeros_r = cv.add<float>(std::max(std::max(n_pad, r_pad), l_img));
-    const auto off_r = cv.add<int64_t>(n_songs + 1);
-    const auto units_r = cv.add<songsort::Unit>(n_units);
-    const auto ends_r = cv.add<int32_t>((int64_t)table.ends.size());
-    const auto bad_r = cv.add<unsigned int>(n_songs);
-    const auto flag_r = cv.add<unsigned int>(128);             // word 0: the baseline's projections; word 64: the song rows', never read
-    FAD_TRY(cv.reserve(ws.sliced));
-    FAD_HIP_TRY(hipMemsetAsync(cv.ptr(zeros_r), 0, (size_t)std::max(std::max(n_pad, r_pad), l_img) * sizeof(float), st));
-    FAD_HIP_TRY(hipMemsetAsync(cv.ptr(flag_r), 0, 128 * sizeof(unsigned int), st));
-    FAD_HIP_TRY(hipMemsetAsync(cv.ptr(bad_r), 0, (size_t)n_songs * sizeof(unsigned int), st));
-    FAD_HIP_TRY(hipMemcpyAsync(cv.ptr(off_r), offsets, (size_t)(n_songs + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    if (n_units) {
-        FAD_HIP_TRY(hipMemcpyAsync(cv.ptr(units_r), table.units.data(), (size_t)n_units * sizeof(songsort::Unit), hipMemcpyHostToDevice, st));
-        FAD_HIP_TRY(hipMemcpyAsync(cv.ptr(ends_r), table.ends.data(), table.ends.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    }
-    sliced_song_plan_value() = SlicedSongPlan{{chunks, lc, n_units, n_long, table.most_songs, songsort::kCapacity}};
-
-    if (n_rows > 0) {
-        sliced_song_norm_kernel<<<(unsigned int)cdiv(n_rows, 256), 256, 0, st>>>(pr.h, n_rows, cv.ptr(off_r), n_songs, cv.ptr(bad_r));
-        FAD_HIP_TRY(hipGetLastError());
-    }
-    // everything is staged on the host: a refusal after the first chunk must leave the caller's arrays as they were
-    std::vector<double> S((size_t)(L * n_songs), 0.0);
-    std::vector<float> sx, sr;
-    if (detail && detail->sorted_x) sx.resize((size_t)(L * n));
-    if (detail && detail->sorted_rows) sr.resize((size_t)(L * n_rows));
-    const char* theta = static_cast<const char*>(ws.sliced_theta.p);
-    float* Px = cv.ptr(px_r);
-    float* Pr = cv.ptr(pr_r);
-    unsigned int* flags = cv.ptr(flag_r);
-    for (int64_t l0 = 0; l0 < L; l0 += lc) {
-        const int64_t cur = std::min(lc, L - l0);
-        FAD_TRY(sliced_project_sort(cx, px, theta, cv.ptr(zeros_r), l0, cur, Px, n_pad, cv.ptr(tmp_r), nullptr, nullptr, cv.ptr(counts_r),
-                                    cv.ptr(bases_r), flags));
-        if (n_rows > 0) {
-            ProjArgs p{};
-            p.th = theta + l0 * pr.pitch; p.rows = pr.img; p.zeros = cv.ptr(zeros_r); p.pitch = pr.pitch; p.nchunks = pr.nchunks;
-            p.TI = kad::blocks(cur); p.TJ = kad::blocks(n_rows); p.lc = cur; p.n = n_rows; p.P = Pr; p.ppitch = r_pad; p.flag = flags + 64;
-            const unsigned int grid = (unsigned int)std::min<int64_t>(p.TI * p.TJ, grid_cap(device));
-            FAD_TRY(with_dtype(dtype, [&](auto dt) { sliced_project_kernel<dt><<<grid, kThreads, kLdsProject, st>>>(p); }));
-            FAD_HIP_TRY(songsort::sort_units(Pr, r_pad, cur, cv.ptr(units_r), cv.ptr(ends_r), n_units, st));
-            for (const int64_t s : table.long_songs)           // the rare path: the global sort, song by song
-                FAD_HIP_TRY(ssort::sort_segments(Pr + offsets[s], cv.ptr(tmp_r) + offsets[s], r_pad, offsets[s + 1] - offsets[s], cur,
-                                                 cv.ptr(counts_r), cv.ptr(bases_r), st));
-            SongMatchArgs ma{Px, n_pad, n, Pr, r_pad, cv.ptr(off_r), n_songs, cv.ptr(s_r), cv.ptr(bad_r)};
-            const int64_t per = std::max<int64_t>(1, (int64_t)INT32_MAX / n_songs);    // directions per launch: the grid's x extent
-            for (int64_t c0 = 0; c0 < cur; c0 += per) {
-                const int64_t cc = std::min(per, cur - c0);
-                ma.px = Px + c0 * n_pad; ma.pr = Pr + c0 * r_pad; ma.S = cv.ptr(s_r) + c0 * n_songs;
-                sliced_song_match_kernel<<<(unsigned int)(cc * n_songs), kMatchBlock, 0, st>>>(ma);
-                FAD_HIP_TRY(hipGetLastError());
-            }
-            FAD_HIP_TRY(hipMemcpyAsync(S.data() + l0 * n_songs, cv.ptr(s_r), (size_t)(cur * n_songs) * sizeof(double), hipMemcpyDeviceToHost, st));
-        }
-        if (!sx.empty())
-            FAD_HIP_TRY(hipMemcpy2DAsync(sx.data() + l0 * n, (size_t)n * 4, Px, (size_t)n_pad * 4, (size_t)n * 4, (size_t)cur, hipMemcpyDeviceToHost, st));
-        if (!sr.empty())
-            FAD_HIP_TRY(hipMemcpy2DAsync(sr.data() + l0 * n_rows, (size_t)n_rows * 4, Pr, (size_t)r_pad * 4, (size_t)n_rows * 4, (size_t)cur,
-                                         hipMemcpyDeviceToHost, st));
-    }
-    std::vector<unsigned int> bad((size_t)n_songs);
-    unsigned int flag = 0;
-    FAD_HIP_TRY(hipMemcpyAsync(bad.data(), cv.ptr(bad_r), (size_t)n_songs * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
-    FAD_HIP_TRY(hipMemcpyAsync(&flag, flags, sizeof(flag), hipMemcpyDeviceToHost, st));
-    FAD_HIP_TRY(hipStreamSynchronize(st));
-    if (flag) return set_error(FAD_ERR_NOT_FINITE, "%s: a projection of the baseline is not finite in float32", who);
-
-    // per song, as fad_sliced_wasserstein: W_l = S_l / (n m q_l), one division; mean, spread and maximum over l in index order
-    std::vector<double> W((size_t)L);
-    for (int64_t s = 0; s < n_songs; ++s) {
-        const int64_t m = offsets[s + 1] - offsets[s];
-        double* vals = detail && detail->values ? detail->values + s * L : nullptr;
-        if (m == 0 || bad[(size_t)s]) {
-            out_status[s] = m == 0 ? FAD_ERR_TOO_FEW_ROWS : FAD_ERR_NOT_FINITE;
-            out_sw2[s] = out_std_error[s] = out_max_sliced[s] = NAN;
-            out_max_index[s] = -1;
-            for (int64_t l = 0; vals && l < L; ++l) vals[l] = NAN;
-            continue;
-        }
-        const double nm = (double)(n * m);
-        double sum = 0.0, best = -INFINITY;
-        int64_t best_l = 0;
-        for (int64_t l = 0; l < L; ++l) {
-            const double w = S[(size_t)(l * n_songs + s)] / (nm * q[(size_t)l]);
-            W[(size_t)l] = w;
-            sum += w;
-            if (w > best) { best = w; best_l = l; }
-        }
-        const double mean = sum / (double)L;
-        double dev2 = 0.0;
-        for (int64_t l = 0; l < L; ++l) {
-            const double dv = W[(size_t)l] - mean;
-            const double sq = dv * dv;
-            dev2 += sq;
-        }
-        out_status[s] = FAD_OK;
-        out_sw2[s] = mean;
-        out_std_error[s] = L > 1 ? std::sqrt(dev2 / (double)(L - 1)) / std::sqrt((double)L) : (double)NAN;
-        out_max_sliced[s] = best; out_max_index[s] = best_l;
-        if (vals) memcpy(vals, W.data(), (size_t)L * sizeof(double));
-    }
-    if (detail) {
-        if (detail->sorted_x) memcpy(detail->sorted_x, sx.data(), sx.size() * sizeof(float));
-        if (detail->sorted_rows && !sr.empty()) memcpy(detail->sorted_rows, sr.data(), sr.size() * sizeof(float));
-    }
-    return FAD_OK;
+    SlicedSongOut o{out_sw2, out_std_error, out_max_sliced, out_max_index, out_status, nullptr, nullptr, nullptr};
+    if (detail) { o.values = detail->values; o.sorted_x = detail->sorted_x; o.sorted_rows = detail->sorted_rows; }
+    return sliced_songs(who, x, n, ldx, rows, n_rows, ldy, offsets, n_songs, d, dtype, on_device, directions, projections, o, device, stream);
 }
 
 int fad_sliced_individual_last_plan(int64_t out[6]) {

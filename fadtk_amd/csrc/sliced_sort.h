@@ -1,5 +1,5 @@
 // The segmented key sort of the sliced Wasserstein distance (fad_sliced_wasserstein): `segs` segments of n float32 keys
-// each, every segment sorted ascending on its own.  Keys only, no payload.
+// each, every segment sorted ascending on its own.  Keys only here; sliced_sort_pairs.h runs the same passes with a uint32 payload.
 //
 // An LSD radix sort with 8-bit digits: kPasses = 4 passes, each of three launches, between two buffers (the result ends where it began).
 //   - map:     a float goes through the order-preserving map to uint32 (all bits of a negative flipped, the sign bit of the rest set),
@@ -17,6 +17,8 @@
 //              alone: the sort is stable, nothing is placed by order of arrival, the output does not depend on timing.
 // Every pass runs whatever the keys are: all-equal, sorted, reversed and two-valued inputs cost the same.  n >= 1.
 //
+// The scatter body and the pass loop exist once, below, for both forms.
+//
 // Scratch: counts_elems(n, segs) uint32 of counts and 256 per segment of bases.  Nothing here is a template of the callers' dtype: the
 // header stands alone (tests/native/sliced_sort_check.hip includes only it).
 #pragma once
@@ -24,6 +26,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 namespace fad {
 namespace ssort {
@@ -110,8 +113,11 @@ __global__ void __launch_bounds__(kRadix) scan_kernel(Args a) {
     a.bases[(int64_t)blockIdx.x * kRadix + d] = tot[d] - run;
 }
 
-template <bool FIRST, bool LAST>
-__global__ void __launch_bounds__(kThreads) scatter_kernel(Args a) {
+// The scatter of one workgroup.  With PAIRS every key carries a uint32 payload, the position it had in its segment before the sort
+// (sliced_sort_pairs.h): stored at the key's place of a second buffer, idx_out; on the first pass it is the key's own position, later
+// passes read it beside the key from idx_in.  Without PAIRS the two pointers are never touched.
+template <bool FIRST, bool LAST, bool PAIRS>
+__device__ __forceinline__ void scatter_body(const Args& a, const uint32_t* idx_in, uint32_t* idx_out) {
     __shared__ unsigned int place[kRadix];                 // where the next key of digit d of this workgroup goes
     __shared__ unsigned int wcnt[kThreads / 64][kRadix];   // this round's keys of digit d in wave w
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -124,11 +130,15 @@ __global__ void __launch_bounds__(kThreads) scatter_kernel(Args a) {
         __syncthreads();
         const uint32_t* src = a.in + s * a.pitch;
         uint32_t* dst = a.out + s * a.pitch;
+        const uint32_t* isrc = PAIRS ? idx_in + s * a.pitch : nullptr;
+        uint32_t* idst = PAIRS ? idx_out + s * a.pitch : nullptr;
         for (int r = 0; r < kRounds; ++r) {
             const int64_t i0 = wg * kShare + r * kThreads;
             if (i0 >= a.n) break;                                                     // uniform over the workgroup
             const bool live = i0 + tid < a.n;
             uint32_t k = live ? src[i0 + tid] : 0u;
+            uint32_t row = 0u;
+            if (PAIRS) row = FIRST ? (uint32_t)(i0 + tid) : (live ? isrc[i0 + tid] : 0u);
             if (FIRST) k = key_image(k);
             const unsigned int d = (k >> a.shift) & 0xffu;
             unsigned long long peers = __ballot(live);     // the live lanes of the wave with this lane's digit
@@ -144,7 +154,10 @@ __global__ void __launch_bounds__(kThreads) scatter_kernel(Args a) {
             if (live) {
                 unsigned int at = place[d] + below;
                 for (int w = 0; w < wave; ++w) at += wcnt[w][d];
-                if (at < a.n) dst[at] = LAST ? key_bits(k) : k;                       // always true; keeps a wrong count inside the segment
+                if (at < a.n) {                                                       // always true; keeps a wrong count inside the segment
+                    dst[at] = LAST ? key_bits(k) : k;
+                    if (PAIRS) idst[at] = row;
+                }
             }
             __syncthreads();
             unsigned int add = 0;
@@ -156,13 +169,19 @@ __global__ void __launch_bounds__(kThreads) scatter_kernel(Args a) {
     }
 }
 
-// `segs` segments of n float32 keys at keys + s * pitch, sorted ascending in place; `tmp` is a second buffer of the same shape, `counts`
-// and `bases` hold counts_elems(n, segs) and bases_elems(segs) uint32.  Enqueued on `st`; the first error of a launch is returned.
-inline hipError_t sort_segments(float* keys, float* tmp, int64_t pitch, int64_t n, int64_t segs, uint32_t* counts, uint32_t* bases,
-                                hipStream_t st) {
+template <bool FIRST, bool LAST>
+__global__ void __launch_bounds__(kThreads) scatter_kernel(Args a) {
+    scatter_body<FIRST, LAST, false>(a, nullptr, nullptr);
+}
+
+// The kPasses passes over `segs` segments of n keys at keys + s * pitch, between keys and tmp: count, scan, then the pass's scatter --
+// scatter(pass, grid, first, last) launches it, first and last as std::bool_constant, after a.in, a.out and a.shift are set for the
+// pass.  Enqueued on `st`; the first error of a launch is returned.
+template <class Scatter>
+inline hipError_t sort_passes(Args& a, float* keys, float* tmp, int64_t pitch, int64_t n, int64_t segs, uint32_t* counts, uint32_t* bases,
+                              hipStream_t st, Scatter scatter) {
     if (n < 1 || segs < 1) return hipSuccess;
     const Plan p = plan(n, segs);
-    Args a{};
     a.pitch = pitch; a.n = n; a.segs = segs; a.W = p.W; a.G = p.G; a.counts = counts; a.bases = bases;
     const unsigned int grid = (unsigned int)(p.groups * p.W);
     uint32_t* buf[2] = {reinterpret_cast<uint32_t*>(keys), reinterpret_cast<uint32_t*>(tmp)};
@@ -171,13 +190,23 @@ inline hipError_t sort_segments(float* keys, float* tmp, int64_t pitch, int64_t 
         if (pass == 0) count_kernel<true><<<grid, kThreads, 0, st>>>(a);
         else count_kernel<false><<<grid, kThreads, 0, st>>>(a);
         scan_kernel<<<(unsigned int)segs, kRadix, 0, st>>>(a);
-        if (pass == 0) scatter_kernel<true, false><<<grid, kThreads, 0, st>>>(a);
-        else if (pass == kPasses - 1) scatter_kernel<false, true><<<grid, kThreads, 0, st>>>(a);
-        else scatter_kernel<false, false><<<grid, kThreads, 0, st>>>(a);
+        if (pass == 0) scatter(pass, grid, std::true_type{}, std::false_type{});
+        else if (pass == kPasses - 1) scatter(pass, grid, std::false_type{}, std::true_type{});
+        else scatter(pass, grid, std::false_type{}, std::false_type{});
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+// `segs` segments of n float32 keys at keys + s * pitch, sorted ascending in place; `tmp` is a second buffer of the same shape, `counts`
+// and `bases` hold counts_elems(n, segs) and bases_elems(segs) uint32.
+inline hipError_t sort_segments(float* keys, float* tmp, int64_t pitch, int64_t n, int64_t segs, uint32_t* counts, uint32_t* bases,
+                                hipStream_t st) {
+    Args a{};
+    return sort_passes(a, keys, tmp, pitch, n, segs, counts, bases, st, [&](int, unsigned int grid, auto first, auto last) {
+        scatter_kernel<decltype(first)::value, decltype(last)::value><<<grid, kThreads, 0, st>>>(a);
+    });
 }
 #endif
 

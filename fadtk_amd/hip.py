@@ -1244,34 +1244,55 @@ def sliced_directions_array(directions, d: int) -> np.ndarray:
     return t
 
 
+def _sliced_rows(x, y, what: str, device: int):
+    """-> (rows_view of x, rows_view of y) for the sliced entries: ``_kad_pair``, then one D and one dtype.  ``what`` names y in the
+    messages: "y", or "rows" for the songs of ``sliced_individual``, which are checked only where there are any."""
+    vx, vy = _kad_pair(x, y, what, device)
+    has, other = ("the songs have", "the songs") if what == "rows" else ("y has", "y")
+    if what != "rows" or vy[1] > 0:
+        if vx[2] != vy[2]:
+            raise ValueError(f"sliced Wasserstein: x has D = {vx[2]}, {has} D = {vy[2]}")
+        if vx[4] != vy[4]:
+            raise ValueError(f"sliced Wasserstein: x and {other} must have the same dtype")
+    return vx, vy
+
+
+def _sliced_detail(struct, arrays: dict):
+    """-> byref of the detail ``struct`` with the address of every array asked for (its fields' names are the keys), NULL without any"""
+    if not arrays:
+        return None
+    return C.byref(struct(*(arrays[k].ctypes.data if k in arrays else None for k, _ in struct._fields_)))
+
+
+def _sliced_pair_call(entry: str, struct, x, y, directions, device: int, values: bool, sorted_projections: bool, indices: bool,
+                      shares: bool) -> dict:
+    """``fad_sliced_wasserstein`` / ``fad_sliced_shares`` (``entry``, with its detail ``struct``): the rows, the directions, the arrays
+    asked for, the call -> dict of fad_sliced_result and those arrays."""
+    lib = K.load_library()
+    (px, n, d, ldx, cx, dev_x, kx), (py, m, dy, ldy, cy, dev_y, ky) = _sliced_rows(x, y, "y", device)
+    t = sliced_directions_array(directions, d)
+    L = t.shape[0]
+    res = K.FadSlicedResult()
+    out = {"share_x": np.zeros(max(n, 0)), "share_y": np.zeros(max(m, 0))} if shares else {}
+    arrays = {}
+    if values:
+        arrays["values"] = np.zeros(L)
+    for on, stem, dtype in ((sorted_projections, "sorted", np.float32), (indices, "index", np.int32)):
+        if on:
+            arrays[stem + "_x"] = np.zeros((L, n), dtype=dtype)
+            arrays[stem + "_y"] = np.zeros((L, m), dtype=dtype)
+    K.check(getattr(lib, entry)(px, n, ldx, py, m, ldy, d, cx, dev_x, t.ctypes.data, L, C.byref(res), *(a.ctypes.data for a in out.values()),
+                                _sliced_detail(struct, arrays), int(device), K.current_stream_ptr(device)), entry)
+    return {**res.as_dict(), **arrays, **out}
+
+
 def sliced_wasserstein(x, y, directions, device: int = 0, values: bool = False, sorted_projections: bool = False) -> dict:
     """``fad_sliced_wasserstein``: the sliced 2-Wasserstein distance between the rows of x (baseline) and y over the float32 directions
     [L x D] (not normalised: the library divides by their squared lengths) -> dict of fad_sliced_result (sw2_squared, std_error,
     max_sliced, max_index, n, m, projections).  ``values=True`` adds the float64 array ``values`` [L] (W_l); ``sorted_projections=True``
     adds the float32 arrays ``sorted_x`` [L x n] and ``sorted_y`` [L x m].  Both sets are numpy arrays or both torch CUDA tensors of
     one dtype (float16 / bfloat16 / float32)."""
-    lib = K.load_library()
-    (px, n, d, ldx, cx, dev_x, kx), (py, m, dy, ldy, cy, dev_y, ky) = _kad_pair(x, y, "y", device)
-    if d != dy:
-        raise ValueError(f"sliced Wasserstein: x has D = {d}, y has D = {dy}")
-    if cx != cy:
-        raise ValueError("sliced Wasserstein: x and y must have the same dtype")
-    t = sliced_directions_array(directions, d)
-    L = t.shape[0]
-    res = K.FadSlicedResult()
-    arrays = {}
-    if values:
-        arrays["values"] = np.zeros(L)
-    if sorted_projections:
-        arrays["sorted_x"] = np.zeros((L, n), dtype=np.float32)
-        arrays["sorted_y"] = np.zeros((L, m), dtype=np.float32)
-    det = K.FadSlicedDetail(*(arrays[k].ctypes.data if k in arrays else None for k in ("values", "sorted_x", "sorted_y"))) if arrays else None
-    K.check(lib.fad_sliced_wasserstein(px, n, ldx, py, m, ldy, d, cx, dev_x, t.ctypes.data, L, C.byref(res),
-                                       C.byref(det) if det is not None else None, int(device), K.current_stream_ptr(device)),
-            "fad_sliced_wasserstein")
-    out = res.as_dict()
-    out.update(arrays)
-    return out
+    return _sliced_pair_call("fad_sliced_wasserstein", K.FadSlicedDetail, x, y, directions, device, values, sorted_projections, False, False)
 
 
 def sliced_shares(x, y, directions, device: int = 0, values: bool = False, sorted_projections: bool = False, indices: bool = False) -> dict:
@@ -1279,34 +1300,7 @@ def sliced_shares(x, y, directions, device: int = 0, values: bool = False, sorte
     that dict with the float64 arrays ``share_x`` [n] and ``share_y`` [m], each summing to ``sw2_squared`` up to rounding.  ``values``
     and ``sorted_projections`` as there; ``indices=True`` adds the int32 arrays ``index_x`` [L x n] and ``index_y`` [L x m]: the row at
     every rank of every direction (equal projections in ascending row order)."""
-    lib = K.load_library()
-    (px, n, d, ldx, cx, dev_x, kx), (py, m, dy, ldy, cy, dev_y, ky) = _kad_pair(x, y, "y", device)
-    if d != dy:
-        raise ValueError(f"sliced Wasserstein: x has D = {d}, y has D = {dy}")
-    if cx != cy:
-        raise ValueError("sliced Wasserstein: x and y must have the same dtype")
-    t = sliced_directions_array(directions, d)
-    L = t.shape[0]
-    res = K.FadSlicedResult()
-    share_x, share_y = np.zeros(max(n, 0)), np.zeros(max(m, 0))
-    arrays = {}
-    if values:
-        arrays["values"] = np.zeros(L)
-    if sorted_projections:
-        arrays["sorted_x"] = np.zeros((L, n), dtype=np.float32)
-        arrays["sorted_y"] = np.zeros((L, m), dtype=np.float32)
-    if indices:
-        arrays["index_x"] = np.zeros((L, n), dtype=np.int32)
-        arrays["index_y"] = np.zeros((L, m), dtype=np.int32)
-    det = K.FadSlicedSharesDetail(*(arrays[k].ctypes.data if k in arrays else None
-                                    for k in ("values", "sorted_x", "sorted_y", "index_x", "index_y"))) if arrays else None
-    K.check(lib.fad_sliced_shares(px, n, ldx, py, m, ldy, d, cx, dev_x, t.ctypes.data, L, C.byref(res), share_x.ctypes.data,
-                                  share_y.ctypes.data, C.byref(det) if det is not None else None, int(device),
-                                  K.current_stream_ptr(device)),
-            "fad_sliced_shares")
-    out = res.as_dict()
-    out.update(arrays, share_x=share_x, share_y=share_y)
-    return out
+    return _sliced_pair_call("fad_sliced_shares", K.FadSlicedSharesDetail, x, y, directions, device, values, sorted_projections, indices, True)
 
 
 def sliced_last_plan() -> dict:
@@ -1327,11 +1321,7 @@ def sliced_individual(x, rows, offsets: Sequence[int], directions, device: int =
     (every song's range sorted on its own).  x and rows are both numpy arrays or both torch CUDA tensors of one dtype (float16 /
     bfloat16 / float32)."""
     lib = K.load_library()
-    (px, n, d, ldx, cx, dev_x, kx), (py, m, dy, ldy, cy, dev_y, ky) = _kad_pair(x, rows, "rows", device)
-    if m > 0 and d != dy:
-        raise ValueError(f"sliced Wasserstein: x has D = {d}, the songs have D = {dy}")
-    if m > 0 and cx != cy:
-        raise ValueError("sliced Wasserstein: x and the songs must have the same dtype")
+    (px, n, d, ldx, cx, dev_x, kx), (py, m, dy, ldy, cy, dev_y, ky) = _sliced_rows(x, rows, "rows", device)
     off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
     if off.ndim != 1 or off.shape[0] < 2:
         raise ValueError("sliced Wasserstein: offsets must be a 1-D sequence of S + 1 row indices, S >= 1")
@@ -1347,12 +1337,10 @@ def sliced_individual(x, rows, offsets: Sequence[int], directions, device: int =
     if sorted:
         arrays["sorted_x"] = np.zeros((L, n), dtype=np.float32)
         arrays["sorted_rows"] = np.zeros((L, m), dtype=np.float32)
-    det = K.FadSlicedIndividualDetail(*(arrays[k].ctypes.data if k in arrays else None
-                                        for k in ("values", "sorted_x", "sorted_rows"))) if arrays else None
     K.check(lib.fad_sliced_individual(px, n, ldx, py if m > 0 else None, m, max(ldy, d), off.ctypes.data_as(C.POINTER(C.c_int64)), S, d,
                                       cx, dev_x, t.ctypes.data, L, out["sw2_squared"].ctypes.data, out["std_error"].ctypes.data,
                                       out["max_sliced"].ctypes.data, out["max_index"].ctypes.data, out["status"].ctypes.data,
-                                      C.byref(det) if det is not None else None, int(device), K.current_stream_ptr(device)),
+                                      _sliced_detail(K.FadSlicedIndividualDetail, arrays), int(device), K.current_stream_ptr(device)),
             "fad_sliced_individual")
     out.update(arrays)
     out.update(n=n, projections=L)

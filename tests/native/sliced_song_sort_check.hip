@@ -9,48 +9,24 @@
 //   hipcc --offload-arch=gfx950 -O2 -std=c++17 -o tests/native/sliced_song_sort_check tests/native/sliced_song_sort_check.hip
 #include "../../fadtk_amd/csrc/sliced_song_sort.h"
 
-#include <algorithm>
-#include <cfloat>
-#include <cstdio>
-#include <cstring>
-#include <random>
-#include <vector>
+#include "sliced_keys.h"
 
 using namespace fad;
 
-#define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("%s failed: %s\n", #x, hipGetErrorString(e_)); return 2; } } while (0)
-
-static const uint32_t kGuard = 0x7fc0dead;                 // a NaN payload no generator below produces on purpose
 static const int64_t C = songsort::kCapacity;
-static int g_checks = 0, g_fail = 0;
 
-static uint32_t bits_of(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
-
-// key set `kind` for direction s, element i of n
-static uint32_t make_key(int kind, int64_t s, int64_t i, int64_t n, std::mt19937& rng) {
+// sliced_keys.h's key set `kind` for direction s, element i of n, with NaN bit patterns let in: among the special values of kind 2,
+// wherever the shared bytes of kinds 3 .. 6 make one, and kind 10 is any word at all
+static uint32_t song_key(int kind, int64_t s, int64_t i, int64_t n, std::mt19937& rng) {
     switch (kind) {
-        case 0: {
-            uint32_t u = rng();
-            if ((u & 0x7f800000u) == 0x7f800000u) u &= 0xff7fffffu;
-            return u;
-        }
-        case 1: return (rng() & 0x807fffffu);                                         // denormals and zeros of both signs
-        case 2: {                                                                     // a few special values, many ties, NaNs of both signs
+        case 2: {
             static const uint32_t nan[] = {0x7fc00000u, 0xffc00000u, 0x7f800001u, 0xffffffffu};
-            static const float v[] = {0.f, -0.f, FLT_MAX, -FLT_MAX, FLT_MIN, -FLT_MIN, 1.f, -1.f, INFINITY, -INFINITY, 1e-45f, -1e-45f};
             const uint32_t r = rng() % 16;
-            return r < 12 ? bits_of(v[r]) : nan[r - 12];
+            return r < 12 ? bits_of(kSpecial[r]) : nan[r - 12];
         }
-        case 3: case 4: case 5: case 6: {                                             // three bytes shared: byte (kind - 3) alone differs
-            const int b = kind - 3;
-            uint32_t u = 0x40490fdbu ^ (((uint32_t)s * 0x01010101u) & 0x7f7f7f7fu);
-            u = (u & ~(0xffu << (8 * b))) | ((rng() & 0xffu) << (8 * b));
-            return u;
-        }
-        case 7: return bits_of(-3.5f);                                                // all equal
-        case 8: return bits_of((float)(i - n / 2) * 0.25f);                           // sorted
-        case 9: return bits_of((float)(n / 2 - i) * 0.25f);                           // reversed
-        default: return rng();                                                        // any word, NaN patterns included
+        case 3: case 4: case 5: case 6: return shared_bytes_key(kind, s, rng);
+        case 10: return rng();
+        default: return make_key(kind, s, i, n, rng);
     }
 }
 
@@ -65,7 +41,7 @@ static int run(int kind, int pat, const std::vector<int64_t>& lens, int64_t dirs
     std::mt19937 rng((uint32_t)(kind * 1000003 + pat * 7919 + dirs));
     std::vector<uint32_t> host((size_t)total, kGuard), back((size_t)total);
     for (int64_t l = 0; l < dirs; ++l)
-        for (int64_t i = 0; i < n; ++i) host[(size_t)(guard + l * pitch + i)] = make_key(kind, l, i, n, rng);
+        for (int64_t i = 0; i < n; ++i) host[(size_t)(guard + l * pitch + i)] = song_key(kind, l, i, n, rng);
     uint32_t* keys;
     songsort::Unit* units_d;
     int32_t* ends_d;
@@ -94,14 +70,8 @@ static int run(int kind, int pat, const std::vector<int64_t>& lens, int64_t dirs
         for (int64_t i = n; i < pitch; ++i) bad += back[row + (size_t)i] != kGuard;
     }
     for (int64_t i = 0; i < guard; ++i) bad += back[(size_t)i] != kGuard || back[(size_t)(total - 1 - i)] != kGuard;
-    ++g_checks;
-    if (bad) { ++g_fail; printf("FAILED kind %d pattern %d dirs %lld: %d words differ\n", kind, pat, (long long)dirs, bad); }
+    expect_none(bad, "pattern x directions", kind, pat, dirs);
     return 0;
-}
-
-static void expect(bool ok, const char* what) {
-    ++g_checks;
-    if (!ok) { ++g_fail; printf("FAILED table: %s\n", what); }
 }
 
 int main() {
@@ -148,7 +118,5 @@ int main() {
                 const int rc = run(kind, pat, pats[(size_t)pat], dirs);
                 if (rc) return rc;
             }
-    printf("%d checks, %d failed\n", g_checks, g_fail);
-    if (g_fail) printf("%d checks FAILED\n", g_fail); else printf("all checks passed\n");
-    return g_fail ? 1 : 0;
+    return report();
 }

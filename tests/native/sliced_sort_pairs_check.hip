@@ -1,7 +1,7 @@
 // The key-index segmented sort of fadtk_amd/csrc/sliced_sort_pairs.h on its own, below fad_sliced_shares: this file includes that
 // header (which includes sliced_sort.h) and nothing else of the library.  Every segment's keys AND indices are compared bit for bit with
 // std::stable_sort of (mapped uint32 key, position) by key -- so equal keys must carry ascending positions -- over the key families
-// of sliced_sort_check.hip: random bits, denormals and both zeros, a few special values with many ties (+-0, +-FLT_MAX, +-FLT_MIN,
+// of sliced_keys.h (kinds 0 .. 10): random bits, denormals and both zeros, a few special values with many ties (+-0, +-FLT_MAX, +-FLT_MIN,
 // +-inf), keys that share three of their four bytes (one digit alone decides, per byte position), all keys equal (the indices must come
 // out as the identity), sorted, reversed and two-valued input -- at 1, 3 and 65 segments of 1, 255, 256, 257, 2047, 2048, 2049, 4100
 // and 10 007 keys.  The index buffer goes in filled with the guard word: the sort must not need it initialised.  The words after each
@@ -10,49 +10,11 @@
 //   hipcc --offload-arch=gfx950 -O2 -std=c++17 -o tests/native/sliced_sort_pairs_check tests/native/sliced_sort_pairs_check.hip
 #include "../../fadtk_amd/csrc/sliced_sort_pairs.h"
 
-#include <algorithm>
-#include <cfloat>
-#include <cstdio>
-#include <cstring>
-#include <random>
+#include "sliced_keys.h"
+
 #include <utility>
-#include <vector>
 
 using namespace fad;
-
-#define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("%s failed: %s\n", #x, hipGetErrorString(e_)); return 2; } } while (0)
-
-static const uint32_t kGuard = 0x7fc0dead;                 // a NaN payload no generator below produces, and no valid position
-static int g_checks = 0, g_fail = 0;
-
-static uint32_t bits_of(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
-
-// key set `kind` for segment s, element i of n
-static uint32_t make_key(int kind, int64_t s, int64_t i, int64_t n, std::mt19937& rng) {
-    switch (kind) {
-        case 0: {
-            uint32_t u = rng();
-            if ((u & 0x7f800000u) == 0x7f800000u) u &= 0xff7fffffu;                   // no NaN: not ordered
-            return u;
-        }
-        case 1: return (rng() & 0x807fffffu);                                         // denormals and zeros of both signs
-        case 2: {                                                                     // a few special values, many ties
-            static const float v[] = {0.f, -0.f, FLT_MAX, -FLT_MAX, FLT_MIN, -FLT_MIN, 1.f, -1.f, INFINITY, -INFINITY, 1e-45f, -1e-45f};
-            return bits_of(v[rng() % 12]);
-        }
-        case 3: case 4: case 5: case 6: {                                             // three bytes shared: byte (kind - 3) alone differs
-            const int b = kind - 3;
-            uint32_t u = 0x40490fdbu ^ (((uint32_t)s * 0x01010101u) & 0x7f7f7f7fu);
-            u = (u & ~(0xffu << (8 * b))) | ((rng() & 0xffu) << (8 * b));
-            if ((u & 0x7f800000u) == 0x7f800000u) u ^= 0x00800000u;
-            return u;
-        }
-        case 7: return bits_of(-3.5f);                                                // all equal
-        case 8: return bits_of((float)(i - n / 2) * 0.25f);                           // sorted
-        case 9: return bits_of((float)(n / 2 - i) * 0.25f);                           // reversed
-        default: return bits_of((rng() & 1u) ? 2.0f : -0.0f);                         // two-valued
-    }
-}
 
 static int run(int kind, int64_t n, int64_t segs) {
     const int64_t pitch = n + 5, guard = 64;
@@ -104,8 +66,7 @@ static int run(int kind, int64_t n, int64_t segs) {
         for (int b = 0; b < 4; ++b) bad += back[b][(size_t)i] != kGuard || back[b][(size_t)(total - 1 - i)] != kGuard;
         bad += cg[(size_t)i] != kGuard || bg[(size_t)i] != kGuard;
     }
-    ++g_checks;
-    if (bad) { ++g_fail; printf("FAILED kind %d n %lld segs %lld: %d words differ\n", kind, (long long)n, (long long)segs, bad); }
+    expect_none(bad, "keys x segments", kind, n, segs);
     return 0;
 }
 
@@ -120,7 +81,5 @@ int main() {
                 const int rc = run(kind, n, segs);
                 if (rc) return rc;
             }
-    printf("%d checks, %d failed\n", g_checks, g_fail);
-    if (g_fail) printf("%d checks FAILED\n", g_fail); else printf("all checks passed\n");
-    return g_fail ? 1 : 0;
+    return report();
 }
