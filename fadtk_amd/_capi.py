@@ -124,6 +124,17 @@ class FadSlicedIndividualDetail(C.Structure):
     _fields_ = [("values", C.c_void_p), ("sorted_x", C.c_void_p), ("sorted_rows", C.c_void_p)]
 
 
+class FadSlicedPermutationResult(C.Structure):
+    _fields_ = [("observed", FadSlicedResult), ("p_value", C.c_double), ("p_value_max", C.c_double), ("permutations", C.c_int64)]
+
+    def as_dict(self):
+        return {**self.observed.as_dict(), "p_value": self.p_value, "p_value_max": self.p_value_max, "permutations": self.permutations}
+
+
+class FadSlicedPermutationDetail(C.Structure):
+    _fields_ = [("values", C.c_void_p), ("sorted_z", C.c_void_p), ("index_z", C.c_void_p)]
+
+
 _P = C.c_void_p
 _I64 = C.c_int64
 # name -> (restype, argtypes)     -- one entry per declaration in include/fad_hip.h
@@ -217,6 +228,10 @@ SIGNATURES = {
     "fad_sliced_individual": (C.c_int, [_P, _I64, _I64, _P, _I64, _I64, C.POINTER(_I64), _I64, _I64, C.c_int, C.c_int, _P, C.c_int,
                                         _P, _P, _P, _P, _P, C.POINTER(FadSlicedIndividualDetail), C.c_int, _P]),
     "fad_sliced_individual_last_plan": (C.c_int, [C.POINTER(_I64)]),
+    "fad_sliced_permutation_test": (C.c_int, [_P, _I64, _I64, _P, _I64, _I64, _I64, C.c_int, C.c_int, _P, C.c_int, _P, _I64, C.c_int,
+                                              C.POINTER(FadSlicedPermutationResult), _P, _P, C.POINTER(FadSlicedPermutationDetail),
+                                              C.c_int, _P]),
+    "fad_sliced_permutation_last_plan": (C.c_int, [C.POINTER(_I64)]),
     "fad_sinkhorn": (C.c_int, [_P, _I64, _I64, _P, _I64, _I64, _I64, C.c_int, C.c_int, C.c_double, C.c_int, C.POINTER(FadSinkhornResult),
                                C.POINTER(FadSinkhornDetail), C.c_int, _P]),
 }

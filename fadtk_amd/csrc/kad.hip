@@ -30,6 +30,7 @@
 #include "sliced_sort.h"
 #include "sliced_sort_pairs.h"
 #include "sliced_song_sort.h"
+#include "sliced_split.h"
 
 #include <algorithm>
 #include <cmath>
@@ -2738,7 +2739,8 @@ static int perm_check_args(const void* x, int64_t n, int64_t ldx, const void* y,
 }
 
 // host labellings: every one with exactly n ones and no bit at or past N (device labellings are counted on the device)
-static int perm_check_labels(int64_t n, int64_t m, const uint32_t* labels, int64_t n_perm, int labels_on_device) {
+static int perm_check_labels(int64_t n, int64_t m, const uint32_t* labels, int64_t n_perm, int labels_on_device,
+                             const char* who = "fad_kad_permutation_test") {
     const int64_t N = n + m;
     const int64_t nwl = cdiv(N, 32);                                                   // words per labelling in the ABI
     if (!labels_on_device) {
@@ -2748,15 +2750,16 @@ static int perm_check_labels(int64_t n, int64_t m, const uint32_t* labels, int64
             int64_t ones = 0;
             for (int64_t b = 0; b < nwl; ++b) ones += __builtin_popcount(row[b]);
             if (ones != n || (row[nwl - 1] & ~tail))
-                return set_error(FAD_ERR_INVALID, "fad_kad_permutation_test: labelling %lld has %lld ones%s; every labelling needs exactly n = %lld"
-                                 " and no bit at or past N = %lld", (long long)q, (long long)ones, (row[nwl - 1] & ~tail) ? " and a bit past N" : "",
+                return set_error(FAD_ERR_INVALID, "%s: labelling %lld has %lld ones%s; every labelling needs exactly n = %lld"
+                                 " and no bit at or past N = %lld", who, (long long)q, (long long)ones, (row[nwl - 1] & ~tail) ? " and a bit past N" : "",
                                  (long long)n, (long long)N);
         }
     }
     return FAD_OK;
 }
 
-// Z's image and h, the labellings (the observed one first) and their row and column words, all on the device
+// Z's image and h, the labellings (the observed one first) and their row and column words, all on the device.  perm_prepare's two
+// refusals name `who` and `family`: the KAD entries' by default, fad_sliced_permutation_test gives its own.
 struct PermPrep {
     Packed z;                                                                          // the pooled rows, N of them
     int64_t n, m, N, TZ, z_pad, nwz, dp, NL, W;
@@ -2764,7 +2767,8 @@ struct PermPrep {
 };
 
 static int perm_prepare(const Ctx& cx, const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int on_device,
-                        const uint32_t* labels, int64_t n_perm, int labels_on_device, PermPrep* out) {
+                        const uint32_t* labels, int64_t n_perm, int labels_on_device, PermPrep* out,
+                        const char* who = "fad_kad_permutation_test", const char* family = "KAD") {
     KadWorkspace& ws = *cx.ws;
     const hipStream_t st = cx.st;
     const int64_t N = n + m, nwl = cdiv(N, 32);
@@ -2798,10 +2802,10 @@ static int perm_prepare(const Ctx& cx, const void* x, int64_t n, int64_t ldx, co
     FAD_HIP_TRY(hipMemcpyAsync(info, info_d, sizeof(info), hipMemcpyDeviceToHost, st));
     FAD_HIP_TRY(hipMemcpyAsync(&bad, bad_d, sizeof(bad), hipMemcpyDeviceToHost, st));
     FAD_HIP_TRY(hipStreamSynchronize(st));
-    if (bad) return set_error(FAD_ERR_INVALID, "fad_kad_permutation_test: %llu labellings do not have exactly n = %lld ones below N = %lld", bad,
+    if (bad) return set_error(FAD_ERR_INVALID, "%s: %llu labellings do not have exactly n = %lld ones below N = %lld", who, bad,
                               (long long)n, (long long)N);
     if (info[1] != 0.0)
-        return set_error(FAD_ERR_NOT_FINITE, "KAD: %lld of %lld rows of x and y have a NaN/Inf norm", (long long)info[1], (long long)N);
+        return set_error(FAD_ERR_NOT_FINITE, "%s: %lld of %lld rows of x and y have a NaN/Inf norm", family, (long long)info[1], (long long)N);
 
     // the row and column words of every labelling word
     FAD_TRY(ws.perm_rows.reserve((size_t)(W * z_pad) * sizeof(uint32_t)));
@@ -3379,6 +3383,147 @@ static int sliced_sets(const char* who, const void* x, int64_t n, int64_t ldx, c
         for (int64_t i = 0; i < n; ++i) o.share_x[i] = acc[(size_t)i] / (double)L;
         for (int64_t j = 0; j < m; ++j) o.share_y[j] = acc[(size_t)(n + j)] / (double)L;
     }
+    return FAD_OK;
+}
+
+// ------------------------------------------------------------------------------- sliced Wasserstein permutation test
+// fad_sliced_permutation_last_plan: sort chunks, directions per sort chunk, pair rounds in all, directions per round, labelling words
+// per round, the sort's share (as fad_sliced_last_plan reports it, of the pooled rows)
+struct SlicedPermPlan { int64_t v[6]; };
+static SlicedPermPlan& sliced_perm_plan_value() {
+    static thread_local SlicedPermPlan p{{0, 0, 0, 0, 0, 0}};
+    return p;
+}
+
+// fad_sliced_permutation_test's detail.  All host; every pointer may be NULL.
+struct SlicedPermOut { double* values; float* sorted_z; int32_t* index_z; };
+
+// fad_sliced_permutation_test.  The pooled rows are projected and sorted once per direction, with the row at every rank
+// (sliced_project_sort's key-index form); the sorted keys and the rows never see a label.  A round takes some directions of the sort
+// chunk and some labelling words: ssplit's stable split gives every (direction, labelling) pair of the round its two sorted groups,
+// and sliced_match_kernel<false> and sliced_finish_kernel run over the pairs as if they were the directions of a chunk -- the larger
+// group leads, the label-1 group at n == m, as x leads in sliced_sets.  S [L][NL] stays on the device until every round has run.
+static int sliced_permutation(const char* who, const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d,
+                              int dtype, int on_device, const float* directions, int projections, const uint32_t* labels, int64_t n_perm,
+                              int labels_on_device, fad_sliced_permutation_result_t* out, double* null_out, double* null_max,
+                              const SlicedPermOut& o, int device, void* stream) {
+    if (!x || !y) return set_error(FAD_ERR_INVALID, "%s: NULL rows", who);
+    FAD_TRY(sliced_check_args(who, directions, dtype, d, ldx, &ldy, projections));
+    if (n < 1 || m < 1) return set_error(FAD_ERR_TOO_FEW_ROWS, "%s: needs at least 1 row per set, got %lld and %lld", who, (long long)n, (long long)m);
+    const int64_t N = n + m, L = projections, NL = n_perm + 1;
+    if (n > INT32_MAX - kTile || m > INT32_MAX - kTile || N > INT32_MAX - kTile)
+        return set_error(FAD_ERR_INVALID, "%s: %lld rows in all (at most %d)", who, (long long)N, INT32_MAX - kTile);
+    if (n > (((int64_t)1 << 53) - 1) / m)
+        return set_error(FAD_ERR_INVALID, "%s: n m = %lld x %lld is 2^53 or more: the integer weights would not be exact in float64", who,
+                         (long long)n, (long long)m);
+    if (n_perm < 1 || n_perm > kad::kPermMax)
+        return set_error(FAD_ERR_INVALID, "%s: %lld permutations (1 .. %lld)", who, (long long)n_perm, (long long)kad::kPermMax);
+    if (!labels) return set_error(FAD_ERR_INVALID, "%s: NULL labels", who);
+    SlicedDirections dirs;                                     // before any device call
+    FAD_TRY(dirs.build(directions, L, d, dtype, who));
+    FAD_TRY(perm_check_labels(n, m, labels, n_perm, labels_on_device, who));
+    const int64_t budget = sliced_budget();
+
+    Ctx cx;
+    FAD_TRY(cx.open(dtype, FAD_KAD_GAUSSIAN, device, stream));
+    const hipStream_t st = cx.st;
+    PermPrep pp;                                               // Z packed once, its norms and the labellings checked; rows_d is not read
+    FAD_TRY(perm_prepare(cx, x, n, ldx, y, m, ldy, d, on_device, labels, n_perm, labels_on_device, &pp, who, who));
+    const char* theta;
+    FAD_TRY(dirs.upload(cx, &theta));
+
+    // the sort chunk: lc directions' pooled keys and rows, their second buffers, the sort's counts -- a quarter of the budget.  The
+    // round: dr directions x wr labelling words, 32 pairs a word, each pair its two groups, its match slots and the split's counts.
+    const bool one_leads = n >= m;
+    const int64_t z_pad = pp.z_pad, W = pp.W, n_pad = kad::blocks(n) * kTile, m_pad = kad::blocks(m) * kTile;
+    const int64_t na = one_leads ? n : m, nb = one_leads ? m : n, nblk = cdiv(na, kMatchBlock), G = ssplit::groups(N);
+    const int64_t count_words = ssort::counts_elems(N, 1);
+    const int64_t per_dir = 16 * z_pad + 4 * (count_words + ssort::kRadix);
+    const int64_t lc = std::max<int64_t>(1, std::min<int64_t>(L, budget / 4 / per_dir));
+    const int64_t per_word = 32 * (4 * (n_pad + m_pad) + 8 * nblk + 4 * G + 8);
+    const int64_t most = (int64_t)INT32_MAX / (32 * std::max(nblk, G));                // words a launch's grid can hold
+    const int64_t units = std::max<int64_t>(1, std::min(most, (budget - budget / 4) / per_word));
+    const int64_t wr = std::min(W, units), dr = units >= W ? std::min(lc, units / W) : 1;
+    Carve cv;
+    const auto k_r = cv.add<float>(lc * z_pad), tmp_r = cv.add<float>(lc * z_pad);
+    const auto i_r = cv.add<uint32_t>(lc * z_pad), itmp_r = cv.add<uint32_t>(lc * z_pad);
+    const auto counts_r = cv.add<uint32_t>(lc * count_words), bases_r = cv.add<uint32_t>(lc * ssort::kRadix);
+    const auto one_r = cv.add<float>(dr * wr * 32 * n_pad), zero_r = cv.add<float>(dr * wr * 32 * m_pad);
+    const auto slots_r = cv.add<double>(dr * wr * 32 * nblk), sround_r = cv.add<double>(dr * wr * 32);
+    const auto scounts_r = cv.add<uint32_t>(ssplit::counts_elems(N, dr, wr));
+    const auto s_r = cv.add<double>(L * NL);
+    const auto zeros_r = cv.add<float>(std::max(z_pad, dirs.l_img));
+    const auto flag_r = cv.add<unsigned int>(64);
+    FAD_TRY(cv.reserve(cx.ws->sliced));
+    FAD_HIP_TRY(hipMemsetAsync(cv.ptr(zeros_r), 0, (size_t)std::max(z_pad, dirs.l_img) * sizeof(float), st));
+    FAD_HIP_TRY(hipMemsetAsync(cv.ptr(flag_r), 0, 64 * sizeof(unsigned int), st));
+    int64_t rounds = 0;
+    for (int64_t l0 = 0; l0 < L; l0 += lc) rounds += cdiv(std::min(lc, L - l0), dr) * cdiv(W, wr);
+    const ssort::Plan sp = ssort::plan(N, lc);
+    sliced_perm_plan_value() = SlicedPermPlan{{cdiv(L, lc), lc, rounds, dr, wr, sp.G > 1 ? -sp.G : sp.W}};
+
+    std::vector<float> sz(o.sorted_z ? (size_t)(L * N) : 0);
+    std::vector<int32_t> hz(o.index_z ? (size_t)(L * N) : 0);
+    float* K = cv.ptr(k_r);
+    uint32_t* I = cv.ptr(i_r);
+    float* one = cv.ptr(one_r);
+    float* zero = cv.ptr(zero_r);
+    const SlicedSortScratch sc{cv.ptr(tmp_r), cv.ptr(itmp_r), cv.ptr(counts_r), cv.ptr(bases_r)};
+    const float* A = one_leads ? one : zero;
+    const float* B = one_leads ? zero : one;
+    const int64_t a_pad = one_leads ? n_pad : m_pad, b_pad = one_leads ? m_pad : n_pad;
+    for (int64_t l0 = 0; l0 < L; l0 += lc) {
+        const int64_t cur = std::min(lc, L - l0);
+        FAD_TRY(sliced_project_sort(cx, pp.z, theta, cv.ptr(zeros_r), l0, cur, K, z_pad, I, sc, cv.ptr(flag_r)));
+        FAD_TRY(sliced_stage(sz, l0, N, K, z_pad, cur, st));
+        FAD_TRY(sliced_stage(hz, l0, N, I, z_pad, cur, st));
+        for (int64_t d0 = 0; d0 < cur; d0 += dr)
+            for (int64_t w0 = 0; w0 < W; w0 += wr) {
+                const int64_t dc = std::min(dr, cur - d0), wc = std::min(wr, W - w0), nq = std::min(32 * wc, NL - 32 * w0), pairs = dc * nq;
+                const ssplit::Args a{K + d0 * z_pad, I + d0 * z_pad, z_pad, N, pp.cols_d + w0 * z_pad, z_pad, dc, wc, G, nq,
+                                     cv.ptr(scounts_r), one, zero, n_pad, m_pad, n, m};
+                FAD_HIP_TRY(ssplit::split_segments(a, st));
+                sliced_match_kernel<false><<<(unsigned int)(pairs * nblk), kMatchBlock, 0, st>>>(A, nullptr, a_pad, na, B, b_pad, nb, nblk, nullptr,
+                                                                                                cv.ptr(slots_r), nullptr);
+                FAD_HIP_TRY(hipGetLastError());
+                sliced_finish_kernel<<<(unsigned int)cdiv(pairs, 256), 256, 0, st>>>(cv.ptr(slots_r), nblk, pairs, cv.ptr(sround_r));
+                FAD_HIP_TRY(hipGetLastError());
+                FAD_HIP_TRY(hipMemcpy2DAsync(cv.ptr(s_r) + (l0 + d0) * NL + 32 * w0, (size_t)NL * sizeof(double), cv.ptr(sround_r),
+                                             (size_t)nq * sizeof(double), (size_t)nq * sizeof(double), (size_t)dc, hipMemcpyDeviceToDevice, st));
+            }
+    }
+    std::vector<double> S((size_t)(L * NL));
+    unsigned int flag = 0;
+    FAD_HIP_TRY(hipMemcpyAsync(S.data(), cv.ptr(s_r), S.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    FAD_HIP_TRY(hipMemcpyAsync(&flag, cv.ptr(flag_r), sizeof(flag), hipMemcpyDeviceToHost, st));
+    FAD_HIP_TRY(hipStreamSynchronize(st));
+    if (flag) return set_error(FAD_ERR_NOT_FINITE, "%s: a projection is not finite in float32", who);
+
+    // per labelling the statistics of fad_sliced_wasserstein over its L values, S at a stride of NL; then the two counts, in float64
+    const double nm = (double)(n * m);
+    std::vector<double> Wv(o.values ? (size_t)(NL * L) : (size_t)L), T((size_t)NL), M((size_t)NL);
+    SlicedStats obs{};
+    for (int64_t u = 0; u < NL; ++u) {
+        const SlicedStats t = sliced_stats(S.data() + u, NL, nm, dirs.q, Wv.data() + (o.values ? u * L : 0));
+        T[(size_t)u] = t.mean; M[(size_t)u] = t.best;
+        if (u == 0) obs = t;
+    }
+    int64_t ge = 0, ge_max = 0;
+    for (int64_t p = 0; p < n_perm; ++p) {
+        null_out[p] = T[(size_t)(p + 1)];
+        null_max[p] = M[(size_t)(p + 1)];
+        ge += T[(size_t)(p + 1)] >= T[0];
+        ge_max += M[(size_t)(p + 1)] >= M[0];
+    }
+    out->observed.sw2_squared = obs.mean; out->observed.std_error = obs.std_error;
+    out->observed.max_sliced = obs.best; out->observed.max_index = obs.best_l;
+    out->observed.n = n; out->observed.m = m; out->observed.projections = projections;
+    out->p_value = (double)(1 + ge) / (double)NL;
+    out->p_value_max = (double)(1 + ge_max) / (double)NL;
+    out->permutations = n_perm;
+    if (o.values) memcpy(o.values, Wv.data(), Wv.size() * sizeof(double));
+    if (o.sorted_z) memcpy(o.sorted_z, sz.data(), sz.size() * sizeof(float));
+    if (o.index_z) memcpy(o.index_z, hz.data(), hz.size() * sizeof(int32_t));
     return FAD_OK;
 }
 
@@ -4443,6 +4588,29 @@ int fad_sliced_last_plan(int64_t out[4]) {
     if (!out) return set_error(FAD_ERR_INVALID, "fad_sliced_last_plan: NULL output");
     const SlicedPlan& p = sliced_plan_value();
     out[0] = p.chunks; out[1] = p.lc; out[2] = p.passes; out[3] = p.share;
+    return FAD_OK;
+}
+
+int fad_sliced_permutation_test(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype,
+                                int on_device, const float* directions, int projections, const uint32_t* labels, int64_t n_perm,
+                                int labels_on_device, fad_sliced_permutation_result_t* out, double* null_out, double* null_max,
+                                fad_sliced_permutation_detail_t* detail, int device, void* stream) {
+    using namespace fad;
+    begin_entry();
+    sliced_perm_plan_value() = SlicedPermPlan{{0, 0, 0, 0, 0, 0}};
+    const char* who = "fad_sliced_permutation_test";
+    if (!out || !null_out || !null_max) return set_error(FAD_ERR_INVALID, "%s: NULL output", who);
+    SlicedPermOut o{};
+    if (detail) { o.values = detail->values; o.sorted_z = detail->sorted_z; o.index_z = detail->index_z; }
+    return sliced_permutation(who, x, n, ldx, y, m, ldy, d, dtype, on_device, directions, projections, labels, n_perm, labels_on_device, out,
+                              null_out, null_max, o, device, stream);
+}
+
+int fad_sliced_permutation_last_plan(int64_t out[6]) {
+    using namespace fad;
+    if (!out) return set_error(FAD_ERR_INVALID, "fad_sliced_permutation_last_plan: NULL output");
+    const SlicedPermPlan& p = sliced_perm_plan_value();
+    for (int i = 0; i < 6; ++i) out[i] = p.v[i];
     return FAD_OK;
 }
 

@@ -1354,3 +1354,43 @@ def sliced_individual_last_plan() -> dict:
     out = (C.c_int64 * 6)()
     K.check(K.load_library().fad_sliced_individual_last_plan(out), "fad_sliced_individual_last_plan")
     return dict(zip(("chunks", "directions_per_chunk", "units", "long_songs", "most_songs", "capacity"), map(int, out)))
+
+
+# ------------------------------------------------------------------------ sliced Wasserstein two-sample permutation test
+def sliced_permutation_test(x, y, labels, directions, device: int = 0, per_labelling: bool = False, stages: bool = False) -> dict:
+    """``fad_sliced_permutation_test``: the two-sample permutation test with the sliced 2-Wasserstein distance as its statistic, on the
+    pooled rows Z = [x; y] -> dict of fad_sliced_result for the observed labelling (bit for bit ``sliced_wasserstein(x, y, directions)``),
+    ``null`` and ``null_max`` [P] (the mean and the maximum over the directions under every labelling of ``labels``), ``p_value`` =
+    (1 + #{null >= sw2_squared}) / (P + 1), ``p_value_max`` the same with the maxima, and ``permutations`` = P.  ``labels`` as
+    ``kad_permutation_test`` takes them; the observed labelling is added by the library.  ``per_labelling=True`` adds the float64 array
+    ``values`` [P + 1, L] (row 0 the observed labelling); ``stages=True`` adds ``sorted_z`` (float32) and ``index_z`` (int32) [L x N]: the
+    sorted pooled projections and the pooled row at every rank."""
+    lib = K.load_library()
+    (px, n, d, ldx, cx, dev_x, kx), (py, m, dy, ldy, cy, dev_y, ky) = _sliced_rows(x, y, "y", device)
+    t = sliced_directions_array(directions, d)
+    L = t.shape[0]
+    pl, P, dev_l, kl = _kad_labels(labels, n + m, device)
+    if not 1 <= P <= KAD_MAX_PERMUTATIONS:
+        raise ValueError(f"sliced Wasserstein permutation test takes 1 .. {KAD_MAX_PERMUTATIONS} labellings, got {P}")
+    res = K.FadSlicedPermutationResult()
+    null = np.zeros(P)
+    null_max = np.zeros(P)
+    arrays = {}
+    if per_labelling:
+        arrays["values"] = np.zeros((P + 1, L))
+    if stages:
+        arrays["sorted_z"] = np.zeros((L, n + m), dtype=np.float32)
+        arrays["index_z"] = np.zeros((L, n + m), dtype=np.int32)
+    K.check(lib.fad_sliced_permutation_test(px, n, ldx, py, m, ldy, d, cx, dev_x, t.ctypes.data, L, pl, P, dev_l, C.byref(res),
+                                            null.ctypes.data, null_max.ctypes.data, _sliced_detail(K.FadSlicedPermutationDetail, arrays),
+                                            int(device), K.current_stream_ptr(device)), "fad_sliced_permutation_test")
+    return {**res.as_dict(), "null": null, "null_max": null_max, **arrays}
+
+
+def sliced_permutation_last_plan() -> dict:
+    """``fad_sliced_permutation_last_plan``: how this thread's last fad_sliced_permutation_test call was laid out -> dict of
+    ``sort_chunks``, ``directions_per_sort_chunk``, ``rounds`` (pair rounds in all), ``directions_per_round``, ``words_per_round``
+    (labelling words of 32) and ``share`` (as ``sliced_last_plan``, of the pooled rows)."""
+    out = (C.c_int64 * 6)()
+    K.check(K.load_library().fad_sliced_permutation_last_plan(out), "fad_sliced_permutation_last_plan")
+    return dict(zip(("sort_chunks", "directions_per_sort_chunk", "rounds", "directions_per_round", "words_per_round", "share"), map(int, out)))

@@ -250,6 +250,73 @@ def calc_sliced_wasserstein_shares(x, y, projections: int = 512, seed: int = 0, 
     return out
 
 
+MAX_PERMUTATIONS = 65536
+
+
+def check_permutations(permutations) -> int:
+    """-> permutations, or a ValueError: not an integer in 1 .. 65536."""
+    if isinstance(permutations, bool) or int(permutations) != permutations or not 1 <= int(permutations) <= MAX_PERMUTATIONS:
+        raise ValueError(f"sliced Wasserstein permutation test takes 1 .. {MAX_PERMUTATIONS} permutations, got {permutations!r}")
+    return int(permutations)
+
+
+def _check_labels(labels, N: int) -> None:
+    """the shape of given labellings, or a ValueError -- before the native library is loaded: [P, N] 0/1 (bool / uint8) or
+    [P, ceil(N / 32)] packed 32-bit words, P in 1 .. 65536"""
+    if not hasattr(labels, "dtype"):
+        labels = np.asarray(labels)
+    sh = tuple(labels.shape)
+    words = (N + 31) // 32
+    kind = str(labels.dtype).replace("torch.", "")
+    if len(sh) != 2:
+        raise ValueError(f"sliced Wasserstein permutation test: labels must be 2-D, got shape {sh}")
+    want = N if kind in ("bool", "uint8") else words
+    if sh[1] != want:
+        raise ValueError(f"sliced Wasserstein permutation test: labels of shape {sh} and dtype {kind}; 0/1 labels have N = {N} columns, "
+                         f"packed 32-bit words ceil(N / 32) = {words}")
+    check_permutations(sh[0])
+
+
+def calc_sliced_wasserstein_permutation_test(x, y, permutations: int = 1000, projections: int = 512, seed: int = 0, directions=None,
+                                             labels=None, return_labels: bool = False, per_labelling: bool = False,
+                                             device: int = 0) -> dict:
+    """Is y distinguishable from the baseline x at all?  The two-sample permutation test with the sliced 2-Wasserstein distance as its
+    statistic (``fad_sliced_permutation_test``): no bandwidth, no pair pass.  The pooled rows are projected and sorted
+    once per direction; each of ``permutations`` random relabellings that hold the sizes at n and m splits the sorted projections into
+    its two sorted groups, and the statistic is recomputed -- all labellings in one GPU call.  Labellings come from
+    ``kad.random_labellings`` (the same seed gives the KAD and k-NN tests' labellings) unless ``labels`` gives them (bool / uint8 [P, N]
+    or packed words [P, ceil(N / 32)]); the directions as ``calc_sliced_wasserstein`` (``seed`` seeds both).  -> everything
+    ``calc_sliced_wasserstein(x, y)`` returns, with its bits, plus ``p_value`` = (1 + #{null >= sw2_squared}) / (P + 1), ``p_value_max``
+    (the same with the largest slice: sensitive to a difference that lives in few directions), ``null`` and ``null_max`` [P],
+    ``permutations``, ``seed`` (None when labels or directions are given) and, on request, ``values`` [P + 1, L] (row 0 the observed
+    labelling) and ``labels``."""
+    n, m, d = _check(x, y)
+    given = directions is not None or labels is not None
+    if directions is None:
+        directions = sliced_directions(d, projections, seed)
+    else:
+        from .hip import sliced_directions_array
+        directions = sliced_directions_array(directions, d)
+    if labels is None:
+        permutations = check_permutations(permutations)
+        from .kad import random_labellings
+        labels = random_labellings(n, m, permutations, seed=seed, device=device)
+    else:
+        _check_labels(labels, n + m)
+    from . import hip
+    x, y = _one_dtype(x, y)
+    res = hip.sliced_permutation_test(x, y, labels, directions, device=device, per_labelling=per_labelling)
+    out = {"sw2_squared": res["sw2_squared"], "sliced_w2": math.sqrt(max(res["sw2_squared"], 0.0)), "std_error": res["std_error"],
+           "max_sliced": res["max_sliced"], "max_index": res["max_index"], "fad_scale": d * res["sw2_squared"], "n": res["n"],
+           "m": res["m"], "projections": res["projections"], "seed": None if given else seed, "p_value": res["p_value"],
+           "p_value_max": res["p_value_max"], "null": res["null"], "null_max": res["null_max"], "permutations": int(res["permutations"])}
+    if per_labelling:
+        out["values"] = res["values"]
+    if return_labels:
+        out["labels"] = labels
+    return out
+
+
 def check_csv(target: PathLike, header: str = CSV_HEADER) -> None:
     """Refuse (ValueError) an existing CSV whose first line is not ``header`` (CSV_HEADER; INDIV_CSV_HEADER for the per-song file)."""
     if Path(target).is_file():
@@ -335,6 +402,16 @@ class SlicedWasserstein:
             x, y = x.astype(np.float32), y.astype(np.float32)
         return calc_sliced_wasserstein(x, y, projections=self.projections, seed=self.seed, per_direction=per_direction,
                                        device=self.device_index)
+
+    def score_permutation_test(self, baseline: PathLike, eval_dir: PathLike, permutations: int = 1000) -> dict:
+        """calc_sliced_wasserstein_permutation_test of all rows of ``eval_dir`` against all rows of ``baseline``: the directions and the
+        labellings both from this object's seed."""
+        permutations = check_permutations(permutations)
+        x, y = self.kad.load_rows(baseline), self.kad.load_rows(eval_dir)
+        if x.dtype != y.dtype or x.dtype == np.float64:          # float64 caches and mixed dtypes go to float32
+            x, y = x.astype(np.float32), y.astype(np.float32)
+        return calc_sliced_wasserstein_permutation_test(x, y, permutations=permutations, projections=self.projections, seed=self.seed,
+                                                        device=self.device_index)
 
     def score_individual(self, baseline: PathLike, eval_dir: PathLike, csv: PathLike = INDIV_CSV_NAME) -> Path:
         """calc_sliced_wasserstein_individual of every file of ``eval_dir`` against all rows of ``baseline``, written to ``csv`` under

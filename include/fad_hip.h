@@ -761,6 +761,61 @@ int fad_sliced_shares(const void* x, int64_t n, int64_t ldx, const void* y, int6
                       double* share_x /* host, [n] */, double* share_y /* host, [m] */,
                       fad_sliced_shares_detail_t* detail /* may be NULL */, int device, void* stream);
 
+/* ------------------------------------------------------------------ sliced 2-Wasserstein two-sample permutation test
+ * Not in the reference.  "Is y distinguishable from x at all", with the sliced distance as the statistic: no bandwidth, no pair pass.
+ * Rows, directions, their rounding to the rows' dtype, q_l and the float32 projections are fad_sliced_wasserstein's.  Z = [x; y],
+ * N = n + m.  A labelling u is a 0/1 vector over Z's rows with exactly n ones, given as packed bits in fad_kad_permutation_test's
+ * layout (labels [n_perm x ceil(N / 32)] uint32, bit j % 32 of word j / 32 = row j; host or device); the library puts the observed
+ * labelling (the first n rows) in front: NL = n_perm + 1 labellings, u_0 the observed one.
+ * Per direction l and labelling u: a = the sorted projections of the rows with u = 1, b = those with u = 0,
+ *   W_l(u) = S_l(a, b) / ((double)(n m) q_l),
+ * S_l exactly as fad_sliced_wasserstein forms it: the same integer weights, float64 with every operation rounded once and no fused
+ * multiply-add; the larger group leads (the label-1 group at n == m); per leading element over its j ascending, blocks of 256 by the
+ * halving tree, the blocks in index order, one division.  Per labelling, over l in index order as fad_sliced_wasserstein's statistics:
+ *   T(u) = mean_l W_l(u)      M(u) = max_l W_l(u)
+ *   observed = the fad_sliced_result_t of u_0;  null[p] = T(u_{p+1}),  null_max[p] = M(u_{p+1})   (host, [n_perm], required)
+ *   p_value = (1 + #{p : null[p] >= T(u_0)}) / (n_perm + 1);  p_value_max the same with M -- the max-sliced test, sensitive to a
+ *   difference that lives in few directions.  Both counts compare float64 values on the host; ties count (>=).
+ *   detail (may be NULL; each array NULL or host): values [NL x L], labelling-major, row 0 the observed labelling; sorted_z [L x N] and
+ *   index_z [L x N]: the sorted pooled projections and the pooled row at every rank (equal keys in ascending row order).
+ * How: the pooled rows are projected and sorted once per direction (csrc/sliced_sort_pairs.h).  A labelling splits that one sorted array
+ * into its two sorted groups by a stable compaction (csrc/sliced_split.h: the place of a key is a function of its rank alone), 32
+ * labellings per gathered label word; fad_sliced_wasserstein's match and finish kernels then run over the (direction, labelling) pairs
+ * as if they were directions.  No sort per labelling.
+ * Exactness: the sorted pooled projections and the row indices never see a label, and every labelling, the observed one included, goes
+ * through the same kernels.  So under exchangeability of the pooled rows both p-values are exact, whatever float32 rounding did to the
+ * projections.
+ * Contract: observed and values[0] have the bits of fad_sliced_wasserstein(x, y, directions); values[p] has the bits of
+ * fad_sliced_wasserstein(Z[u_p], Z[~u_p], directions), rows taken in ascending pooled order; the same bits on every run, for any
+ * chunking of directions and of labelling words, and for swapped arguments with complemented labellings.  No floating-point atomics.
+ * Refusals: everything fad_sliced_wasserstein refuses about rows and directions, with its codes; n or m < 1 -> FAD_ERR_TOO_FEW_ROWS;
+ * N >= 2^31 - 128, a NULL out, null, null_max or labels, n_perm outside 1 .. 65536, a host labelling whose count of ones is not n or
+ * that has a bit at or past N -> FAD_ERR_INVALID, all before any device call; device labellings are checked on the device, with the
+ * same code; a NaN/Inf row norm or a projection that is not finite in float32 -> FAD_ERR_NOT_FINITE.  Any refusal leaves every output
+ * untouched (results are staged in host memory until the call succeeds).
+ * Workspace: Z's image, the directions' and the labellings with their words as fad_kad_permutation_test keeps them; then, per
+ * direction of a sort chunk, 16 bytes per padded pooled row (keys, rows, their second buffers) and the sort's counts; per (direction,
+ * labelling) pair of a round 4 (n_pad + m_pad) bytes of split keys, 8 per 256 rows of the larger set and 4 per 2048 pooled rows; and
+ * 8 L NL bytes of sums.  Sort chunks take a quarter of 1 GiB (or of FAD_SLICED_WORKSPACE), rounds of (directions of the chunk) x
+ * (labelling words) the rest; never less than one direction per chunk nor than one direction x one word per round.
+ * Synchronises `stream`. */
+typedef struct fad_sliced_permutation_result {
+    fad_sliced_result_t observed;
+    double p_value, p_value_max;
+    int64_t permutations;
+} fad_sliced_permutation_result_t;
+typedef struct fad_sliced_permutation_detail {
+    double* values;      /* [NL x L]  W_l(u), labelling-major, may be NULL */
+    float* sorted_z;     /* [L x N]   may be NULL */
+    int32_t* index_z;    /* [L x N]   may be NULL */
+} fad_sliced_permutation_detail_t;
+int fad_sliced_permutation_test(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype,
+                                int on_device, const float* directions /* host, [L x d] */, int projections,
+                                const uint32_t* labels /* [n_perm x ceil(N / 32)] */, int64_t n_perm, int labels_on_device,
+                                fad_sliced_permutation_result_t* out, double* null /* [n_perm] host */,
+                                double* null_max /* [n_perm] host */, fad_sliced_permutation_detail_t* detail /* may be NULL */,
+                                int device, void* stream);
+
 /* ------------------------------------------------------------------ diagnostics (NOT part of the drop-in surface)
  * Nothing in fadtk corresponds to these two calls and no binding of the reference needs them: they exist for bench.py's
  * roofline object (HIP events around the tile kernel on the stream it is launched on) and for the GPU tests that check
@@ -800,6 +855,11 @@ int fad_sliced_last_plan(int64_t out[4]);
  * units per direction, songs on the long path (more than C rows), most songs in one unit, C }; all 0 when the call was refused
  * before it planned. */
 int fad_sliced_individual_last_plan(int64_t out[6]);
+
+/* Diagnostic: how the last fad_sliced_permutation_test call of this thread was laid out.  out = { sort chunks, directions per sort
+ * chunk, pair rounds in all, directions per round, labelling words per round, share }; all 0 when the call was refused before it
+ * planned.  share is fad_sliced_last_plan's, of the pooled rows' segments in a full sort chunk. */
+int fad_sliced_permutation_last_plan(int64_t out[6]);
 
 /* A HIP stream confined to a subset of the device's CUs (hipExtStreamCreateWithCUMask; `mask` = `words` x 32 bits, bit i = CU i in
  * the runtime's numbering, which on this 8-XCD part walks the XCDs first: bit i -> XCD i % 8).  bench.py's --chain-cus layout
