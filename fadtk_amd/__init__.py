@@ -41,7 +41,8 @@ def __getattr__(name):
         from . import sinkhorn
         return getattr(sinkhorn, name)
     if name in ("SlicedWasserstein", "calc_sliced_wasserstein", "calc_sliced_wasserstein_individual", "calc_sliced_wasserstein_shares",
-                "calc_sliced_wasserstein_permutation_test", "sliced_directions"):      # lazy, as KAD's
+                "calc_sliced_wasserstein_permutation_test", "calc_sliced_wasserstein_bootstrap",
+                "calc_sliced_wasserstein_bootstrap_compare", "bootstrap_counts", "sliced_directions"):      # lazy, as KAD's
         from . import sliced
         return getattr(sliced, name)
     if name == "cache_embedding_files":

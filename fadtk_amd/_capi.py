@@ -135,6 +135,18 @@ class FadSlicedPermutationDetail(C.Structure):
     _fields_ = [("values", C.c_void_p), ("sorted_z", C.c_void_p), ("index_z", C.c_void_p)]
 
 
+class FadSlicedBootstrapResult(C.Structure):
+    _fields_ = [("observed", FadSlicedResult), ("replicates", C.c_int64)]
+
+    def as_dict(self):
+        return {**self.observed.as_dict(), "replicates": self.replicates}
+
+
+class FadSlicedBootstrapDetail(C.Structure):
+    _fields_ = [("values", C.c_void_p), ("sorted_x", C.c_void_p), ("index_x", C.c_void_p), ("sorted_y", C.c_void_p), ("index_y", C.c_void_p),
+                ("totals", C.c_void_p)]
+
+
 _P = C.c_void_p
 _I64 = C.c_int64
 # name -> (restype, argtypes)     -- one entry per declaration in include/fad_hip.h
@@ -232,6 +244,9 @@ SIGNATURES = {
                                               C.POINTER(FadSlicedPermutationResult), _P, _P, C.POINTER(FadSlicedPermutationDetail),
                                               C.c_int, _P]),
     "fad_sliced_permutation_last_plan": (C.c_int, [C.POINTER(_I64)]),
+    "fad_sliced_bootstrap": (C.c_int, [_P, _I64, _I64, _P, _I64, _I64, _I64, C.c_int, C.c_int, _P, C.c_int, _P, _P, _I64,
+                                       C.POINTER(FadSlicedBootstrapResult), _P, _P, C.POINTER(FadSlicedBootstrapDetail), C.c_int, _P]),
+    "fad_sliced_bootstrap_last_plan": (C.c_int, [C.POINTER(_I64)]),
     "fad_sinkhorn": (C.c_int, [_P, _I64, _I64, _P, _I64, _I64, _I64, C.c_int, C.c_int, C.c_double, C.c_int, C.POINTER(FadSinkhornResult),
                                C.POINTER(FadSinkhornDetail), C.c_int, _P]),
 }

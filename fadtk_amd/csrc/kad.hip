@@ -31,6 +31,7 @@
 #include "sliced_sort_pairs.h"
 #include "sliced_song_sort.h"
 #include "sliced_split.h"
+#include "sliced_expand.h"
 
 #include <algorithm>
 #include <cmath>
@@ -839,6 +840,41 @@ __global__ void __launch_bounds__(256) sliced_finish_kernel(const double* __rest
     double s = 0.0;
     for (int64_t k = 0; k < nblk; ++k) s += slots[l * nblk + k];
     S[l] = s;
+}
+
+// ------------------------------------------------------------------------------- sliced Wasserstein bootstrap
+// sliced_match_kernel<false> with sizes per pair: pair p = blockIdx.x / nblk is replicate q = p % nq of its direction, its sorted sets
+// x + p px [nx[q]] and y + p py [ny[q]].  The larger set leads, x at a tie, as in sliced_sets; block k takes the leading elements
+// [256 k, 256 k + 256), each its sliced_overlap_sum, then the tree into slot p nblk + k.  nblk is the launch's (the largest leading set's):
+// a pair's blocks past its own ceil(na / 256) leave at once and their slots are never read.
+__global__ void __launch_bounds__(kMatchBlock) sliced_match_sized_kernel(const float* __restrict__ x, int64_t px, const float* __restrict__ y,
+                                                                         int64_t py, const int32_t* __restrict__ nx,
+                                                                         const int32_t* __restrict__ ny, int64_t nq, int64_t nblk,
+                                                                         double* __restrict__ slots) {
+    const int64_t p = blockIdx.x / nblk, k = blockIdx.x % nblk, i = k * kMatchBlock + threadIdx.x;
+    const int64_t n = nx[p % nq], m = ny[p % nq];
+    const bool x_larger = n >= m;
+    const int64_t na = x_larger ? n : m, nb = x_larger ? m : n;
+    if (k * kMatchBlock >= na) return;                                                 // the whole workgroup
+    const float* a = x_larger ? x + p * px : y + p * py;
+    const float* b = x_larger ? y + p * py : x + p * px;
+    double s = 0.0;
+    if (i < na) s = sliced_overlap_sum((double)a[i], i, na, b, nb);
+    sliced_tree_store(s, slots);
+}
+
+// S[p] = the pair's own ceil(na / 256) slots summed in index order, one thread per pair of the launch
+__global__ void __launch_bounds__(256) sliced_finish_sized_kernel(const double* __restrict__ slots, int64_t nblk, const int32_t* __restrict__ nx,
+                                                                  const int32_t* __restrict__ ny, int64_t nq, int64_t pairs,
+                                                                  double* __restrict__ S) {
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= pairs) return;
+    const int64_t n = nx[p % nq], m = ny[p % nq], na = n >= m ? n : m;
+    int64_t mine = (na + kMatchBlock - 1) / kMatchBlock;
+    if (mine > nblk) mine = nblk;                                                      // always false; keeps a wrong size inside the pair's slots
+    double s = 0.0;
+    for (int64_t k = 0; k < mine; ++k) s += slots[p * nblk + k];
+    S[p] = s;
 }
 
 // ------------------------------------------------------------------------------------ sliced Wasserstein per-row shares
@@ -3527,6 +3563,202 @@ static int sliced_permutation(const char* who, const void* x, int64_t n, int64_t
     return FAD_OK;
 }
 
+// ------------------------------------------------------------------------------- sliced Wasserstein bootstrap
+// fad_sliced_bootstrap_last_plan: sort chunks, directions per sort chunk, rounds in all, directions per round, replicate words per
+// round, replicates per word
+struct SlicedBootPlan { int64_t v[6]; };
+static SlicedBootPlan& sliced_boot_plan_value() {
+    static thread_local SlicedBootPlan p{{0, 0, 0, 0, 0, 0}};
+    return p;
+}
+
+constexpr int64_t kBootMax = 65536;
+
+// fad_sliced_bootstrap's detail.  All host; every pointer may be NULL.
+struct SlicedBootOut { double* values; float* sorted_x; int32_t* index_x; float* sorted_y; int32_t* index_y; int64_t* totals; };
+
+// One side's replicates on the host: the all-ones replicate in front of the caller's n_boot, every replicate's total, and the count
+// words as sexpand takes them (cols [W x pad], byte b of word w of a row = its count in replicate 4 w + b; 0 past the last replicate).
+struct BootSide {
+    std::vector<int64_t> total;
+    std::vector<uint32_t> cols;
+    int64_t most = 0;
+
+    int sum(const uint8_t* counts, int64_t rows, int64_t n_boot, const char* side, const char* who) {
+        total.assign((size_t)(n_boot + 1), 0);
+        total[0] = most = rows;
+        for (int64_t b = 0; b < n_boot; ++b) {
+            int64_t t = 0;
+            for (int64_t i = 0; i < rows; ++i) t += counts[b * rows + i];
+            if (t < 1) return set_error(FAD_ERR_INVALID, "%s: replicate %lld takes no row of %s", who, (long long)b, side);
+            if (t > INT32_MAX - kTile)
+                return set_error(FAD_ERR_INVALID, "%s: replicate %lld takes %lld rows of %s (at most %d)", who, (long long)b, (long long)t, side,
+                                 INT32_MAX - kTile);
+            total[(size_t)(b + 1)] = t;
+            most = std::max(most, t);
+        }
+        return FAD_OK;
+    }
+    void pack(const uint8_t* counts, int64_t rows, int64_t pad) {
+        const int64_t NB = (int64_t)total.size(), W = sexpand::words(NB);
+        cols.assign((size_t)(W * pad), 0u);
+        for (int64_t q = 0; q < NB; ++q) {
+            uint32_t* w = cols.data() + (q / sexpand::kPerWord) * pad;
+            const int shift = 8 * (int)(q % sexpand::kPerWord);
+            if (q == 0) for (int64_t i = 0; i < rows; ++i) w[i] |= 1u << shift;
+            else for (int64_t i = 0; i < rows; ++i) w[i] |= (uint32_t)counts[(q - 1) * rows + i] << shift;
+        }
+    }
+};
+
+// fad_sliced_bootstrap.  x and y are each projected and sorted once per direction, with the row at every rank (sliced_project_sort's
+// key-index form).  A round takes some directions of the sort chunk and some replicate words: sexpand's stable expansion gives every
+// (direction, replicate) pair of the round its two sorted resamples, and sliced_match_sized_kernel and sliced_finish_sized_kernel run
+// over the pairs with every replicate's own sizes.  S [L][NB] stays on the device until every round has run.
+static int sliced_bootstrap(const char* who, const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype,
+                            int on_device, const float* directions, int projections, const uint8_t* counts_x, const uint8_t* counts_y,
+                            int64_t n_boot, fad_sliced_bootstrap_result_t* out, double* boot, double* boot_max, const SlicedBootOut& o,
+                            int device, void* stream) {
+    if (!x || !y) return set_error(FAD_ERR_INVALID, "%s: NULL rows", who);
+    FAD_TRY(sliced_check_args(who, directions, dtype, d, ldx, &ldy, projections));
+    if (n < 1 || m < 1) return set_error(FAD_ERR_TOO_FEW_ROWS, "%s: needs at least 1 row per set, got %lld and %lld", who, (long long)n, (long long)m);
+    if (n > INT32_MAX - kTile || m > INT32_MAX - kTile)
+        return set_error(FAD_ERR_INVALID, "%s: %lld and %lld rows (at most %d per set)", who, (long long)n, (long long)m, INT32_MAX - kTile);
+    if (n > (((int64_t)1 << 53) - 1) / m)
+        return set_error(FAD_ERR_INVALID, "%s: n m = %lld x %lld is 2^53 or more: the integer weights would not be exact in float64", who,
+                         (long long)n, (long long)m);
+    if (n_boot < 1 || n_boot > kBootMax)
+        return set_error(FAD_ERR_INVALID, "%s: %lld replicates (1 .. %lld)", who, (long long)n_boot, (long long)kBootMax);
+    if (!counts_x || !counts_y) return set_error(FAD_ERR_INVALID, "%s: NULL counts", who);
+    const int64_t L = projections, NB = n_boot + 1, W = sexpand::words(NB);
+    SlicedDirections dirs;                                     // before any device call
+    FAD_TRY(dirs.build(directions, L, d, dtype, who));
+    BootSide bx, by;
+    FAD_TRY(bx.sum(counts_x, n, n_boot, "x", who));
+    FAD_TRY(by.sum(counts_y, m, n_boot, "y", who));
+    for (int64_t u = 0; u < NB; ++u)
+        if (bx.total[(size_t)u] > (((int64_t)1 << 53) - 1) / by.total[(size_t)u])
+            return set_error(FAD_ERR_INVALID, "%s: replicate %lld has n m = %lld x %lld, 2^53 or more: the integer weights would not be exact "
+                             "in float64", who, (long long)(u - 1), (long long)bx.total[(size_t)u], (long long)by.total[(size_t)u]);
+    const int64_t budget = sliced_budget();
+    const int64_t n_pad = kad::blocks(n) * kTile, m_pad = kad::blocks(m) * kTile, t_pad = std::max(n_pad, m_pad);
+    bx.pack(counts_x, n, n_pad);
+    by.pack(counts_y, m, m_pad);
+    std::vector<int32_t> sizes((size_t)(2 * NB));              // every replicate's total of x, then of y
+    for (int64_t u = 0; u < NB; ++u) { sizes[(size_t)u] = (int32_t)bx.total[(size_t)u]; sizes[(size_t)(NB + u)] = (int32_t)by.total[(size_t)u]; }
+
+    Ctx cx;
+    FAD_TRY(cx.open(dtype, FAD_KAD_GAUSSIAN, device, stream));
+    const hipStream_t st = cx.st;
+    Packed px, py;                                             // each set packed once, its norms checked finite
+    FAD_TRY(pack_set(cx, 0, x, n, ldx, d, on_device, &px));
+    FAD_TRY(pack_set(cx, 1, y, m, ldy, d, on_device, &py));
+    const char* theta;
+    FAD_TRY(dirs.upload(cx, &theta));
+
+    // the sort chunk: lc directions' keys and rows of both sets, the sort's second buffers and counts -- a quarter of the budget.  The
+    // round: dr directions x wr replicate words, 4 pairs a word, each pair its two expanded sets at the pitch of the largest replicate,
+    // its match slots and the expansion's counts (x's, then y's in the same words).
+    const int64_t xp = kad::blocks(bx.most) * kTile, yp = kad::blocks(by.most) * kTile;
+    const int64_t nblk = cdiv(std::max(bx.most, by.most), kMatchBlock), G = std::max(sexpand::groups(n), sexpand::groups(m));
+    const int64_t count_words = std::max(ssort::counts_elems(n, 1), ssort::counts_elems(m, 1));
+    const int64_t per_dir = 8 * (n_pad + m_pad + t_pad) + 4 * (count_words + ssort::kRadix);
+    const int64_t lc = std::max<int64_t>(1, std::min<int64_t>(L, budget / 4 / per_dir));
+    const int64_t per_word = sexpand::kPerWord * (4 * (xp + yp) + 8 * nblk + 4 * G + 8);
+    const int64_t most = (int64_t)INT32_MAX / (sexpand::kPerWord * std::max(nblk, G)); // words a launch's grid can hold
+    const int64_t units = std::max<int64_t>(1, std::min(most, (budget - budget / 4) / per_word));
+    const int64_t wr = std::min(W, units), dr = units >= W ? std::min(lc, units / W) : 1;
+    Carve cv;
+    const auto kx_r = cv.add<float>(lc * n_pad), ky_r = cv.add<float>(lc * m_pad), tmp_r = cv.add<float>(lc * t_pad);
+    const auto ix_r = cv.add<uint32_t>(lc * n_pad), iy_r = cv.add<uint32_t>(lc * m_pad), itmp_r = cv.add<uint32_t>(lc * t_pad);
+    const auto counts_r = cv.add<uint32_t>(lc * count_words), bases_r = cv.add<uint32_t>(lc * ssort::kRadix);
+    const auto ex_r = cv.add<float>(dr * wr * sexpand::kPerWord * xp), ey_r = cv.add<float>(dr * wr * sexpand::kPerWord * yp);
+    const auto slots_r = cv.add<double>(dr * wr * sexpand::kPerWord * nblk), sround_r = cv.add<double>(dr * wr * sexpand::kPerWord);
+    const auto ecounts_r = cv.add<uint32_t>(dr * wr * G * sexpand::kPerWord);
+    const auto colsx_r = cv.add<uint32_t>(W * n_pad), colsy_r = cv.add<uint32_t>(W * m_pad);
+    const auto sizes_r = cv.add<int32_t>(2 * NB);
+    const auto s_r = cv.add<double>(L * NB);
+    const auto zeros_r = cv.add<float>(std::max(t_pad, dirs.l_img));
+    const auto flag_r = cv.add<unsigned int>(64);
+    FAD_TRY(cv.reserve(cx.ws->sliced));
+    FAD_HIP_TRY(hipMemsetAsync(cv.ptr(zeros_r), 0, (size_t)std::max(t_pad, dirs.l_img) * sizeof(float), st));
+    FAD_HIP_TRY(hipMemsetAsync(cv.ptr(flag_r), 0, 64 * sizeof(unsigned int), st));
+    FAD_HIP_TRY(hipMemcpyAsync(cv.ptr(colsx_r), bx.cols.data(), bx.cols.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    FAD_HIP_TRY(hipMemcpyAsync(cv.ptr(colsy_r), by.cols.data(), by.cols.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    FAD_HIP_TRY(hipMemcpyAsync(cv.ptr(sizes_r), sizes.data(), sizes.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    int64_t rounds = 0;
+    for (int64_t l0 = 0; l0 < L; l0 += lc) rounds += cdiv(std::min(lc, L - l0), dr) * cdiv(W, wr);
+    sliced_boot_plan_value() = SlicedBootPlan{{cdiv(L, lc), lc, rounds, dr, wr, sexpand::kPerWord}};
+
+    std::vector<float> sx(o.sorted_x ? (size_t)(L * n) : 0), sy(o.sorted_y ? (size_t)(L * m) : 0);
+    std::vector<int32_t> hx(o.index_x ? (size_t)(L * n) : 0), hy(o.index_y ? (size_t)(L * m) : 0);
+    float* Kx = cv.ptr(kx_r);
+    float* Ky = cv.ptr(ky_r);
+    uint32_t* Ix = cv.ptr(ix_r);
+    uint32_t* Iy = cv.ptr(iy_r);
+    float* Ex = cv.ptr(ex_r);
+    float* Ey = cv.ptr(ey_r);
+    const int32_t* tx = cv.ptr(sizes_r);
+    const int32_t* ty = tx + NB;
+    const SlicedSortScratch sc{cv.ptr(tmp_r), cv.ptr(itmp_r), cv.ptr(counts_r), cv.ptr(bases_r)};
+    for (int64_t l0 = 0; l0 < L; l0 += lc) {
+        const int64_t cur = std::min(lc, L - l0);
+        FAD_TRY(sliced_project_sort(cx, px, theta, cv.ptr(zeros_r), l0, cur, Kx, n_pad, Ix, sc, cv.ptr(flag_r)));
+        FAD_TRY(sliced_project_sort(cx, py, theta, cv.ptr(zeros_r), l0, cur, Ky, m_pad, Iy, sc, cv.ptr(flag_r)));
+        FAD_TRY(sliced_stage(sx, l0, n, Kx, n_pad, cur, st));
+        FAD_TRY(sliced_stage(sy, l0, m, Ky, m_pad, cur, st));
+        FAD_TRY(sliced_stage(hx, l0, n, Ix, n_pad, cur, st));
+        FAD_TRY(sliced_stage(hy, l0, m, Iy, m_pad, cur, st));
+        for (int64_t d0 = 0; d0 < cur; d0 += dr)
+            for (int64_t w0 = 0; w0 < W; w0 += wr) {
+                const int64_t dc = std::min(dr, cur - d0), wc = std::min(wr, W - w0), q0 = sexpand::kPerWord * w0;
+                const int64_t nq = std::min(sexpand::kPerWord * wc, NB - q0), pairs = dc * nq;
+                const sexpand::Args ax{Kx + d0 * n_pad, Ix + d0 * n_pad, n_pad, n, cv.ptr(colsx_r) + w0 * n_pad, n_pad, dc, wc,
+                                       sexpand::groups(n), nq, cv.ptr(ecounts_r), Ex, xp, tx + q0};
+                const sexpand::Args ay{Ky + d0 * m_pad, Iy + d0 * m_pad, m_pad, m, cv.ptr(colsy_r) + w0 * m_pad, m_pad, dc, wc,
+                                       sexpand::groups(m), nq, cv.ptr(ecounts_r), Ey, yp, ty + q0};
+                FAD_HIP_TRY(sexpand::expand_segments(ax, st));
+                FAD_HIP_TRY(sexpand::expand_segments(ay, st));
+                sliced_match_sized_kernel<<<(unsigned int)(pairs * nblk), kMatchBlock, 0, st>>>(Ex, xp, Ey, yp, tx + q0, ty + q0, nq, nblk,
+                                                                                              cv.ptr(slots_r));
+                FAD_HIP_TRY(hipGetLastError());
+                sliced_finish_sized_kernel<<<(unsigned int)cdiv(pairs, 256), 256, 0, st>>>(cv.ptr(slots_r), nblk, tx + q0, ty + q0, nq, pairs,
+                                                                                         cv.ptr(sround_r));
+                FAD_HIP_TRY(hipGetLastError());
+                FAD_HIP_TRY(hipMemcpy2DAsync(cv.ptr(s_r) + (l0 + d0) * NB + q0, (size_t)NB * sizeof(double), cv.ptr(sround_r),
+                                             (size_t)nq * sizeof(double), (size_t)nq * sizeof(double), (size_t)dc, hipMemcpyDeviceToDevice, st));
+            }
+    }
+    std::vector<double> S((size_t)(L * NB));
+    unsigned int flag = 0;
+    FAD_HIP_TRY(hipMemcpyAsync(S.data(), cv.ptr(s_r), S.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    FAD_HIP_TRY(hipMemcpyAsync(&flag, cv.ptr(flag_r), sizeof(flag), hipMemcpyDeviceToHost, st));
+    FAD_HIP_TRY(hipStreamSynchronize(st));
+    if (flag) return set_error(FAD_ERR_NOT_FINITE, "%s: a projection is not finite in float32", who);
+
+    // per replicate the statistics of fad_sliced_wasserstein over its L values, S at a stride of NB, with the replicate's own n m
+    std::vector<double> Wv(o.values ? (size_t)(NB * L) : (size_t)L);
+    SlicedStats obs{};
+    for (int64_t u = 0; u < NB; ++u) {
+        const double nm = (double)(bx.total[(size_t)u] * by.total[(size_t)u]);
+        const SlicedStats t = sliced_stats(S.data() + u, NB, nm, dirs.q, Wv.data() + (o.values ? u * L : 0));
+        if (u == 0) obs = t;
+        else { boot[u - 1] = t.mean; boot_max[u - 1] = t.best; }
+    }
+    out->observed.sw2_squared = obs.mean; out->observed.std_error = obs.std_error;
+    out->observed.max_sliced = obs.best; out->observed.max_index = obs.best_l;
+    out->observed.n = n; out->observed.m = m; out->observed.projections = projections;
+    out->replicates = n_boot;
+    if (o.values) memcpy(o.values, Wv.data(), Wv.size() * sizeof(double));
+    if (o.sorted_x) memcpy(o.sorted_x, sx.data(), sx.size() * sizeof(float));
+    if (o.sorted_y) memcpy(o.sorted_y, sy.data(), sy.size() * sizeof(float));
+    if (o.index_x) memcpy(o.index_x, hx.data(), hx.size() * sizeof(int32_t));
+    if (o.index_y) memcpy(o.index_y, hy.data(), hy.size() * sizeof(int32_t));
+    if (o.totals)
+        for (int64_t u = 0; u < NB; ++u) { o.totals[2 * u] = bx.total[(size_t)u]; o.totals[2 * u + 1] = by.total[(size_t)u]; }
+    return FAD_OK;
+}
+
 // What fad_sliced_individual writes: five values per song and, where not NULL, its detail's arrays.  All host.
 struct SlicedSongOut {
     double* sw2; double* std_error; double* max_sliced; int64_t* max_index; int32_t* status;
@@ -4610,6 +4842,32 @@ int fad_sliced_permutation_last_plan(int64_t out[6]) {
     using namespace fad;
     if (!out) return set_error(FAD_ERR_INVALID, "fad_sliced_permutation_last_plan: NULL output");
     const SlicedPermPlan& p = sliced_perm_plan_value();
+    for (int i = 0; i < 6; ++i) out[i] = p.v[i];
+    return FAD_OK;
+}
+
+int fad_sliced_bootstrap(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype, int on_device,
+                         const float* directions, int projections, const uint8_t* counts_x, const uint8_t* counts_y, int64_t n_boot,
+                         fad_sliced_bootstrap_result_t* out, double* boot, double* boot_max, fad_sliced_bootstrap_detail_t* detail,
+                         int device, void* stream) {
+    using namespace fad;
+    begin_entry();
+    sliced_boot_plan_value() = SlicedBootPlan{{0, 0, 0, 0, 0, 0}};
+    const char* who = "fad_sliced_bootstrap";
+    if (!out || !boot || !boot_max) return set_error(FAD_ERR_INVALID, "%s: NULL output", who);
+    SlicedBootOut o{};
+    if (detail) {
+        o.values = detail->values; o.sorted_x = detail->sorted_x; o.index_x = detail->index_x;
+        o.sorted_y = detail->sorted_y; o.index_y = detail->index_y; o.totals = detail->totals;
+    }
+    return sliced_bootstrap(who, x, n, ldx, y, m, ldy, d, dtype, on_device, directions, projections, counts_x, counts_y, n_boot, out, boot,
+                            boot_max, o, device, stream);
+}
+
+int fad_sliced_bootstrap_last_plan(int64_t out[6]) {
+    using namespace fad;
+    if (!out) return set_error(FAD_ERR_INVALID, "fad_sliced_bootstrap_last_plan: NULL output");
+    const SlicedBootPlan& p = sliced_boot_plan_value();
     for (int i = 0; i < 6; ++i) out[i] = p.v[i];
     return FAD_OK;
 }

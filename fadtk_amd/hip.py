@@ -1394,3 +1394,63 @@ def sliced_permutation_last_plan() -> dict:
     out = (C.c_int64 * 6)()
     K.check(K.load_library().fad_sliced_permutation_last_plan(out), "fad_sliced_permutation_last_plan")
     return dict(zip(("sort_chunks", "directions_per_sort_chunk", "rounds", "directions_per_round", "words_per_round", "share"), map(int, out)))
+
+
+# ------------------------------------------------------------------------ sliced Wasserstein bootstrap
+SLICED_MAX_REPLICATES = 65536
+
+
+def sliced_bootstrap_counts_array(counts, rows: int, name: str) -> np.ndarray:
+    """-> ``counts`` as the C ABI takes them: a C-contiguous uint8 [B x rows] array, B in 1 .. 65536.  Anything else is a ValueError,
+    raised before the native library is touched."""
+    if not isinstance(counts, np.ndarray) or counts.dtype != np.uint8 or counts.ndim != 2 or counts.shape[1] != rows:
+        raise ValueError(f"sliced Wasserstein bootstrap: {name} must be a uint8 array [B x {rows}], got "
+                         f"{getattr(counts, 'dtype', type(counts).__name__)} {getattr(counts, 'shape', '')}")
+    if not 1 <= counts.shape[0] <= SLICED_MAX_REPLICATES:
+        raise ValueError(f"sliced Wasserstein bootstrap takes 1 .. {SLICED_MAX_REPLICATES} replicates, got {counts.shape[0]}")
+    return np.ascontiguousarray(counts)
+
+
+def sliced_bootstrap(x, y, counts_x, counts_y, directions, device: int = 0, per_replicate: bool = False, stages: bool = False) -> dict:
+    """``fad_sliced_bootstrap``: the sliced 2-Wasserstein distance on B resamples of both sets, each given as uint8 row counts
+    (``counts_x`` [B x n], ``counts_y`` [B x m]) -> dict of fad_sliced_result for the sets as given (bit for bit
+    ``sliced_wasserstein(x, y, directions)``), ``boot`` and ``boot_max`` [B] (the mean and the maximum over the directions on every
+    resample, bit for bit ``sliced_wasserstein(np.repeat(x, counts_x[b], 0), np.repeat(y, counts_y[b], 0), directions)``) and
+    ``replicates`` = B.  ``per_replicate=True`` adds the float64 array ``values`` [B + 1, L] (row 0 the sets as given) and the int64
+    array ``totals`` [B + 1, 2] (the rows of x and of y every replicate takes); ``stages=True`` adds ``sorted_x``, ``sorted_y`` (float32)
+    and ``index_x``, ``index_y`` (int32) as ``sliced_shares`` gives them."""
+    (px, n, d, ldx, cx, dev_x, kx), (py, m, dy, ldy, cy, dev_y, ky) = _sliced_rows(x, y, "y", device)
+    t = sliced_directions_array(directions, d)
+    L = t.shape[0]
+    ca = sliced_bootstrap_counts_array(counts_x, n, "counts_x")
+    cb = sliced_bootstrap_counts_array(counts_y, m, "counts_y")
+    B = ca.shape[0]
+    if cb.shape[0] != B:
+        raise ValueError(f"sliced Wasserstein bootstrap: counts_x has {B} replicates, counts_y has {cb.shape[0]}")
+    lib = K.load_library()
+    res = K.FadSlicedBootstrapResult()
+    boot = np.zeros(B)
+    boot_max = np.zeros(B)
+    arrays = {}
+    if per_replicate:
+        arrays["values"] = np.zeros((B + 1, L))
+        arrays["totals"] = np.zeros((B + 1, 2), dtype=np.int64)
+    if stages:
+        arrays["sorted_x"] = np.zeros((L, n), dtype=np.float32)
+        arrays["index_x"] = np.zeros((L, n), dtype=np.int32)
+        arrays["sorted_y"] = np.zeros((L, m), dtype=np.float32)
+        arrays["index_y"] = np.zeros((L, m), dtype=np.int32)
+    K.check(lib.fad_sliced_bootstrap(px, n, ldx, py, m, ldy, d, cx, dev_x, t.ctypes.data, L, ca.ctypes.data, cb.ctypes.data, B, C.byref(res),
+                                     boot.ctypes.data, boot_max.ctypes.data, _sliced_detail(K.FadSlicedBootstrapDetail, arrays),
+                                     int(device), K.current_stream_ptr(device)), "fad_sliced_bootstrap")
+    return {**res.as_dict(), "boot": boot, "boot_max": boot_max, **arrays}
+
+
+def sliced_bootstrap_last_plan() -> dict:
+    """``fad_sliced_bootstrap_last_plan``: how this thread's last fad_sliced_bootstrap call was laid out -> dict of ``sort_chunks``,
+    ``directions_per_sort_chunk``, ``rounds`` (rounds in all), ``directions_per_round``, ``words_per_round`` (replicate words) and
+    ``replicates_per_word``."""
+    out = (C.c_int64 * 6)()
+    K.check(K.load_library().fad_sliced_bootstrap_last_plan(out), "fad_sliced_bootstrap_last_plan")
+    return dict(zip(("sort_chunks", "directions_per_sort_chunk", "rounds", "directions_per_round", "words_per_round", "replicates_per_word"),
+                    map(int, out)))

@@ -23,6 +23,10 @@ rows' shares), ``fraction`` (of ``sw2_squared``) and ``lift`` (fraction / the fi
 carries the distance in proportion to its length); the baseline's files first, each side sorted by ``share`` descending.  A baseline
 file with a high lift holds rows the evaluation set does not cover (mode dropping); an evaluation file with one holds rows far from
 the baseline.
+
+The two-sample permutation test (``calc_sliced_wasserstein_permutation_test``) and the bootstrap intervals
+(``calc_sliced_wasserstein_bootstrap``, ``calc_sliced_wasserstein_bootstrap_compare``, ``bootstrap_counts``) have command
+lines of their own: ``python -m fadtk_amd.sliced_permutation`` and ``python -m fadtk_amd.sliced_bootstrap``.
 """
 from __future__ import annotations
 
@@ -317,6 +321,164 @@ def calc_sliced_wasserstein_permutation_test(x, y, permutations: int = 1000, pro
     return out
 
 
+MAX_REPLICATES = 65536
+
+
+def check_bootstrap(replicates=1000, confidence=0.95):
+    """-> (replicates, confidence), or a ValueError: replicates not an integer in 1 .. 65536, confidence not strictly between 0 and 1."""
+    if isinstance(replicates, bool) or int(replicates) != replicates or not 1 <= int(replicates) <= MAX_REPLICATES:
+        raise ValueError(f"sliced Wasserstein bootstrap takes 1 .. {MAX_REPLICATES} replicates, got {replicates!r}")
+    if isinstance(confidence, bool) or not 0.0 < float(confidence) < 1.0:
+        raise ValueError(f"sliced Wasserstein bootstrap: confidence must lie strictly between 0 and 1, got {confidence!r}")
+    return int(replicates), float(confidence)
+
+
+def bootstrap_counts(sizes, replicates: int = 1000, seed: int = 0, stream: int = 0) -> np.ndarray:
+    """The resamples of one set as row counts -> uint8 [replicates x rows].  ``sizes`` is the row count of every resampling unit:
+    ``np.ones(n, int)`` resamples rows, ``np.diff(offsets)`` resamples files (all rows of a file move together, because the frames of
+    one song are not independent).  Units without rows are left out of the pool.  With F units in the pool and
+    ``rng = np.random.default_rng([seed, stream])``, for each replicate in order: the units' counts are
+    ``np.bincount(rng.integers(0, F, size=F), minlength=F)`` and a row's count is its unit's.  A count above 255 is a ValueError.
+    ``stream`` 0 is the baseline's, 1 + k the k-th evaluation set's: the baseline's resamples are the same whichever set they meet,
+    which is what makes comparisons of sets paired."""
+    sizes = np.asarray(sizes)
+    if sizes.ndim != 1 or (sizes.size and not np.all(sizes == np.floor(sizes))) or np.any(sizes < 0):
+        raise ValueError("sliced Wasserstein bootstrap: sizes must be a 1-D sequence of row counts >= 0")
+    sizes = sizes.astype(np.int64)
+    replicates, _ = check_bootstrap(replicates)
+    _, seed = check_params(1, seed)
+    if isinstance(stream, bool) or int(stream) != stream or int(stream) < 0:
+        raise ValueError(f"sliced Wasserstein bootstrap: stream must be an integer >= 0, got {stream!r}")
+    pool = np.flatnonzero(sizes > 0)
+    F = int(pool.size)
+    if F < 1:
+        raise ValueError("sliced Wasserstein bootstrap: no resampling unit has a row")
+    rng = np.random.default_rng([seed, int(stream)])
+    out = np.zeros((replicates, int(sizes.sum())), dtype=np.uint8)
+    for b in range(replicates):
+        units = np.bincount(rng.integers(0, F, size=F), minlength=F)
+        if units.max() > 255:
+            raise ValueError(f"sliced Wasserstein bootstrap: replicate {b} draws one unit {int(units.max())} times (at most 255)")
+        out[b] = np.repeat(units, sizes[pool]).astype(np.uint8)
+    return out
+
+
+def bootstrap_statistics(boot, observed: float, confidence: float = 0.95) -> dict:
+    """The interval statistics of the replicates ``boot`` [B] around the plug-in value ``observed`` -> dict: ``boot_mean``, ``boot_std``
+    (ddof = 1; NaN for one replicate), ``bias`` = boot_mean - observed, ``ci_percentile`` = np.quantile(boot, [(1 - c) / 2, (1 + c) / 2])
+    and ``ci_basic`` = (2 observed - q_hi, 2 observed - q_lo), both as tuples of floats."""
+    boot = np.asarray(boot, dtype=np.float64)
+    _, c = check_bootstrap(1, confidence)
+    lo, hi = (float(v) for v in np.quantile(boot, [(1 - c) / 2, (1 + c) / 2]))
+    mean = float(np.mean(boot))
+    return {"boot_mean": mean, "boot_std": float(np.std(boot, ddof=1)) if boot.size > 1 else float("nan"), "bias": mean - observed,
+            "ci_percentile": (lo, hi), "ci_basic": (2 * observed - hi, 2 * observed - lo)}
+
+
+def bootstrap_difference(boot_i, boot_j, observed_i: float, observed_j: float, confidence: float = 0.95) -> dict:
+    """Two evaluation sets on one baseline, replicate by replicate (the baseline's resamples shared) -> dict: ``diff`` [B] =
+    boot_i - boot_j, ``diff_observed``, ``ci_diff`` (the percentile interval of diff) and ``prob_closer`` (the share of replicates with
+    diff < 0: set i closer to the baseline than set j)."""
+    diff = np.asarray(boot_i, dtype=np.float64) - np.asarray(boot_j, dtype=np.float64)
+    _, c = check_bootstrap(1, confidence)
+    lo, hi = (float(v) for v in np.quantile(diff, [(1 - c) / 2, (1 + c) / 2]))
+    return {"diff": diff, "diff_observed": observed_i - observed_j, "ci_diff": (lo, hi), "prob_closer": float(np.mean(diff < 0))}
+
+
+def _bootstrap_side(counts, offsets, rows: int, name: str, replicates: int, seed: int, stream: int):
+    """one side's counts and unit: given counts (uint8 [B x rows], checked), else drawn over the files of ``offsets`` or over the rows"""
+    off = _check_offsets(offsets, rows, f"{name}_offsets") if offsets is not None else None
+    unit = "row" if off is None else "file"
+    if counts is not None:
+        from .hip import sliced_bootstrap_counts_array
+        return sliced_bootstrap_counts_array(counts, rows, f"counts_{name}"), unit
+    return bootstrap_counts(np.ones(rows, dtype=np.int64) if off is None else np.diff(off), replicates, seed, stream), unit
+
+
+def calc_sliced_wasserstein_bootstrap(x, y, replicates: int = 1000, confidence: float = 0.95, projections: int = 512, seed: int = 0,
+                                      directions=None, x_offsets=None, y_offsets=None, counts_x=None, counts_y=None,
+                                      per_replicate: bool = False, device: int = 0, y_stream: int = 1) -> dict:
+    """How certain is the sliced 2-Wasserstein distance of y against the baseline x?  The bootstrap over the ROWS' sampling variability
+    (``std_error`` is only the Monte-Carlo error over the directions): both sets are resampled with replacement ``replicates`` times and
+    the distance is recomputed on every resample, all in one GPU call (``fad_sliced_bootstrap``, DESIGN.md 4.21: both sets are sorted
+    once per direction and every resample expands the sorted arrays by its row counts).  With ``x_offsets`` / ``y_offsets`` [F + 1] whole
+    files are resampled on that side, which is right when the frames of a song are not independent; without, rows.  Counts come from
+    ``bootstrap_counts`` (stream 0 for x, ``y_stream`` for y) unless ``counts_x`` / ``counts_y`` (uint8 [B x rows]) give them, as
+    ``labels`` does in the permutation test.
+    -> everything ``calc_sliced_wasserstein(x, y)`` returns, with its bits, plus ``boot`` and ``boot_max`` [B] (each the bits of
+    ``calc_sliced_wasserstein`` on ``np.repeat`` of the rows by the counts), ``boot_mean``, ``boot_std`` (ddof = 1), ``bias`` =
+    boot_mean - sw2_squared, ``ci_percentile``, ``ci_basic``, ``replicates``, ``confidence``, ``unit`` (``unit_x``, ``unit_y``: "file"
+    where offsets were given, else "row"; ``unit`` is "file" when either is) and ``seed`` (None when counts or directions are given);
+    with ``per_replicate`` also ``values`` [B + 1, L], ``totals`` [B + 1, 2], ``counts_x`` and ``counts_y``.
+    The plug-in SW2^2 is biased UPWARD: two samples of one distribution give a positive value of order 1/n + 1/m, and resampling adds
+    that bias once more, so ``boot`` sits above ``sw2_squared`` as ``sw2_squared`` sits above the population value.  ``bias`` estimates
+    it, ``ci_basic`` (reflected about the plug-in value) removes it to first order, ``ci_percentile`` does not and lies too high."""
+    n, m, d = _check(x, y)
+    replicates, confidence = check_bootstrap(replicates, confidence)
+    given = directions is not None or counts_x is not None or counts_y is not None
+    cx, unit_x = _bootstrap_side(counts_x, x_offsets, n, "x", replicates, seed, 0)
+    cy, unit_y = _bootstrap_side(counts_y, y_offsets, m, "y", replicates, seed, y_stream)
+    if cx.shape[0] != cy.shape[0]:
+        raise ValueError(f"sliced Wasserstein bootstrap: counts_x has {cx.shape[0]} replicates, counts_y has {cy.shape[0]}")
+    if directions is None:
+        directions = sliced_directions(d, projections, seed)
+    else:
+        from .hip import sliced_directions_array
+        directions = sliced_directions_array(directions, d)
+    from . import hip
+    x, y = _one_dtype(x, y)
+    res = hip.sliced_bootstrap(x, y, cx, cy, directions, device=device, per_replicate=per_replicate)
+    out = {"sw2_squared": res["sw2_squared"], "sliced_w2": math.sqrt(max(res["sw2_squared"], 0.0)), "std_error": res["std_error"],
+           "max_sliced": res["max_sliced"], "max_index": res["max_index"], "fad_scale": d * res["sw2_squared"], "n": res["n"],
+           "m": res["m"], "projections": res["projections"], "seed": None if given else seed, "boot": res["boot"],
+           "boot_max": res["boot_max"], **bootstrap_statistics(res["boot"], res["sw2_squared"], confidence),
+           "replicates": int(res["replicates"]), "confidence": confidence, "unit_x": unit_x, "unit_y": unit_y,
+           "unit": "file" if "file" in (unit_x, unit_y) else "row"}
+    if per_replicate:
+        out.update(values=res["values"], totals=res["totals"], counts_x=cx, counts_y=cy)
+    return out
+
+
+def calc_sliced_wasserstein_bootstrap_compare(x, ys, replicates: int = 1000, confidence: float = 0.95, projections: int = 512,
+                                              seed: int = 0, directions=None, x_offsets=None, ys_offsets=None,
+                                              per_replicate: bool = False, device: int = 0) -> dict:
+    """Is evaluation set A really closer to the baseline x than set B?  One ``calc_sliced_wasserstein_bootstrap`` per set of ``ys``, all
+    with the same directions and the same resamples of the baseline (stream 0 of ``bootstrap_counts``; set k draws from stream 1 + k),
+    so replicate b of every set meets the same resampled baseline and the comparison is paired.  ``ys_offsets``: None, or one offsets
+    array (or None) per set.  -> dict: ``sets`` (the per-set dicts) and ``pairs`` {(i, j): dict for i < j} with ``diff`` [B] =
+    boot_i - boot_j, ``diff_observed``, ``ci_diff`` (the percentile interval of diff) and ``prob_closer`` (the share of replicates in
+    which set i is closer to the baseline than set j), plus ``replicates``, ``confidence`` and ``seed``.
+    The upward bias of the plug-in SW2^2 (see ``calc_sliced_wasserstein_bootstrap``) largely cancels in the difference, because the
+    baseline's part of it is shared; it does NOT cancel when the evaluation sets differ much in size (the 1/m terms differ): compare
+    sets of similar size, or read ``bias`` of both."""
+    ys = list(ys)
+    if not ys:
+        raise ValueError("sliced Wasserstein bootstrap compare needs at least 1 evaluation set")
+    offs = list(ys_offsets) if ys_offsets is not None else [None] * len(ys)
+    if len(offs) != len(ys):
+        raise ValueError(f"sliced Wasserstein bootstrap compare: {len(ys)} sets, {len(offs)} offsets")
+    replicates, confidence = check_bootstrap(replicates, confidence)
+    shapes = [_check(x, y) for y in ys]                        # every set before any work
+    n, d = shapes[0][0], shapes[0][2]
+    own = directions is not None
+    if own:
+        from .hip import sliced_directions_array
+        directions = sliced_directions_array(directions, d)
+    else:
+        directions = sliced_directions(d, projections, seed)
+    cx, _ = _bootstrap_side(None, x_offsets, n, "x", replicates, seed, 0)
+    sets = []
+    for k, (y, off) in enumerate(zip(ys, offs)):
+        r = calc_sliced_wasserstein_bootstrap(x, y, replicates=replicates, confidence=confidence, directions=directions,
+                                              x_offsets=x_offsets, y_offsets=off, counts_x=cx, per_replicate=per_replicate,
+                                              device=device, seed=seed, y_stream=1 + k)
+        r["seed"] = None if own else seed
+        sets.append(r)
+    pairs = {(i, j): bootstrap_difference(sets[i]["boot"], sets[j]["boot"], sets[i]["sw2_squared"], sets[j]["sw2_squared"], confidence)
+             for i in range(len(sets)) for j in range(i + 1, len(sets))}
+    return {"sets": sets, "pairs": pairs, "replicates": replicates, "confidence": confidence, "seed": None if own else seed}
+
+
 def check_csv(target: PathLike, header: str = CSV_HEADER) -> None:
     """Refuse (ValueError) an existing CSV whose first line is not ``header`` (CSV_HEADER; INDIV_CSV_HEADER for the per-song file)."""
     if Path(target).is_file():
@@ -492,6 +654,37 @@ class SlicedWasserstein:
                                              device=self.device_index)
         res["x_files"], res["y_files"] = [f for f, _ in xs], [f for f, _ in ys]
         write_shares_csv(csv, res["x_files"], res["y_files"], res, xo, yo)
+        return res
+
+    def score_bootstrap(self, baseline: PathLike, eval_dirs, replicates: int = 1000, confidence: float = 0.95, rows: bool = False) -> dict:
+        """calc_sliced_wasserstein_bootstrap_compare of all rows of every directory of ``eval_dirs`` against all rows of ``baseline`` ->
+        its result, with ``x_files`` and, per set, ``files``.  Files are the resampling units (one offset per file, built as
+        score_shares builds them) unless ``rows``.  Files are dropped and logged as score_shares drops them; a file with non-finite
+        rows refuses the call.  The directions and the resamples both come from this object's seed."""
+        replicates, confidence = check_bootstrap(replicates, confidence)
+        eval_dirs = list(eval_dirs)
+        if not eval_dirs:
+            raise ValueError("sliced Wasserstein bootstrap needs at least 1 evaluation directory")
+        xs = self._embedding_files(baseline, None)
+        if not xs:
+            raise ValueError(f"sliced Wasserstein bootstrap: no embedding rows under {baseline}")
+        sets = []
+        for e in eval_dirs:
+            ys = self._embedding_files(e, xs[0][1].shape[1])
+            if not ys:
+                raise ValueError(f"sliced Wasserstein bootstrap: no embedding rows under {e}")
+            sets.append(ys)
+        dts = {e.dtype for _, e in xs + [fe for ys in sets for fe in ys]}
+        cast = (lambda e: e.astype(np.float32)) if len(dts) > 1 or np.float64 in dts else (lambda e: e)
+        offsets = lambda fs: np.concatenate([[0], np.cumsum([len(e) for _, e in fs], dtype=np.int64)])      # noqa: E731
+        x = np.concatenate([cast(e) for _, e in xs])
+        res = calc_sliced_wasserstein_bootstrap_compare(
+            x, [np.concatenate([cast(e) for _, e in ys]) for ys in sets], replicates=replicates, confidence=confidence,
+            projections=self.projections, seed=self.seed, x_offsets=None if rows else offsets(xs),
+            ys_offsets=None if rows else [offsets(ys) for ys in sets], device=self.device_index)
+        res["x_files"] = [f for f, _ in xs]
+        for r, ys in zip(res["sets"], sets):
+            r["files"] = [f for f, _ in ys]
         return res
 
 

@@ -816,6 +816,64 @@ int fad_sliced_permutation_test(const void* x, int64_t n, int64_t ldx, const voi
                                 double* null_max /* [n_perm] host */, fad_sliced_permutation_detail_t* detail /* may be NULL */,
                                 int device, void* stream);
 
+/* ------------------------------------------------------------------ sliced 2-Wasserstein bootstrap
+ * Not in the reference.  "How certain is the number": the sliced distance recomputed on resamples of both sets, for an interval on the
+ * distance and, with one baseline resampled alike against several sets, on the difference of two distances.  Rows, directions, their
+ * rounding to the rows' dtype, q_l and the float32 projections are fad_sliced_wasserstein's.
+ * A resample of a set is the set with an integer multiplicity per row: counts_x [n_boot x n] and counts_y [n_boot x m], uint8, host,
+ * replicate-major (row counts of a replicate contiguous).  Who draws them decides the resampling unit: rows one by one, or all rows
+ * of a file together.  The library puts the all-ones replicate in front: NB = n_boot + 1 replicates, replicate 0 the sets as given.
+ * n_b and m_b are the totals of replicate b over x and over y; they differ from replicate to replicate when files are the unit.
+ * Per direction l and replicate b: a = the sorted projections of x with the projection of row i taken counts_x[b][i] times, b the same
+ * of y,
+ *   W_l(b) = S_l(a, b) / ((double)(n_b m_b) q_l),
+ * S_l exactly as fad_sliced_wasserstein forms it on sets of n_b and m_b rows: the same integer weights, float64 with every operation
+ * rounded once and no fused multiply-add; the larger set leads (x at n_b == m_b); per leading element over its j ascending, blocks
+ * of 256 by the halving tree, the blocks in index order, one division.  Per replicate, over l in index order as
+ * fad_sliced_wasserstein's statistics:
+ *   observed = the fad_sliced_result_t of replicate 0;  boot[b] = mean_l W_l(b + 1),  boot_max[b] = max_l W_l(b + 1)   (host, [n_boot],
+ *   required);  replicates = n_boot.  Intervals are the caller's to take from boot (fadtk_amd/sliced.py).
+ *   detail (may be NULL; each array NULL or host): values [NB x L], replicate-major, row 0 the sets as given; sorted_x, sorted_y, index_x,
+ *   index_y as fad_sliced_shares_detail; totals [NB x 2] int64: n_b, m_b.
+ * How: x and y are each projected and sorted once per direction, with the row at every rank (csrc/sliced_sort_pairs.h).  The sorted
+ * projections of a resample are that one sorted array with the key at rank r repeated by the count of its row: a stable expansion
+ * (csrc/sliced_expand.h: the key at rank r goes to the exclusive prefix sum of the counts over the lower ranks and the places behind
+ * it, a function of the rank alone), 4 replicates per gathered word of byte counts.  A match with per-pair sizes then runs over the
+ * (direction, replicate) pairs.  No sort per replicate, no gather of rows.
+ * Contract: observed and values[0] have the bits of fad_sliced_wasserstein(x, y, directions); values[b] has the bits of
+ * fad_sliced_wasserstein(repeat(x, counts_x[b - 1]), repeat(y, counts_y[b - 1]), directions), repeat as numpy.repeat along the rows (rows
+ * in ascending order, copies adjacent); the same bits on every run, for any chunking of directions and of replicate words, and for
+ * swapped arguments with swapped counts; sets of identical bits with identical counts give exactly 0.  No floating-point atomics.
+ * Refusals: everything fad_sliced_wasserstein refuses about rows and directions, with its codes; n or m < 1 -> FAD_ERR_TOO_FEW_ROWS;
+ * a NULL counts_x, counts_y, out, boot or boot_max, n_boot outside 1 .. 65536, a replicate whose total over x or over y is 0 or above
+ * 2^31 - 129, n_b m_b >= 2^53 for a replicate -> FAD_ERR_INVALID, all before any device call; a NaN/Inf row norm or a projection that
+ * is not finite in float32 -> FAD_ERR_NOT_FINITE.  Any refusal leaves every output untouched (results are staged in host memory until
+ * the call succeeds).
+ * Workspace: the two images and the directions'; 4 bytes per padded row and word of 4 replicates (the count words); then, per direction
+ * of a sort chunk, 8 bytes per padded row of x, of y and of the larger of the two (keys, rows, their second buffers) and the sort's
+ * counts; per (direction, replicate) pair of a round 4 (xp + yp) bytes of expanded keys, xp and yp the largest n_b and m_b rounded up
+ * to 128, 8 per 256 rows of the largest replicate and 4 per 2048 rows of the larger set; and 8 L NB bytes of sums.  Sort chunks take a
+ * quarter of 1 GiB (or of FAD_SLICED_WORKSPACE), rounds of (directions of the chunk) x (replicate words) the rest; never less than one
+ * direction per chunk nor than one direction x one word per round.  Synchronises `stream`. */
+typedef struct fad_sliced_bootstrap_result {
+    fad_sliced_result_t observed;
+    int64_t replicates;
+} fad_sliced_bootstrap_result_t;
+typedef struct fad_sliced_bootstrap_detail {
+    double* values;      /* [NB x L]  W_l(b), replicate-major, may be NULL */
+    float* sorted_x;     /* [L x n]   may be NULL */
+    int32_t* index_x;    /* [L x n]   may be NULL */
+    float* sorted_y;     /* [L x m]   may be NULL */
+    int32_t* index_y;    /* [L x m]   may be NULL */
+    int64_t* totals;     /* [NB x 2]  n_b, m_b, may be NULL */
+} fad_sliced_bootstrap_detail_t;
+int fad_sliced_bootstrap(const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int64_t d, int dtype, int on_device,
+                         const float* directions /* host, [L x d] */, int projections,
+                         const uint8_t* counts_x /* host, [n_boot x n] */, const uint8_t* counts_y /* host, [n_boot x m] */,
+                         int64_t n_boot, fad_sliced_bootstrap_result_t* out, double* boot /* [n_boot] host */,
+                         double* boot_max /* [n_boot] host */, fad_sliced_bootstrap_detail_t* detail /* may be NULL */,
+                         int device, void* stream);
+
 /* ------------------------------------------------------------------ diagnostics (NOT part of the drop-in surface)
  * Nothing in fadtk corresponds to these two calls and no binding of the reference needs them: they exist for bench.py's
  * roofline object (HIP events around the tile kernel on the stream it is launched on) and for the GPU tests that check
@@ -860,6 +918,11 @@ int fad_sliced_individual_last_plan(int64_t out[6]);
  * chunk, pair rounds in all, directions per round, labelling words per round, share }; all 0 when the call was refused before it
  * planned.  share is fad_sliced_last_plan's, of the pooled rows' segments in a full sort chunk. */
 int fad_sliced_permutation_last_plan(int64_t out[6]);
+
+/* Diagnostic: how the last fad_sliced_bootstrap call of this thread was laid out.  out = { sort chunks, directions per sort chunk,
+ * rounds in all, directions per round, replicate words per round, replicates per word }; all 0 when the call was refused before it
+ * planned. */
+int fad_sliced_bootstrap_last_plan(int64_t out[6]);
 
 /* A HIP stream confined to a subset of the device's CUs (hipExtStreamCreateWithCUMask; `mask` = `words` x 32 bits, bit i = CU i in
  * the runtime's numbering, which on this 8-XCD part walks the XCDs first: bit i -> XCD i % 8).  bench.py's --chain-cus layout
