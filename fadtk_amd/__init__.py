@@ -45,6 +45,9 @@ def __getattr__(name):
                 "calc_sliced_wasserstein_bootstrap_compare", "bootstrap_counts", "sliced_directions"):      # lazy, as KAD's
         from . import sliced
         return getattr(sliced, name)
+    if name in ("Mauve", "calc_mauve", "calc_kmeans"):      # lazy, as KAD's
+        from . import mauve
+        return getattr(mauve, name)
     if name == "cache_embedding_files":
         from .fad_batch import cache_embedding_files
         return cache_embedding_files

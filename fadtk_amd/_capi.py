@@ -83,6 +83,14 @@ class FadNnTestResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class FadKmeansResult(C.Structure):
+    _fields_ = [("inertia", C.c_double), ("n", C.c_int64), ("k", C.c_int64), ("iterations", C.c_int64), ("converged", C.c_int64),
+                ("changed_last", C.c_int64), ("empty_clusters", C.c_int64), ("assignments", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class FadKidResult(C.Structure):
     _fields_ = [("mmd2", C.c_double), ("kxx_mean", C.c_double), ("kyy_mean", C.c_double), ("kxy_mean", C.c_double),
                 ("gamma", C.c_double), ("coef0", C.c_double), ("degree", C.c_int), ("n", C.c_int64), ("m", C.c_int64)]
@@ -247,6 +255,9 @@ SIGNATURES = {
     "fad_sliced_bootstrap": (C.c_int, [_P, _I64, _I64, _P, _I64, _I64, _I64, C.c_int, C.c_int, _P, C.c_int, _P, _P, _I64,
                                        C.POINTER(FadSlicedBootstrapResult), _P, _P, C.POINTER(FadSlicedBootstrapDetail), C.c_int, _P]),
     "fad_sliced_bootstrap_last_plan": (C.c_int, [C.POINTER(_I64)]),
+    "fad_kmeans": (C.c_int, [C.POINTER(_P), C.POINTER(_I64), C.POINTER(_I64), C.c_int, _I64, C.c_int, C.c_int, _I64, _P, C.c_int, _P, _P, _P,
+                             _P, _P, C.POINTER(FadKmeansResult), C.c_int, _P]),
+    "fad_kmeans_last_plan": (C.c_int, [C.POINTER(_I64)]),
     "fad_sinkhorn": (C.c_int, [_P, _I64, _I64, _P, _I64, _I64, _I64, C.c_int, C.c_int, C.c_double, C.c_int, C.POINTER(FadSinkhornResult),
                                C.POINTER(FadSinkhornDetail), C.c_int, _P]),
 }

@@ -3,7 +3,8 @@
 // KAD's standard errors (4.9), its permutation test (4.10), the nearest baseline rows with authenticity (4.11), KAD at several
 // bandwidths in one pass (4.12), the permutation test at several bandwidths, aggregated (4.13), the leave-one-out k-NN two-sample
 // test on the pooled rows (4.14), the polynomial-kernel distance of the KID protocol (4.15) and the Sinkhorn divergence (4.16) run on
-// the same main loop; the sliced Wasserstein distance (4.17) takes its projections from it.
+// the same main loop; the sliced Wasserstein distance (4.17) takes its projections from it, and Lloyd's k-means (4.22) its assignment
+// (the nearest pass of 4.11 with the centroids as the row operand; csrc/kmeans_update.h has the rest).
 //
 // Every pass is one GEMM-shaped walk over 128 x 128 tiles of a pair space (kad_tiles.h) whose n x m matrix is never stored:
 //   - pack:   each set is copied once into a zero-padded [n_pad x dp] image of its own dtype (dp: D rounded up to 128 bytes, n_pad:
@@ -32,6 +33,7 @@
 #include "sliced_song_sort.h"
 #include "sliced_split.h"
 #include "sliced_expand.h"
+#include "kmeans_update.h"
 
 #include <algorithm>
 #include <cmath>
@@ -2261,12 +2263,13 @@ struct KadWorkspace {
     DevBuf kid_index, kid;                           // fad_kid_subsets: the two index lists; the bad-index count, sums and results
     DevBuf sink_slots, sink;                         // fad_sinkhorn: the column states of a half-step; potentials and sums
     DevBuf sliced_theta, sliced;                     // fad_sliced_wasserstein, fad_sliced_individual: the directions' image; projections, sort scratch and sums
+    DevBuf kmeans;                                   // fad_kmeans: the centroid operand, labels, dist2, the update's scratch (img[1]: the repeated rows)
     void release_all() {
         for (int i = 0; i < 2; ++i) { raw[i].release(); img[i].release(); h[i].release(); }
         slots.release(); small.release(); cross.release(); band.release(); songs.release(); lists.release(); prdc.release();
         unc_slots.release(); unc.release(); perm_lab.release(); perm_rows.release(); perm_cols.release(); perm.release();
         near.release(); kid_index.release(); kid.release(); sink_slots.release(); sink.release();
-        sliced_theta.release(); sliced.release();
+        sliced_theta.release(); sliced.release(); kmeans.release();
     }
 };
 
@@ -3898,6 +3901,210 @@ static int sliced_songs(const char* who, const void* x, int64_t n, int64_t ldx, 
     return FAD_OK;
 }
 
+// ------------------------------------------------------------------------------------------- Lloyd's k-means
+// fad_kmeans_last_plan: planes, launches of the last assignment, update chunk rows, most chunks of one cluster in the last update,
+// iterations, assignments made
+struct KmeansPlan { int64_t v[6]; };
+static KmeansPlan& kmeans_plan_value() {
+    static thread_local KmeansPlan p{{0, 0, 0, 0, 0, 0}};
+    return p;
+}
+
+template <int DT> struct KmeansRow { using type = float; };
+template <> struct KmeansRow<FAD_F16> { using type = _Float16; };
+template <> struct KmeansRow<FAD_BF16> { using type = __bf16; };
+
+static int kmeans_planes(int dtype) { return dtype == FAD_F16 ? 2 : dtype == FAD_BF16 ? 3 : 1; }
+
+// fad_kmeans once its arguments are checked: the pooled rows packed once (and repeated once per plane), then the loop of DESIGN 4.22 --
+// an assignment is nearest_pass with the centroids as the row operand and k = 1, an update is kmeans::update.  The host reads one
+// integer per iteration (the changed labels); everything else stays on the device until the end.
+static int kmeans_run(const Ctx& cx, const RowSet* sets, int n_sets, int64_t N, int64_t d, int on_device, int64_t K, const float* init,
+                      int max_iter, float* centroids, int32_t* labels, int64_t* counts, float* dist2, double* inertia_trace,
+                      fad_kmeans_result_t* out) {
+    KadWorkspace& ws = *cx.ws;
+    const hipStream_t st = cx.st;
+    const size_t es = dtype_size(cx.dtype);
+    const int P = kmeans_planes(cx.dtype);
+    const int64_t z_pad = kad::blocks(N) * kTile, k_pad = kad::blocks(K) * kTile, dp = depth_elems(d, cx.dtype);
+
+    Packed pz;
+    FAD_TRY(pack_sets(cx, sets, n_sets, d, on_device, z_pad, true, &pz));
+    pz.n = N;
+    std::vector<double> info((size_t)(2 * n_sets));
+    FAD_HIP_TRY(hipMemcpyAsync(info.data(), static_cast<double*>(ws.small.p) + 1024, info.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    FAD_HIP_TRY(hipStreamSynchronize(st));
+    double bad_rows = 0.0;
+    for (int i = 0; i < n_sets; ++i) bad_rows += info[(size_t)(2 * i + 1)];
+    if (bad_rows != 0.0)
+        return set_error(FAD_ERR_NOT_FINITE, "fad_kmeans: %lld of %lld rows have a NaN/Inf norm", (long long)bad_rows, (long long)N);
+
+    // float16 rows: the power of two g that the operands are scaled by (kmeans::f16_scale), from the largest row magnitude
+    float g = 1.f;
+    if (cx.dtype == FAD_F16) {
+        unsigned int* max_d = reinterpret_cast<unsigned int*>(static_cast<double*>(ws.small.p) + 1024 + 2 * kmeans::kMaxSets);
+        unsigned int max_bits = 0;
+        FAD_HIP_TRY(hipMemsetAsync(max_d, 0, sizeof(unsigned int), st));
+        const int64_t count = z_pad * dp;
+        kmeans::absmax_f16_kernel<<<(unsigned)std::min<int64_t>(cdiv(count, 256), 4096), 256, 0, st>>>(reinterpret_cast<const uint16_t*>(pz.img),
+                                                                                                     count, max_d);
+        FAD_HIP_TRY(hipGetLastError());
+        FAD_HIP_TRY(hipMemcpyAsync(&max_bits, max_d, sizeof(max_bits), hipMemcpyDeviceToHost, st));
+        FAD_HIP_TRY(hipStreamSynchronize(st));
+        g = kmeans::f16_scale(max_bits);
+    }
+
+    // the column operand: every row (times g) P times side by side, against the P planes of g c; h of the rows times g^2
+    Packed rows = pz;
+    if (P > 1) {
+        FAD_TRY(ws.img[1].reserve((size_t)(z_pad * pz.pitch * P)));
+        FAD_TRY(ws.h[1].reserve((size_t)z_pad * sizeof(float)));
+        FAD_TRY(with_dtype(cx.dtype, [&](auto dt) {
+            using T = typename KmeansRow<decltype(dt)::value>::type;
+            if constexpr (kmeans::Planes<T>::value > 1) {
+                const int64_t vecs = z_pad * (dp / (16 / (int64_t)sizeof(T)));
+                kmeans::replicate_kernel<T><<<(unsigned)cdiv(vecs, 256), 256, 0, st>>>(reinterpret_cast<const T*>(pz.img), z_pad, dp, g,
+                                                                                     static_cast<T*>(ws.img[1].p));
+            }
+        }));
+        float* hs = static_cast<float*>(ws.h[1].p);
+        kmeans::scale_kernel<<<(unsigned)cdiv(z_pad, 256), 256, 0, st>>>(pz.h, g * g, z_pad, hs);
+        FAD_HIP_TRY(hipGetLastError());
+        rows = Packed{static_cast<const char*>(ws.img[1].p), hs, N, pz.pitch * P, pz.nchunks * P, 0.0};
+    }
+
+    const int64_t chunks = kmeans::chunks_bound(N, K), T1 = (int64_t)max_iter + 1;
+    Carve cv;
+    const auto cent_r = cv.add<float>(K * d);
+    const auto cimg_r = cv.add<char>(k_pad * rows.pitch);
+    const auto ch_r = cv.add<float>(k_pad);
+    const auto lab_r = cv.add<int32_t>(2 * N);
+    const auto dist2_r = cv.add<float>(N);
+    const auto keys_r = cv.add<uint32_t>(4 * N);
+    const auto scount_r = cv.add<uint32_t>(kmeans::sort_counts_elems(N));
+    const auto sbase_r = cv.add<uint32_t>(ssort::bases_elems(1));
+    const auto counts_r = cv.add<uint32_t>(K), starts_r = cv.add<uint32_t>(K + 1), chunk0_r = cv.add<uint32_t>(K + 1), stats_r = cv.add<uint32_t>(2);
+    const auto partial_r = cv.add<double>(chunks * d);
+    const auto trace_r = cv.add<double>(T1);
+    const auto flag_r = cv.add<unsigned long long>(2);
+    FAD_TRY(cv.reserve(ws.kmeans));
+    float* cent = cv.ptr(cent_r);
+    char* cimg = cv.ptr(cimg_r);
+    float* ch = cv.ptr(ch_r);
+    int32_t* lab[2] = {cv.ptr(lab_r), cv.ptr(lab_r) + N};
+    float* dist2_d = cv.ptr(dist2_r);
+    kmeans::UpdateScratch w{};
+    w.keys = cv.ptr(keys_r); w.keys_tmp = w.keys + N; w.idx = w.keys + 2 * N; w.idx_tmp = w.keys + 3 * N;
+    w.sort_counts = cv.ptr(scount_r); w.sort_bases = cv.ptr(sbase_r);
+    w.counts = cv.ptr(counts_r); w.starts = cv.ptr(starts_r); w.chunk0 = cv.ptr(chunk0_r); w.stats = cv.ptr(stats_r);
+    w.partial = cv.ptr(partial_r);
+    double* trace_d = cv.ptr(trace_r);
+    unsigned long long* bad_d = cv.ptr(flag_r);
+    unsigned long long* changed_d = bad_d + 1;
+    const PrdcPlan q = prdc_plan(cx, Packed{cimg, ch, K, rows.pitch, rows.nchunks, 0.0}, rows, kad::kNearestEpilogue);
+    FAD_TRY(ws.lists.reserve((size_t)(q.NR * z_pad) * sizeof(uint64_t)));
+    const Packed pc{cimg, ch, K, rows.pitch, rows.nchunks, 0.0};
+
+    // C_0: the given centroids, their planes and h
+    FAD_HIP_TRY(hipMemcpyAsync(cent, init, (size_t)(K * d) * sizeof(float), hipMemcpyHostToDevice, st));
+    FAD_HIP_TRY(hipMemsetAsync(bad_d, 0, 2 * sizeof(unsigned long long), st));
+    FAD_HIP_TRY(hipMemsetAsync(w.stats, 0, 2 * sizeof(uint32_t), st));
+    FAD_TRY(with_dtype(cx.dtype, [&](auto dt) {
+        using T = typename KmeansRow<decltype(dt)::value>::type;
+        kmeans::centroid_finish_kernel<T><<<(unsigned)cdiv(k_pad, 4), 256, 0, st>>>(nullptr, nullptr, nullptr, K, k_pad, d, dp, cent,
+                                                                                 reinterpret_cast<T*>(cimg), ch, g, bad_d);
+    }));
+    unsigned long long bad_cent = 0;
+    FAD_HIP_TRY(hipMemcpyAsync(&bad_cent, bad_d, sizeof(bad_cent), hipMemcpyDeviceToHost, st));
+    FAD_HIP_TRY(hipStreamSynchronize(st));
+    if (bad_cent)
+        return set_error(FAD_ERR_NOT_FINITE, "fad_kmeans: %llu of %lld init centroids are not finite in the rows' dtype (float16 rows: an entry "
+                         "must stay below 32x the largest row entry)", bad_cent, (long long)K);
+
+    int64_t assignments = 0, last_launches = 0;
+    auto assign = [&](int32_t* into) -> int {
+        const int64_t before = kad::plan_tally().launches;
+        FAD_TRY(nearest_pass(cx, pc, rows, false, 1, static_cast<uint64_t*>(ws.lists.p), into, dist2_d));
+        last_launches = kad::plan_tally().launches - before;
+        if (g != 1.f) kmeans::scale_kernel<<<(unsigned)cdiv(N, 256), 256, 0, st>>>(dist2_d, 1.f / (g * g), N, dist2_d);   // d^2 of g x, g c
+        kmeans::inertia_kernel<<<1, 256, 0, st>>>(dist2_d, N, trace_d + assignments);
+        FAD_HIP_TRY(hipGetLastError());
+        ++assignments;
+        return FAD_OK;
+    };
+    // the labels of `now` that differ from `then`: the one integer the host reads per iteration
+    auto changed = [&](const int32_t* now, const int32_t* then, unsigned long long* count) -> int {
+        FAD_HIP_TRY(hipMemsetAsync(changed_d, 0, sizeof(unsigned long long), st));
+        kmeans::labels_changed_kernel<<<(unsigned)cdiv(N, 256), 256, 0, st>>>(now, then, N, changed_d);
+        FAD_HIP_TRY(hipGetLastError());
+        FAD_HIP_TRY(hipMemcpyAsync(count, changed_d, sizeof(*count), hipMemcpyDeviceToHost, st));
+        FAD_HIP_TRY(hipStreamSynchronize(st));
+        return FAD_OK;
+    };
+    auto update = [&](const int32_t* from) -> int {
+        hipError_t e = hipSuccess;
+        FAD_TRY(with_dtype(cx.dtype, [&](auto dt) {
+            using T = typename KmeansRow<decltype(dt)::value>::type;
+            e = kmeans::update<T>(from, N, K, k_pad, d, dp, reinterpret_cast<const T*>(pz.img), pz.pitch / (int64_t)es, w, cent,
+                                  reinterpret_cast<T*>(cimg), ch, g, st);
+        }));
+        FAD_HIP_TRY(e);
+        return FAD_OK;
+    };
+
+    int cur = 0, converged = 0, iterations = 0;
+    long long changed_last = -1;
+    bool updated = false;
+    for (int t = 1; t <= max_iter; ++t) {
+        FAD_TRY(assign(lab[cur]));
+        iterations = t;
+        if (t > 1) {
+            unsigned long long c = 0;
+            FAD_TRY(changed(lab[cur], lab[cur ^ 1], &c));
+            changed_last = (long long)c;
+            if (c == 0) { converged = 1; break; }
+        }
+        FAD_TRY(update(lab[cur]));
+        updated = true;
+        cur ^= 1;
+    }
+    if (!converged) {                                                                 // labels that belong to the returned centroids
+        FAD_TRY(assign(lab[cur]));
+        if (max_iter > 0) {
+            unsigned long long c = 0;
+            FAD_TRY(changed(lab[cur], lab[cur ^ 1], &c));
+            changed_last = (long long)c;
+        }
+    }
+
+    // counts of the returned labels
+    FAD_HIP_TRY(hipMemsetAsync(w.counts, 0, (size_t)K * sizeof(uint32_t), st));
+    kmeans::label_count_kernel<<<(unsigned)cdiv(N, 256), 256, 0, st>>>(lab[cur], N, K, w.keys, w.counts);
+    FAD_HIP_TRY(hipGetLastError());
+    std::vector<uint32_t> counts_h((size_t)K);
+    std::vector<double> trace((size_t)assignments);
+    uint32_t stats[2] = {0, 0};
+    FAD_HIP_TRY(hipMemcpyAsync(counts_h.data(), w.counts, (size_t)K * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    FAD_HIP_TRY(hipMemcpyAsync(trace.data(), trace_d, trace.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    FAD_HIP_TRY(hipMemcpyAsync(stats, w.stats, sizeof(stats), hipMemcpyDeviceToHost, st));
+    FAD_HIP_TRY(hipMemcpyAsync(centroids, cent, (size_t)(K * d) * sizeof(float), hipMemcpyDeviceToHost, st));
+    FAD_HIP_TRY(hipMemcpyAsync(labels, lab[cur], (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (dist2) FAD_HIP_TRY(hipMemcpyAsync(dist2, dist2_d, (size_t)N * sizeof(float), hipMemcpyDeviceToHost, st));
+    FAD_HIP_TRY(hipStreamSynchronize(st));
+
+    int64_t empty = 0;
+    for (int64_t c = 0; c < K; ++c) {
+        counts[c] = (int64_t)counts_h[(size_t)c];
+        empty += counts_h[(size_t)c] == 0;
+    }
+    if (inertia_trace) memcpy(inertia_trace, trace.data(), trace.size() * sizeof(double));
+    out->inertia = trace.back();
+    out->n = N; out->k = K; out->iterations = iterations; out->converged = converged; out->changed_last = changed_last;
+    out->empty_clusters = empty; out->assignments = assignments;
+    kmeans_plan_value() = KmeansPlan{{P, last_launches, kmeans::kChunkRows, updated ? (int64_t)stats[0] : 0, iterations, assignments}};
+    return FAD_OK;
+}
+
 }  // namespace
 
 }  // namespace fad
@@ -4891,6 +5098,47 @@ int fad_sliced_individual_last_plan(int64_t out[6]) {
     using namespace fad;
     if (!out) return set_error(FAD_ERR_INVALID, "fad_sliced_individual_last_plan: NULL output");
     const SlicedSongPlan& p = sliced_song_plan_value();
+    for (int i = 0; i < 6; ++i) out[i] = p.v[i];
+    return FAD_OK;
+}
+
+int fad_kmeans(const void* const* xs, const int64_t* ns, const int64_t* lds, int n_sets, int64_t d, int dtype, int on_device, int64_t k,
+               const float* init, int max_iter, float* centroids, int32_t* labels, int64_t* counts, float* dist2, double* inertia_trace,
+               fad_kmeans_result_t* out, int device, void* stream) {
+    using namespace fad;
+    begin_entry();
+    kmeans_plan_value() = KmeansPlan{{0, 0, 0, 0, 0, 0}};
+    if (!out || !centroids || !labels || !counts) return set_error(FAD_ERR_INVALID, "fad_kmeans: NULL output");
+    if (!xs || !ns || !lds || !init) return set_error(FAD_ERR_INVALID, "fad_kmeans: NULL argument");
+    if (n_sets < 1 || n_sets > kmeans::kMaxSets)
+        return set_error(FAD_ERR_INVALID, "fad_kmeans: %d row sets (1 .. %d)", n_sets, kmeans::kMaxSets);
+    if (max_iter < 0) return set_error(FAD_ERR_INVALID, "fad_kmeans: max_iter = %d is negative", max_iter);
+    int64_t N = 0;
+    RowSet sets[kmeans::kMaxSets];
+    for (int i = 0; i < n_sets; ++i) {
+        if (ns[i] < 1) return set_error(FAD_ERR_TOO_FEW_ROWS, "fad_kmeans: set %d has %lld rows", i, (long long)ns[i]);
+        FAD_TRY(check_rows(xs[i], std::max<int64_t>(ns[i], 2), lds[i], d, dtype, "fad_kmeans"));
+        if (ns[i] > INT32_MAX - kTile - N)
+            return set_error(FAD_ERR_INVALID, "fad_kmeans: more than %d pooled rows", INT32_MAX - kTile);
+        sets[i] = RowSet{xs[i], ns[i], lds[i], N, ns[i]};
+        N += ns[i];
+    }
+    if (k < 1 || k > N || k > kmeans::kMaxClusters)
+        return set_error(FAD_ERR_INVALID, "fad_kmeans: K = %lld is outside 1 .. min(N = %lld, %d)", (long long)k, (long long)N,
+                         kmeans::kMaxClusters);
+    for (int64_t i = 0; i < k * d; ++i)
+        if (!std::isfinite(init[i]))
+            return set_error(FAD_ERR_NOT_FINITE, "fad_kmeans: init centroid %lld has a NaN/Inf entry", (long long)(i / d));
+    sets[n_sets - 1].r_pad = kad::blocks(N) * kTile - sets[n_sets - 1].r0;
+    Ctx cx;
+    FAD_TRY(cx.open(dtype, FAD_KAD_GAUSSIAN, device, stream));
+    return kmeans_run(cx, sets, n_sets, N, d, on_device, k, init, max_iter, centroids, labels, counts, dist2, inertia_trace, out);
+}
+
+int fad_kmeans_last_plan(int64_t out[6]) {
+    using namespace fad;
+    if (!out) return set_error(FAD_ERR_INVALID, "fad_kmeans_last_plan: NULL output");
+    const KmeansPlan& p = kmeans_plan_value();
     for (int i = 0; i < 6; ++i) out[i] = p.v[i];
     return FAD_OK;
 }

@@ -1454,3 +1454,96 @@ def sliced_bootstrap_last_plan() -> dict:
     K.check(K.load_library().fad_sliced_bootstrap_last_plan(out), "fad_sliced_bootstrap_last_plan")
     return dict(zip(("sort_chunks", "directions_per_sort_chunk", "rounds", "directions_per_round", "words_per_round", "replicates_per_word"),
                     map(int, out)))
+
+
+# ------------------------------------------------------------------------ Lloyd's k-means on the pooled rows (MAUVE, PRD curves)
+KMEANS_MAX_CLUSTERS = 65536
+KMEANS_MAX_SETS = 8
+
+
+def kmeans_args(clusters, iterations, n_rows: Optional[int] = None):
+    """-> (K, max_iter) as ``fad_kmeans`` takes them: K an integer in 1 .. min(n_rows, 65 536) (when the pooled row count is given),
+    max_iter an integer >= 0.  Anything else is a ValueError, raised before the native library is touched."""
+    for name, v in (("clusters", clusters), ("iterations", iterations)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"k-means: {name} must be an integer, got {v!r}")
+    k, it = int(clusters), int(iterations)
+    if not 1 <= k <= KMEANS_MAX_CLUSTERS:
+        raise ValueError(f"k-means: clusters must be in 1 .. {KMEANS_MAX_CLUSTERS}, got {k}")
+    if n_rows is not None and k > n_rows:
+        raise ValueError(f"k-means: clusters = {k} needs at least {k} pooled rows, got {n_rows}")
+    if not 0 <= it <= 2 ** 31 - 2:
+        raise ValueError(f"k-means: iterations must be >= 0, got {it}")
+    return k, it
+
+
+def kmeans(sets, init, iterations: int = 100, device: int = 0, return_dist2: bool = True) -> dict:
+    """``fad_kmeans``: Lloyd's k-means on the pooled rows of ``sets`` (one frame matrix or a list of 1 .. 8 of them, pooled in the
+    given order without a copy; numpy arrays or torch tensors of one dtype, float16 / bfloat16 / float32, all on the host or all on
+    the device) from the centroids ``init`` [K, D] (float32) -> dict of ``centroids`` [K, D] float32, ``labels`` [N] int32,
+    ``counts`` [K] int64, ``dist2`` [N] float32 (``return_dist2``), ``inertia_trace`` (float64, one value per assignment made) and
+    fad_kmeans_result (inertia, n, k, iterations, converged, changed_last, empty_clusters, assignments).  ``iterations=0`` is a pure
+    assignment of the rows to ``init``.  The rule is fully determined (include/fad_hip.h): the same bits on every run."""
+    if K._is_torch(sets) or isinstance(sets, np.ndarray):
+        sets = [sets]
+    sets = list(sets)
+    if not 1 <= len(sets) <= KMEANS_MAX_SETS:
+        raise ValueError(f"k-means takes 1 .. {KMEANS_MAX_SETS} row sets, got {len(sets)}")
+    init = np.ascontiguousarray(np.asarray(init, dtype=np.float32))
+    if init.ndim != 2:
+        raise ValueError(f"k-means: init must be [K, D], got shape {init.shape}")
+    k, max_iter = kmeans_args(init.shape[0], iterations)
+    views = []
+    for s, x in enumerate(sets):
+        if K._is_torch(x):
+            import torch
+            ok = x.dtype in (torch.float16, torch.bfloat16, torch.float32)
+        else:
+            x = np.asarray(x)
+            ok = x.dtype in (np.float16, np.float32)
+        if not ok:
+            raise ValueError(f"k-means takes float16, bfloat16 or float32 rows; set {s} is {x.dtype}")
+        views.append(K.rows_view(x, host_bf16=True))
+    d, code, dev = views[0][2], views[0][4], views[0][5]
+    for s, v in enumerate(views):
+        if v[2] != d:
+            raise ValueError(f"k-means: set 0 has D = {d}, set {s} has D = {v[2]}")
+        if v[4] != code or v[5] != dev:
+            raise ValueError("k-means: every set must have the same dtype and live on the same side (host or device)")
+        if v[1] < 1:
+            raise ValueError(f"k-means: set {s} has no rows")
+    if init.shape[1] != d:
+        raise ValueError(f"k-means: init has D = {init.shape[1]}, the rows have D = {d}")
+    N = sum(v[1] for v in views)
+    kmeans_args(k, max_iter, N)
+    if not np.isfinite(init).all():
+        raise ValueError("k-means: init has a NaN/Inf entry")
+    lib = K.load_library()
+    S = len(views)
+    ptrs = (C.c_void_p * S)(*[v[0] for v in views])
+    ns = np.array([v[1] for v in views], dtype=np.int64)
+    lds = np.array([v[3] for v in views], dtype=np.int64)
+    centroids = np.zeros((k, d), np.float32)
+    labels = np.zeros(N, np.int32)
+    counts = np.zeros(k, np.int64)
+    dist2 = np.zeros(N, np.float32) if return_dist2 else None
+    trace = np.zeros(max_iter + 1, np.float64)
+    res = K.FadKmeansResult()
+    K.check(lib.fad_kmeans(ptrs, ns.ctypes.data_as(C.POINTER(C.c_int64)), lds.ctypes.data_as(C.POINTER(C.c_int64)), S, d, code, dev, k,
+                           init.ctypes.data, max_iter, centroids.ctypes.data, labels.ctypes.data, counts.ctypes.data,
+                           dist2.ctypes.data if return_dist2 else None, trace.ctypes.data, C.byref(res), int(device),
+                           K.current_stream_ptr(device)), "fad_kmeans")
+    out = res.as_dict()
+    out.update(centroids=centroids, labels=labels, counts=counts, inertia_trace=trace[:out["assignments"]].copy())
+    if return_dist2:
+        out["dist2"] = dist2
+    return out
+
+
+def kmeans_last_plan() -> dict:
+    """``fad_kmeans_last_plan``: how this thread's last fad_kmeans call ran -> dict of ``planes`` (of the centroid operand),
+    ``assign_launches`` (of the last assignment), ``chunk_rows`` (rows per update chunk), ``max_chunks`` (most chunks one cluster took
+    in the last update), ``iterations`` and ``assignments``."""
+    out = (C.c_int64 * 6)()
+    K.check(K.load_library().fad_kmeans_last_plan(out), "fad_kmeans_last_plan")
+    return dict(zip(("planes", "assign_launches", "chunk_rows", "max_chunks", "iterations", "assignments"), map(int, out)))

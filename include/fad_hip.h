@@ -924,6 +924,37 @@ int fad_sliced_permutation_last_plan(int64_t out[6]);
  * planned. */
 int fad_sliced_bootstrap_last_plan(int64_t out[6]);
 
+/* Lloyd's k-means on the pooled rows of 1 .. 8 row sets, the quantisation under MAUVE and PRD curves
+ * (fadtk_amd/mauve.py).  xs / ns / lds: the sets' rows, row counts and row pitches (the list form of fad_kad_uncertainty), all of one
+ * dtype (float16, bfloat16 or float32), all host or all device; they are pooled in the given order, N rows in all, 1 <= D <= 2048,
+ * ld >= D.  1 <= K <= min(N, 65536).  init [K x D] float32 (host, required: seeding is the caller's), max_iter >= 0.
+ *   Assignment A(C): row i takes the centroid with the smallest key (d^2, index): d^2 is fad_nearest's float32 max(-2 S', 0), formed
+ *     against the float32 centroid (16-bit rows: the centroid enters the main loop as 2 (float16) or 3 (bfloat16) planes of the rows'
+ *     dtype whose sum is the float32 value; h_c = -|c|^2 / 2 from the float32 values); equal d^2 go to the smaller index.
+ *   Update M(A): c_k = float32(sum of the rows of cluster k in float64 / count_k); a cluster without rows keeps its centroid.
+ *   Loop, t = 1 .. max_iter: A_t = A(C_{t-1}); if t > 1 and A_t = A_{t-1}, stop with converged = 1; else C_t = M(A_t).  If the loop
+ *     runs out (and for max_iter = 0, a pure assignment against init) the labels are one more assignment against the last centroids,
+ *     so labels, dist2, counts and inertia always belong to the returned centroids.
+ * Outputs (host): centroids [K x D] float32, labels [N] int32 in pooled order, counts [K] int64, dist2 [N] float32 (may be NULL),
+ * inertia_trace [max_iter + 1] (may be NULL): the float64 sum of dist2 in a fixed order after every assignment made, `assignments`
+ * values.  iterations: the t at which the loop stopped (max_iter when it ran out); changed_last: the labels that differed at the
+ * last comparison of two assignments (-1 when none was made); empty_clusters: the clusters without a row under the returned labels.
+ * No floating-point atomics: the same bits on every run and under every launch cut.  Refusals (outputs untouched): FAD_ERR_INVALID
+ * for bad shapes, K or max_iter, FAD_ERR_TOO_FEW_ROWS for an empty set, FAD_ERR_NOT_FINITE for a row or an init centroid that is not
+ * finite (a float32 init entry past the range of float16 rows included). */
+typedef struct fad_kmeans_result {
+    double inertia;
+    int64_t n, k, iterations, converged, changed_last, empty_clusters, assignments;
+} fad_kmeans_result_t;
+int fad_kmeans(const void* const* xs, const int64_t* ns, const int64_t* lds, int n_sets, int64_t d, int dtype, int on_device, int64_t k,
+               const float* init, int max_iter, float* centroids, int32_t* labels, int64_t* counts, float* dist2, double* inertia_trace,
+               fad_kmeans_result_t* out, int device, void* stream);
+
+/* Diagnostic: how the last fad_kmeans call of this thread ran.  out = { planes of the centroid operand, launches of the last
+ * assignment, rows per update chunk, most chunks one cluster took in the last update, iterations, assignments made }; all 0 when the
+ * call was refused before it ran. */
+int fad_kmeans_last_plan(int64_t out[6]);
+
 /* A HIP stream confined to a subset of the device's CUs (hipExtStreamCreateWithCUMask; `mask` = `words` x 32 bits, bit i = CU i in
  * the runtime's numbering, which on this 8-XCD part walks the XCDs first: bit i -> XCD i % 8).  bench.py's --chain-cus layout
  * experiment puts the square-root chains and the moments kernels on disjoint CU sets with it; nothing in the library uses it.

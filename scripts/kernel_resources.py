@@ -4,13 +4,14 @@ VGPRs the compiler spilled: SGPRs go to VGPR lanes, VGPRs to scratch).
     python scripts/kernel_resources.py [substring ...] > profiles/rNN_kernel_resources.txt
     python scripts/kernel_resources.py nn_test > profiles/nn_test_kernel_resources.txt
 `nn_test` stands for the kernels of fad_nn_test and the ones they sit beside, `kid` for those of fad_kid / fad_kid_subsets and their
-Gaussian twins (GROUPS).  No GPU needed (hipcc cross-compiles gfx950)."""
+Gaussian twins, `kmeans` for the kernels fad_kmeans launches (GROUPS).  No GPU needed (hipcc cross-compiles gfx950)."""
 import re, subprocess, sys, pathlib
 sys.path.insert(0, str(pathlib.Path(__file__).resolve().parents[1]))
 from fadtk_amd import build as B
 
 GROUPS = {"nn_test": ["nearest_self_kernel", "nn_vote_kernel", "nearest_cross_kernel", "nearest_reduce_kernel", "prdc_"],
-          "kid": ["kid_", "kad_pass_kernel", "kad_slots_sum_kernel"]}
+          "kid": ["kid_", "kad_pass_kernel", "kad_slots_sum_kernel"],
+          "kmeans": ["kmeans::", "nearest_cross_kernel", "nearest_reduce_kernel", "kad_pack_kernel", "scatter_pairs_kernel"]}
 want = [n for w in sys.argv[1:] for n in GROUPS.get(w, [w])]
 src = sorted((pathlib.Path(B.__file__).parent / "csrc").glob("*.hip"))
 if want and all(w in GROUPS for w in sys.argv[1:]):
